@@ -1,6 +1,6 @@
 """Benchmark: TT-cores sketched / second (fp64) of the streaming TT sketch on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5] [--scaling weak|strong] [--dump-outputs DIR]
 
 Default workload (BASELINE.json configs[2] / SURVEY.md 8d "C3", the configuration the metric is quoted on):
 TensorTrain d=6, n=200, TT-rank 100, TensorTrainDRM left rank 50 (r_out) / right rank 100, all fp64, synthetic
@@ -15,6 +15,9 @@ Gaussian cores generated on the device.  A step sketches `--batch` such TTs per 
                     At N = 1 this is the weak workload repeated items / batch times per step.
   --config c2|c4|c5 the other BASELINE configurations on one GPU (c5 also shards its 32 terms over N ranks),
                     with the roofline SURVEY.md 8d names for each.
+
+  --dump-outputs DIR  after the timed steps, the sketches the last step computed (inputs are seeded: the same
+                    arguments give the same inputs, so two builds can be compared file by file), see dump_sketches.
 
 Ranks are launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`; the launcher
 only sets RANK / LOCAL_RANK / WORLD_SIZE.  This process never imports torch: the RCCL id travels through
@@ -218,6 +221,49 @@ class Job:
             self.comm = None
 
 
+# --------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20        # every file of one dump together
+DUMP_SAMPLE_COLS = 4096            # entries per sketch in sketch_sample.npy (fewer when the budget is short)
+DUMP_SAMPLE_SEED = 7
+
+
+def dump_sketches(directory, first, packed):
+    """What the timed path's last step computed, as its caller receives it, into directory/<name>.npy (float64):
+
+        psi_<mu>, omega_<mu>  the first sketch of the step whole (Psi cores, Omega matrices)
+        sketch_norms          the 2-norm of every sketch of the step
+        sketch_sample         one row per sketch: its packed entries (Psi cores, then Omega matrices, C order) at one
+                              fixed, seeded set of positions -- the same positions for every run of a configuration
+
+    ``first``: (Psi cores, Omega matrices) of the first sketch, device or host arrays; ``packed``: one callable per
+    sketch returning its packed entries on the host (called one at a time: a batch of sketches never sits on the host
+    at once).  At most DUMP_LIMIT_BYTES in all."""
+    os.makedirs(directory, exist_ok=True)
+    psis, omegas = [np.asarray(a, dtype=np.float64) for a in first[0]], [np.asarray(a, dtype=np.float64) for a in first[1]]
+    size = sum(a.size for a in psis + omegas)
+    n = len(packed)
+    budget = DUMP_LIMIT_BYTES - 8 * n
+    if 8 * size <= budget // 2:         # the first sketch whole only while half the budget is left for the sample
+        for names, arrays in (("psi", psis), ("omega", omegas)):
+            for mu, a in enumerate(arrays):
+                np.save(os.path.join(directory, f"{names}_{mu}.npy"), a)
+        budget -= 8 * size
+    cols = max(1, min(size, DUMP_SAMPLE_COLS, budget // (8 * n)))
+    pos = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(size, cols, replace=False))
+    norms, sample = np.empty(n), np.empty((n, cols))
+    for b, get in enumerate(packed):
+        h = np.asarray(get(), dtype=np.float64).ravel()[:size]
+        norms[b], sample[b] = np.linalg.norm(h), h[pos]
+    np.save(os.path.join(directory, "sketch_norms.npy"), norms)
+    np.save(os.path.join(directory, "sketch_sample.npy"), sample)
+
+
+def dump_sketch_object(directory, sk):
+    """dump_sketches of one sketch as the API returns it (SketchContainer / SketchedTensorTrain)."""
+    psis, omegas = [np.asarray(a) for a in sk.Psi_cores], [np.asarray(a) for a in sk.Omega_mats]
+    dump_sketches(directory, (psis, omegas), [lambda: np.concatenate([a.ravel() for a in psis + omegas])])
+
+
 def prof_classes(nat, reps, labels):
     classes = {}
     for c, label in labels.items():
@@ -321,6 +367,15 @@ def bench_c3(args, job):
     elapsed = job.timed(step, args.steps, args.warmup)
     items_per_step = int(args.items) if strong else B * world
     value = D * items_per_step * args.steps / elapsed
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        # before anything below reuses the buffers: the last step's sketches (collective path: the sum, as rank 0 holds it)
+        nat.call("ttsk_sync", -1)
+        if comm_on:
+            last = [sums[(counter[0] - 1) % nslots]]
+        else:
+            buf = outs[0] if strong else outs[(counter[0] - 1) % inflight]
+            last = [buf[b * stride:b * stride + plan.size] for b in range(n_mine)]
+        dump_sketches(args.dump_outputs, plan.views(last[0]), [a.get for a in last])
 
     single_ms, api_ms, cores_per_s_r53 = None, None, None
     if world == 1 and not strong:
@@ -584,15 +639,16 @@ def ref150_batched(nat, l, r, B, reps=10):
                 frac_of_mfma_peak=fl["total"] * B / (med * 1e-3) * 1e-12 / PEAK_F64_MFMA_TF, classes=classes)
 
 
-def bench_ref150(args, job, ranks=(5, 25, 55, 95, 145), reps=7, cpu=True):
+def bench_ref150(args, job, ranks=(5, 25, 55, 95, 145), reps=None, cpu=True):
     nat = job.nat
+    reps = args.steps if reps is None else reps
     import tt_sketch_amd as tsa
     shape = REF150_SHAPE
     tt = device_tt(shape, REF150_TT_RANK, 179)
     rows = []
     for l in ranks:
         for name, fn in ref150_methods(tsa, tt, l).items():
-            best, med = timed_calls(nat, fn, reps=reps)
+            best, med = timed_calls(nat, fn, reps=reps, warm=args.warmup)
             pub = REF150_PUBLISHED_S[name].get(l)
             row = dict(name=name, sketch_rank=l, ms=med, best_ms=best, published_median_s=pub,
                        speedup_vs_published=None if pub is None else pub * 1e3 / med)
@@ -621,7 +677,7 @@ def bench_ref150(args, job, ranks=(5, 25, 55, 95, 145), reps=7, cpu=True):
                        sample=f"oracle (same einsum / lstsq / qr calls as the reference) on the same 100^5 rank-150 TT at "
                               f"l={head_l}: DRM sampling + general_sketch, best of 3 each for streaming (r=2l), orthogonal (r=2l), hmt; "
                               f"{CPU_THREADS} BLAS threads")
-    return dict(metric=metric_name(), value=5 / (head["ms"] * 1e-3), unit="TT-cores/s", n_gpus=args.gpus, steps=reps, warmup=2,
+    return dict(metric=metric_name(), value=5 / (head["ms"] * 1e-3), unit="TT-cores/s", n_gpus=args.gpus, steps=reps, warmup=args.warmup,
                 ms_per_step=head["ms"], higher_is_better=True, scaling="weak", vs_baseline=head["speedup_vs_published"],
                 dtype="f64", data="synthetic",
                 config=dict(workload=f"ref150: the reference's published timing sweep (scripts/plot_timings.py:28-36,94-171): TensorTrain "
@@ -685,8 +741,18 @@ def bench_c5(args, job):
         nat.call("ttsk_sync", -1)
         api_back_to_back_ms = 1e3 * (time.perf_counter() - t0) / 20
         elapsed = job.timed(step_pipelined, args.steps, args.warmup)
+        if getattr(args, "dump_outputs", None):
+            nat.call("ttsk_sync", -1)
+            out = outs[(counter[0] - 1) % inflight]
+            dump_sketches(args.dump_outputs, plan.views(out), [out.get])
     else:
-        elapsed = job.timed(step, args.steps, args.warmup)
+        last = [None]
+
+        def step_kept():
+            last[0] = step()
+        elapsed = job.timed(step_kept if getattr(args, "dump_outputs", None) else step, args.steps, args.warmup)
+        if last[0] is not None and job.rank == 0:
+            dump_sketch_object(args.dump_outputs, last[0])
     check = None
     if args.check:
         # the sketch of the whole sum as rank 0 holds it (the same for every N: what the N = 2 test compares with N = 1)
@@ -737,11 +803,19 @@ def bench_c2(args, job, gaussian=False):
     left = cls(l, shape, False, seed=1)
     right = cls(r, shape, True, seed=2)
 
+    dump = getattr(args, "dump_outputs", None)
+    last = [None]
+
     def step():
-        tsa.general_sketch(T, left, right, tsa.SketchMethod.streaming)
+        sk = tsa.general_sketch(T, left, right, tsa.SketchMethod.streaming)
+        if dump:
+            last[0] = sk
     elapsed = job.timed(step, args.steps, args.warmup)
     if job.rank != 0:
         return None
+    if dump:
+        dump_sketch_object(dump, last[0])
+        last[0] = None
     t_step = elapsed / args.steps
     x_bytes, mats_bytes, unfused, gflop_ref = 8.59e9, 8.18e9, 77.3e9, 484.0
     cpu = None
@@ -839,11 +913,19 @@ def bench_c4(args, job):
     nat.call("ttsk_sync", -1)
     t_first = time.perf_counter() - t0
 
+    dump = getattr(args, "dump_outputs", None)
+    last = [None]
+
     def step():
-        tsa.general_sketch(T, left, right, tsa.SketchMethod.streaming)
+        sk = tsa.general_sketch(T, left, right, tsa.SketchMethod.streaming)
+        if dump:
+            last[0] = sk
     elapsed = job.timed(step, args.steps, args.warmup)
     if job.rank != 0:
         return None
+    if dump:
+        dump_sketch_object(dump, last[0])
+        last[0] = None
     t_step = elapsed / args.steps
     nbytes, samples = 8.0 * nnz * 6, (l + r) * 4 * nnz
     # per kernel class: hipEvent brackets (ttsk_prof_*) around the sampler passes and the segmented sums
@@ -1010,6 +1092,7 @@ def run_extras(args, job):
     extra = {}
     sub = copy.copy(args)
     sub.steps, sub.warmup = 5, 2
+    sub.dump_outputs = None             # the dump is the headline's
     sub.cover = True
     for name, fn in (("c5", bench_c5), ("c4", bench_c4), ("c2", bench_c2), ("c2_gaussian", lambda a, j: bench_c2(a, j, gaussian=True))):
         t0 = time.perf_counter()
@@ -1049,8 +1132,9 @@ def main():
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default: 200 for c3, 7 calls per row for ref150, 20 otherwise)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default: 20 for c3, 2 for ref150, 3 otherwise)")
     ap.add_argument("--config", choices=("c3", "c2", "c2g", "c4", "c5", "ref150"), default="c3")
     ap.add_argument("--scaling", choices=("weak", "strong"), default=None,
                     help="default: weak on one GPU; with --gpus N > 1 the headline is the STRONG job (north_star's quantity) and the "
@@ -1067,9 +1151,16 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="TTs per batched pass (ttsk_tt_sketch_batch; 32 = 8 workgroups x 25 slices per tensor in the fused chain step)")
     ap.add_argument("--inflight", type=int, default=2,
                     help="independent passes in flight (issued on alternating stream pairs); 1 = strictly one after the other")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, <= 64 MB; see dump_sketches)")
     args = ap.parse_args()
-    if args.config != "c3" and args.steps == 200:
-        args.steps, args.warmup = 20, 3
+    steps, warmup = {"c3": (200, 20), "ref150": (7, 2)}.get(args.config, (20, 3))
+    args.steps = steps if args.steps is None else args.steps
+    args.warmup = warmup if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config == "ref150":
+        ap.error("--dump-outputs: ref150 times API calls that sample fresh DRMs every call, so its outputs differ from run to run")
     job = Job(args)
     try:
         both = args.scaling is None and args.config == "c3" and job.world > 1
@@ -1084,7 +1175,7 @@ def main():
             # the same launch also measures the weak job (per-GPU work fixed): a sub-record of the one line
             import copy
             sub = copy.copy(args)
-            sub.scaling, sub.no_cpu, sub.check = "weak", True, False
+            sub.scaling, sub.no_cpu, sub.check, sub.dump_outputs = "weak", True, False, None
             sub.steps, sub.warmup = min(args.steps, 60), min(args.warmup, 10)
             weak = bench_c3(sub, job)
             if result is not None and weak is not None:
