@@ -62,7 +62,7 @@ int ttsk_graph_free(void *graph_exec);
 
 /* ---- generic fp64 contraction (MFMA 16x16x4) -----------------------------
  * C[b,m,n] (+)= alpha * sum_{ko,ki} A[b,m,ko,ki] * B[b,ko,ki,n]
- * with arbitrary element strides.  This is the device counterpart of the
+ * with arbitrary element strides.  batch > 1 needs c_b != 0 (TTSK_ERR_ARG otherwise).  This is the device counterpart of the
  * np.einsum / tensordot / `@` calls in tt_sketch/drm/tensor_train_drm.py:79-141,
  * tt_sketch/drm/dense_gaussian_drm.py:72-75, tt_sketch/tensor.py:390-397 and
  * tt_sketch/sketching_methods/{tensor_train,cp,dense,tucker}_sketch.py.
@@ -174,7 +174,8 @@ int ttsk_dense_left_pass(const double *X, int64_t n0, int64_t n1, int64_t n2, in
 int64_t ttsk_tt_sketch_size(int d, const int64_t *n, const int64_t *l_lo, const int64_t *l_hi,
                             const int64_t *r_lo, const int64_t *r_hi);
 /* per-kernel device timing of the launches made by ttsk_tt_sketch (bench.py roofline leg):
- * while enabled every GEMM launch is bracketed by hipEvents on its stream. */
+ * while enabled every GEMM launch is bracketed by hipEvents on its stream.  on = 1 resets every class's counters
+ * and kernel name. */
 int ttsk_prof_enable(int on);
 /* measured ceiling of v_mfma_f64_16x16x4_f64 on this device (register-resident operands, 4 independent
  * accumulators per wave, two waves per SIMD, every CU busy): TFLOP/s.  MI355X_MICROARCH.md lists no fp64 MFMA
@@ -187,12 +188,13 @@ int ttsk_mfma_f64_peak_probe(double *tflops);
  * ndtri as it comes.  10^9 samples / s.  bench.py prices the sampling passes of the sparse sketch against [0]. */
 int ttsk_ndtri_rate_probe(double *gsamples);
 /* class 0/1: right-chain GEMM1 (T = R^T X^T) / GEMM2 (split-K); 2/3: left-chain GEMM1 / GEMM2;
- * 4: Psi GEMM; 5: small products (Omega, first mode); 7: untagged ttsk_gemm calls.  Only the main
+ * 4: Psi GEMM; 5: small products (Omega, first mode); 6: samplers; 7: sparse Psi / Omega; 8: small
+ * factorisations; 11 (the last class): untagged ttsk_gemm calls.  Only the main
  * contraction kernel of each call is bracketed (not the split-K reduce / zero fill) -- except for the fused
  * chain step, which replaces BOTH products of a step: it is filed under class 1 (right) / 3 (left) with the
  * flops of both and its slab reduce inside the bracket. */
 int ttsk_prof_read(int cls, int64_t *launches, double *total_ms, double *flops);
-/* rocprofv3 name of the contraction-kernel instantiation last launched for class `cls` */
+/* rocprofv3 name of the largest contraction-kernel launch of class `cls` since ttsk_prof_enable(1) (empty: none) */
 int ttsk_prof_kernel_name(int cls, char *buf, size_t len);
 
 /* ---- hash sampler (the reference's native module) -------------------------

@@ -845,6 +845,9 @@ def test_c_abi_argument_errors(tsa):
         nat.call("ttsk_sparse_psi", None, None, None, ctypes.c_size_t(4), None, 1, None, 1, 1, P(out.ptr), 0)
     with pytest.raises((ValueError, RuntimeError)):   # stream index out of range
         nat.call("ttsk_triu", P(A.ptr), 4, 4, 999)
+    d = nat.GemmDesc(batch=2, M=4, N=4, Ko=1, Ki=4, a_m=4, a_ki=1, b_ki=4, b_n=1, c_b=0, c_m=4, c_n=1, alpha=1.0)
+    with pytest.raises(ValueError):          # batch > 1 with every slice writing the same C
+        nat.call("ttsk_gemm", ctypes.byref(d), P(A.ptr), P(A.ptr), P(out.ptr), None, 0)
     # still alive
     nat.call("ttsk_pinv", P(A.ptr), 4, 4, -1.0, P(out.ptr), None, 0)
     assert rel(out.get(), np.eye(4)) < 1e-14

@@ -7,7 +7,7 @@
 // pinv / QR applications).  Arbitrary element strides make Tensor.T, rank_min:rank_max
 // slices and unfoldings zero-copy views.
 //
-// Tiling: one 256-thread workgroup (4 wave64, 2x2) per BM x BN tile of C, BK = 16.
+// Tiling: one 256-thread workgroup (4 wave64, 2x2) per BM x BN tile of C, BK = 32 (gemm_kernel.h).
 // A and B tiles are staged in LDS in one of two layouts chosen by which index is
 // contiguous in global memory, so that both the global read and the LDS write are
 // conflict free and the MFMA fragment reads (ds_read_b64) hit 64 distinct banks:
@@ -217,6 +217,8 @@ int ttsk_gemm(const ttsk_gemm_desc *dp, const double *A, const double *B, double
     TTSK_ARG(dp && A && B && C, "ttsk_gemm: NULL argument");
     ttsk_gemm_desc d = *dp;
     TTSK_ARG(d.batch >= 0 && d.M >= 0 && d.N >= 0 && d.Ko >= 0 && d.Ki >= 0, "ttsk_gemm: negative size");
+    // every slice of a batch would write the same C (and the tiles of different slices would race): no caller means that
+    TTSK_ARG(d.batch <= 1 || d.c_b != 0, "ttsk_gemm: batch %lld with c_b == 0", (long long)d.batch);
     if (d.batch == 0 || d.M == 0 || d.N == 0) return TTSK_OK;
     const int64_t K = d.Ko * d.Ki;
     static int trace = [] { const char *e = getenv("TTSK_GEMM_TRACE"); return e ? atoi(e) : 0; }();

@@ -160,7 +160,7 @@ int ttsk_prof_enable(int on)
     if (!on) prof_flush();
     else {
         prof_flush();
-        for (int i = 0; i < NCLS; ++i) { g_launches[i] = 0; g_ms[i] = 0; g_flops[i] = 0; g_kname_flops[i] = 0; }
+        for (int i = 0; i < NCLS; ++i) { g_launches[i] = 0; g_ms[i] = 0; g_flops[i] = 0; g_kname_flops[i] = 0; g_kname[i][0] = 0; }
     }
     g_prof = on != 0;
     return TTSK_OK;
