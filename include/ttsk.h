@@ -401,6 +401,18 @@ int ttsk_pinv_batch(int count, const double *const *dev_omegas, int64_t l, int64
 int ttsk_tt_assemble(int d, const int64_t *n, const int64_t *lr, const int64_t *rr, const double *const *dev_psi,
                      const double *const *dev_omega, double *const *dev_cores_out, double *const *dev_work, int direction,
                      int stream);
+/* assemble_sketched_tt (sketch.py:400-443) for `count` sketches of one signature at once -- the to_tt() half of the
+ * reference's recompression stream_sketch(tt, l, r).to_tt() (sketch.py:154-229, :279-280).  Per tensor b the contract of
+ * ttsk_tt_assemble on psi + b d, omega + b (d - 1), cores_out + b d, work + b (d - 1); the core that is copied unchanged
+ * (right: d - 1, left: 0) may alias its Psi.  All pairs of one Omega shape share a fixed number of launches on `stream`
+ * (batched normal-equations pseudo-inverses, the Jacobi kernel predicated per matrix, one fused refined product
+ * C = Psi P, R = Psi - C Omega, C += R P) when operands of one mode are equally spaced across the tensors; no host
+ * synchronisation, no stream forked.  TTSK_ERR_ARG before anything is queued for count < 1, a NULL pointer or a
+ * direction other than 0 / 1. */
+int ttsk_tt_assemble_batch(int count, int d, const int64_t *n, const int64_t *lr, const int64_t *rr,
+                           const double *const *dev_psi /* count * d */, const double *const *dev_omega /* count * (d - 1) */,
+                           double *const *dev_cores_out /* count * d */, double *const *dev_work /* count * (d - 1) */,
+                           int direction, int stream);
 /* ---- multi-GPU: one RCCL sum of the packed partial sketch ------------------
  * SketchContainer.__add__ across ranks (sketch_container.py:61-69). */
 int ttsk_comm_unique_id(void *host_id128);                 /* rank 0: 128-byte id */

@@ -1654,6 +1654,45 @@ int ttsk_pinv_batch(int count, const double *const *dev_omegas, int64_t l, int64
     return TTSK_OK;
 }
 
+}  // extern "C"
+
+namespace ttsk {
+
+// ttsk_tt_assemble_batch (assemble_batch.hip): the stages of ttsk_pinv_batch over `count` matrices of one shape that lie
+// equally spaced in the caller's staging buffer, without the 32-matrix limit of the pointer-array products.
+int chol_inv_batch(const double *G, int n, double *Rinv, double *Ginv, int *status, int count, hipStream_t st)
+{
+    if (n > CHOL_ONE || count < 1) return TTSK_ERR_UNSUPPORTED;
+    return launch_chol(G, n, Rinv, Ginv, status, 1.0 / 300.0, st, nullptr, nullptr, count);
+}
+
+bool pinv_batch_fast(int64_t l, int64_t r)
+{
+    return fast_solves() && (l < r ? l : r) <= CHOL_ONE && pinv_rcond(l, r, -1.0) <= 1e-4;
+}
+
+// the Jacobi kernel behind the batched attempt, ONE launch, workgroup b on omega + b * os -> P + b * ps, predicated on
+// status[b]; 1 = queued, 0 = the matrices do not fit the kernel's LDS (nothing queued)
+int jacobi_pinv_spaced(int count, const double *omega, int64_t os, int64_t l, int64_t r, double *P, int64_t ps,
+                       const int *status, hipStream_t st)
+{
+    const int transposed = r >= l;
+    const int64_t mW = transposed ? r : l, nW = transposed ? l : r;
+    size_t jl = 0;
+    const int jm = jacobi_lds_mode(mW, nW, &jl);
+    if (jm < 0) return TTSK_ERR_HIP;
+    if (jm != 2) return 0;
+    hipLaunchKernelGGL(jacobi_pinv_kernel<2>, dim3((unsigned)count), dim3(1024), jl, st, omega, l, r, transposed, (double *)nullptr,
+                       (double *)nullptr, pinv_rcond(l, r, -1.0), P, (int *)nullptr, (double *)nullptr, (double *)nullptr,
+                       (double *)nullptr, status, os, ps);
+    TTSK_LAUNCH_CHECK();
+    return 1;
+}
+
+}  // namespace ttsk
+
+extern "C" {
+
 int ttsk_pinv(const double *dev_omega, int64_t l, int64_t r, double rcond, double *dev_pinv,
               int *host_rank, int stream)
 {

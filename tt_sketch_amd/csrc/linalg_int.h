@@ -30,4 +30,11 @@ size_t qr_batch_ws_elems(int count, int64_t m, int n);
 int qr_cholesky_batch(int count, double *const *A, int64_t m, int n, int stream, hipStream_t st, double *ws, int *sticky);
 int qr_signs_batch(int count, const double *const *Qtop, int n, int square, const double *const *Sprev, int rows_per, double *const *Sout,
                    hipStream_t st);
+// ttsk_tt_assemble_batch: batched Cholesky inverse of `count` n x n matrices lying one after another (n <= 128, the gate of
+// ttsk_pinv_batch), whether the batched fast pseudo-inverse applies to (l x r), and the predicated Jacobi kernel over
+// equally spaced matrices in ONE launch (1 = queued, 0 = outside its LDS, nothing queued)
+int chol_inv_batch(const double *G, int n, double *Rinv, double *Ginv, int *status, int count, hipStream_t st);
+bool pinv_batch_fast(int64_t l, int64_t r);
+int jacobi_pinv_spaced(int count, const double *omega, int64_t os, int64_t l, int64_t r, double *P, int64_t ps,
+                       const int *status, hipStream_t st);
 }  // namespace ttsk

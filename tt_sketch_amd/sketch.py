@@ -425,6 +425,98 @@ def assemble_sketched_tt(sketch: SketchContainer, direction="auto", device: bool
     return [np.asarray(to_host(C)) for C in pending]
 
 
+ASSEMBLE_BATCH_SLICE = 32     # tensors per ttsk_tt_assemble_batch call (outputs of a call share one allocation)
+
+
+def _auto_direction(sketch: SketchContainer) -> str:
+    bigger = np.all(np.array(sketch.left_rank) > np.array(sketch.right_rank))
+    return "left" if bigger else "right"
+
+
+def _assemble_batch_call(group, direction):
+    """One ``ttsk_tt_assemble_batch`` call over sketches of one signature whose operands are device arrays; returns the
+    cores per sketch (device-resident).  Cores of one mode are equally spaced in one allocation."""
+    import ctypes
+    from . import _native as nat
+    from .tt_fused import _carve
+    arrs = [s.device_arrays() for s in group]
+    Psi0, Om0 = arrs[0]
+    d = len(Psi0)
+    if any(s != 0 and s in nat._dirty and nat._joined_into.get(s) != 0 for s in range(nat.NUM_STREAMS)):
+        sync()                                    # operands may still be in flight on another stream
+    lr, rr = [int(o.shape[0]) for o in Om0], [int(o.shape[1]) for o in Om0]
+    n = [int(p.shape[1]) for p in Psi0]
+    if direction == "right":
+        shapes = [(1 if mu == 0 else lr[mu - 1], n[mu], lr[mu]) for mu in range(d - 1)]
+    else:
+        shapes = [(rr[mu - 1], n[mu], 1 if mu == d - 1 else rr[mu]) for mu in range(1, d)]
+    per = shapes + [(rr[k], lr[k]) for k in range(d - 1)]
+    out = _carve(per * len(group))
+    psi_p, om_p, core_p, work_p, cores = [], [], [], [], []
+    for b, (Psi, Om) in enumerate(arrs):
+        Psi = [p.contiguous() for p in Psi]
+        Om = [o.contiguous() for o in Om]
+        mine = out[b * len(per):(b + 1) * len(per)]
+        cs = mine[:d - 1] + [Psi[-1]] if direction == "right" else [Psi[0]] + mine[:d - 1]
+        cores.append(cs)
+        psi_p += [p.ptr for p in Psi]
+        om_p += [o.ptr for o in Om]
+        core_p += [c.ptr for c in cs]
+        work_p += [w.ptr for w in mine[d - 1:]]
+    I64, P = ctypes.c_int64, ctypes.c_void_p
+    nat.call("ttsk_tt_assemble_batch", len(group), d, (I64 * d)(*n), (I64 * (d - 1))(*lr), (I64 * (d - 1))(*rr),
+             (P * len(psi_p))(*psi_p), (P * len(om_p))(*om_p), (P * len(core_p))(*core_p), (P * len(work_p))(*work_p),
+             0 if direction == "right" else 1, 0)
+    return cores
+
+
+def assemble_sketched_tt_batch(sketches: Sequence[SketchContainer], direction="auto", device: bool = False) -> List[ArrayList]:
+    """``[assemble_sketched_tt(s, direction, device) for s in sketches]`` with the sketches of one signature (mode sizes,
+    left and right ranks) assembled together: ``ttsk_tt_assemble_batch`` in slices of ``ASSEMBLE_BATCH_SLICE``, a fixed
+    number of launches per slice.  "auto" picks the direction per signature by the reference's rule (sketch.py:406-410).
+    Sketches whose operands are not device arrays, and signatures met only once, take ``assemble_sketched_tt``.  The
+    result keeps the input order."""
+    sketches = list(sketches)
+    if direction not in ("auto", "right", "left"):
+        raise ValueError(f"Unknown direction {direction}")
+    out: List[Optional[ArrayList]] = [None] * len(sketches)
+    groups: Dict[tuple, List[int]] = {}
+    for i, s in enumerate(sketches):
+        Psi, Om = s._psi, s._omega
+        if len(Psi) >= 2 and all(isinstance(a, DevArray) for a in list(Psi) + list(Om)):
+            groups.setdefault((tuple(s.shape), tuple(s.left_rank), tuple(s.right_rank)), []).append(i)
+    for idx in groups.values():
+        if len(idx) < 2:
+            continue
+        dirn = _auto_direction(sketches[idx[0]]) if direction == "auto" else direction
+        for j in range(0, len(idx), ASSEMBLE_BATCH_SLICE):
+            part = idx[j:j + ASSEMBLE_BATCH_SLICE]
+            if len(part) < 2:
+                continue
+            for i, cores in zip(part, _assemble_batch_call([sketches[i] for i in part], dirn)):
+                out[i] = cores if device else [np.asarray(to_host(C)) for C in cores]
+    for i, s in enumerate(sketches):
+        if out[i] is None:
+            out[i] = assemble_sketched_tt(s, direction=direction, device=device)
+    return out
+
+
+def to_tt_batch(sketched: Sequence[SketchedTensorTrain]) -> List[TensorTrain]:
+    """``[s.to_tt() for s in sketched]`` in batched device passes (``assemble_sketched_tt_batch``): the counterpart of
+    ``stream_sketch_batch`` for the assembly.  Device-resident cores, as ``to_tt``; anything that cannot go through the
+    batched call (host-array sketches, a signature met once) takes ``s.to_tt()``."""
+    sketched = list(sketched)
+    if not sketched:
+        return []
+    batchable = [all(isinstance(a, DevArray) for a in s.sketch_._psi + s.sketch_._omega) for s in sketched]
+    cores = [None] * len(sketched)
+    idx = [i for i, ok in enumerate(batchable) if ok]
+    if idx:
+        for i, cs in zip(idx, assemble_sketched_tt_batch([sketched[i].sketch_ for i in idx], device=True)):
+            cores[i] = cs
+    return [TensorTrain(cores[i]) if cores[i] is not None else s.to_tt() for i, s in enumerate(sketched)]
+
+
 def _assemble_blocked_stream_sketches(left_rank_slices, right_rank_slices, shape,
                                       sketch_dict: BlockedSketch) -> SketchContainer:
     """Place every block at its rank offsets (reference :446-473)."""
