@@ -321,3 +321,19 @@ def test_sparse_one_pass_path_declines_a_mode_beyond_its_sort_key():
     left = SparseGaussianDRM((2, 2), shape, transpose=False, seed=1)
     right = SparseGaussianDRM((3, 3), shape, transpose=True, seed=2)
     assert sparse_fused.try_sparse_gauss_sketch(X, left, right, SketchMethod.streaming) is None
+
+
+def test_every_launch_goes_through_the_one_checked_helper():
+    """csrc/common.h launch() is the library's only kernel launch and runtime.hip's registry its only dynamic-LDS set-up:
+    a kernel added with a local idiom (its own hipFuncSetAttribute, a per-function once-flag) fails here."""
+    import glob
+    import re
+    csrc = os.path.join(os.path.dirname(nat.__file__), "csrc")
+    src = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))}
+    assert len(src) > 40
+    where = lambda pat: sorted(f for f, s in src.items() if re.search(pat, s))
+    assert where(r"\bhipLaunchKernelGGL\b") == ["common.h"]
+    assert where(r"\bhipFuncSetAttribute\b") == ["runtime.hip"]
+    assert where(r"\bPerInit\b") == []
+    assert where(r"static\s+bool\s+attr_done") == []
+    assert where(r"\bTTSK_LAUNCH_CHECK\b") == []

@@ -334,12 +334,6 @@ int assemble_shape(const std::vector<AbPair> &pairs, int64_t l, int64_t r, int d
         }
         return apply_fallback(pairs, l, r, direction, stream, st);
     }
-    static PerInit attr;
-    if (attr.first()) {
-        TTSK_HIP(hipFuncSetAttribute((const void *)assemble_apply_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        TTSK_HIP(hipFuncSetAttribute((const void *)assemble_apply_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        TTSK_HIP(hipFuncSetAttribute((const void *)assemble_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
     const int T = (int)pairs.size(), n = (int)std::min(l, r), K = (int)std::max(l, r);
     const size_t lr = (size_t)l * r, nn = (size_t)n * n;
     auto blk = [](size_t v) { return (v + 31) & ~(size_t)31; };
@@ -358,13 +352,11 @@ int assemble_shape(const std::vector<AbPair> &pairs, int64_t l, int64_t r, int d
         // (the pair index of a group's first tensor is its `first`: the groups of a launch follow one another)
         const int base = t.g[0].first;
         for (int i = 0; i < t.ng; ++i) t.g[i].first -= base;
-        hipLaunchKernelGGL(assemble_gram_kernel, dim3((unsigned)wgs), dim3(AB_THREADS), (size_t)K * n * 8, st, t, (int)l, (int)r,
-                           Os + (size_t)base * lr, Gm + (size_t)base * nn);
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(assemble_gram_kernel, dim3((unsigned)wgs), dim3(AB_THREADS), (size_t)K * n * 8, st, t, (int)l, (int)r,
+                         Os + (size_t)base * lr, Gm + (size_t)base * nn))) return rc;
     }
     if ((rc = chol_inv_batch(Gm, n, Rinv, Ginv, status, T, st))) return rc;
-    hipLaunchKernelGGL(assemble_solve_kernel, dim3((unsigned)T), dim3(AB_THREADS), ((size_t)K * n + nn) * 8, st, (int)l, (int)r, Os, Ginv, Ps);
-    TTSK_LAUNCH_CHECK();
+    if ((rc = launch(assemble_solve_kernel, dim3((unsigned)T), dim3(AB_THREADS), ((size_t)K * n + nn) * 8, st, (int)l, (int)r, Os, Ginv, Ps))) return rc;
     rc = jacobi_pinv_spaced(T, Os, (int64_t)lr, l, r, Ps, (int64_t)lr, status, st);
     if (rc < 0) return rc;
     if (rc == 0) { set_error("ttsk_tt_assemble_batch: Jacobi kernel outside its LDS cover (%lld x %lld)", (long long)l, (long long)r); return TTSK_ERR_UNSUPPORTED; }
@@ -389,11 +381,8 @@ int assemble_shape(const std::vector<AbPair> &pairs, int64_t l, int64_t r, int d
             wgs += g.count * g.chunks;
             t.g[i] = g;
         }
-        if (direction == 0)
-            hipLaunchKernelGGL(assemble_apply_kernel<false>, dim3((unsigned)wgs), dim3(AB_THREADS), lds, st, t, a, b);
-        else
-            hipLaunchKernelGGL(assemble_apply_kernel<true>, dim3((unsigned)wgs), dim3(AB_THREADS), lds, st, t, a, b);
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(direction == 0 ? assemble_apply_kernel<false> : assemble_apply_kernel<true>, dim3((unsigned)wgs), dim3(AB_THREADS),
+                         lds, st, t, a, b))) return rc;
     }
     return TTSK_OK;
 }

@@ -1,22 +1,8 @@
-// Launch helpers shared by the chain_wide_i*.hip instantiation units (one unit per chunk structure).
+// Dispatch shared by the chain_wide_i*.hip instantiation units (one unit per chunk structure).
 #pragma once
 #include "chain_wide.h"
 
 namespace ttsk {
-
-template <int NQF, int STRQ, int NNF, int STRN, bool WT, int UNR, bool MT2>
-static int launch_cw_one(const ChainWide &a, size_t lds, int grid, hipStream_t st)
-{
-    auto kern = chain_wide_kernel<NQF, STRQ, NNF, STRN, WT, UNR, MT2>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        TTSK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, a);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
-}
 
 // waves with two row tiles exist only where the registers allow (chain_wide.hip asks cw_has_mt2 first)
 constexpr bool cw_has_mt2(int nqf, int nnf, int strn) { return nqf <= 3 && nnf + (strn ? 1 : 0) <= 7; }
@@ -25,11 +11,9 @@ template <int NQF, int STRQ, int NNF, int STRN>
 static int launch_cw_pick(const ChainWide &a, bool wt, int unr, size_t lds, int grid, hipStream_t st)
 {
     constexpr bool MT2 = cw_has_mt2(NQF, NNF, STRN);
-    if (unr == 25)
-        return wt ? launch_cw_one<NQF, STRQ, NNF, STRN, true, 25, MT2>(a, lds, grid, st)
-                  : launch_cw_one<NQF, STRQ, NNF, STRN, false, 25, MT2>(a, lds, grid, st);
-    return wt ? launch_cw_one<NQF, STRQ, NNF, STRN, true, 5, MT2>(a, lds, grid, st)
-              : launch_cw_one<NQF, STRQ, NNF, STRN, false, 5, MT2>(a, lds, grid, st);
+    auto kern = unr == 25 ? (wt ? chain_wide_kernel<NQF, STRQ, NNF, STRN, true, 25, MT2> : chain_wide_kernel<NQF, STRQ, NNF, STRN, false, 25, MT2>)
+                          : (wt ? chain_wide_kernel<NQF, STRQ, NNF, STRN, true, 5, MT2> : chain_wide_kernel<NQF, STRQ, NNF, STRN, false, 5, MT2>);
+    return launch(kern, grid, 512, lds, st, a);
 }
 
 #define TTSK_CW_OUT(NNF, STRN) \

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <utility>
 #include "ttsk.h"
 
 namespace ttsk {
@@ -18,12 +19,8 @@ void *scratch(int stream, int slot, size_t bytes);
 // another device gets fresh ones.  nullptr on failure.
 enum { PA_PINV_HOST = 0, PA_PINV_DEV, PA_DEFERRED, PA_PINV_BATCH_VD, PA_DEFERRED_PINNED, PA_SLOTS };
 void *persistent_alloc(int key, size_t bytes, bool host, bool zero);
-// per-function one-time set-up (hipFuncSetAttribute) that has to be repeated after ttsk_shutdown + re-init
+// bumped by ttsk_shutdown: per-function set-up on the device (symbols) is repeated after a re-init, maybe on another device
 int init_generation();
-struct PerInit {
-    int gen = -1;
-    bool first() { const int g = init_generation(); if (gen == g) return false; gen = g; return true; }
-};
 
 #define TTSK_HIP(call)                                                          \
     do {                                                                        \
@@ -47,8 +44,30 @@ struct PerInit {
     hipStream_t var = ttsk::stream_of(s);                                       \
     if (!var) return TTSK_ERR_ARG
 
-#define TTSK_LAUNCH_CHECK()                                                     \
-    TTSK_HIP(hipGetLastError())
+// Where a kernel is launched from: converted from the stream argument of launch(), so that its errors name the call site.
+struct LaunchAt {
+    hipStream_t st;
+    const char *file;
+    int line;
+    LaunchAt(hipStream_t s, const char *f = __builtin_FILE(), int l = __builtin_LINE()) : st(s), file(f), line(l) {}
+};
+
+// runtime.hip: raises kern's dynamic-LDS limit to the device's LDS per workgroup minus its static LDS, once per init
+// generation; lock-free once raised.
+int raise_lds_limit(const void *kern, const char *file, int line);
+
+// Every kernel launch of the library goes through here: the dynamic-LDS limit (lds > 0), the launch, its check.
+// TTSK_OK, or TTSK_ERR_HIP with an error naming the call site.
+template <typename... P, typename... A>
+int launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, LaunchAt at, A &&...args)
+{
+    if (lds > 0 && raise_lds_limit((const void *)kern, at.file, at.line) != TTSK_OK) return TTSK_ERR_HIP;
+    hipLaunchKernelGGL(kern, grid, block, lds, at.st, std::forward<A>(args)...);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return TTSK_OK;
+    set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), at.file, at.line);
+    return TTSK_ERR_HIP;
+}
 
 // Fragment reads of tiles p, p + 1 (256 bytes apart) must NOT be paired into ds_read2_b64: its 16-lane groups bank modulo
 // 32 dwords, and this layout's interleaved k-pairs (lane stride 16 bytes) then collide two by two -- 16 LDS cycles per pair of

@@ -284,27 +284,17 @@ extern "C" int ttsk_dense_left_pass(const double *X, int64_t n0, int64_t n1, int
     a.slab2 = ws;
     a.slab3 = ws + slab;
     const size_t lds = ((size_t)4 * 4 * LP_XP + (size_t)4 * (((3 + a.ni3) * 80 + 127) / 128 * 128 + 128)) * 8;
-    static PerInit attr;
-    if (attr.first()) {
-        if (hipFuncSetAttribute((const void *)dense_left_pass_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void *)dense_left_pass_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("ttsk_dense_left_pass: cannot raise the dynamic LDS limit");
-            return TTSK_ERR_HIP;
-        }
-    }
     const unsigned grid = (unsigned)(n2 * a.nct);
     const bool prof = prof_on();
     if (prof) prof_open_named(st, -2, 8.0 * l * (double)n0 * n1 * n2 * C, "dense_left_pass_kernel");
-    if (l > 16) hipLaunchKernelGGL(dense_left_pass_kernel<true>, dim3(grid), dim3(512), lds, st, a);
-    else hipLaunchKernelGGL(dense_left_pass_kernel<false>, dim3(grid), dim3(512), lds, st, a);
-    TTSK_LAUNCH_CHECK();
+    int rc = launch(l > 16 ? dense_left_pass_kernel<true> : dense_left_pass_kernel<false>, dim3(grid), dim3(512), lds, st, a);
+    if (rc != TTSK_OK) return rc;
     // Z_2 = sum_{i2} slab2[i2], E_3 likewise: the slabs are [chunk = i2][M = l][N = C]
     ReduceOut r2{}, r3{};
     r2.C[0] = Z2;
     r3.C[0] = E3;
-    int rc = launch_r_reduce(st, a.slab2, (int)n2, l, (int)C, 1, (int64_t)l, r2, 1, C, 1, 1.0, 0);
+    rc = launch_r_reduce(st, a.slab2, (int)n2, l, (int)C, 1, (int64_t)l, r2, 1, C, 1, 1.0, 0);
     if (rc == TTSK_OK) rc = launch_r_reduce(st, a.slab3, (int)n2, l, (int)C, 1, (int64_t)l, r3, 1, C, 1, 1.0, 0);
     if (prof) prof_close(st);
-    if (rc != TTSK_OK) { set_error("ttsk_dense_left_pass: reduce launch failed"); return TTSK_ERR_HIP; }
-    return TTSK_OK;
+    return rc;
 }

@@ -371,12 +371,7 @@ int dense_pass_launch(const DensePass &a, int64_t grid, hipStream_t st)
 {
     constexpr int NB = 8 * NBW;
     const size_t lds = (size_t)(2 * NB * 128 + 2 * 8 * dp_prow(TP, SP) + NB * (16 * ZT + 4 * ZS)) * 8;
-    static PerInit attr;
-    if (attr.first() && hipFuncSetAttribute((const void *)dense_pass_kernel<NBW, TP, SP, ZT, ZS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            156 * 1024) != hipSuccess)
-        return TTSK_ERR_HIP;
-    hipLaunchKernelGGL((dense_pass_kernel<NBW, TP, SP, ZT, ZS>), dim3((unsigned)grid), dim3(512), lds, st, a);
-    return hipGetLastError() == hipSuccess ? TTSK_OK : TTSK_ERR_HIP;
+    return launch(dense_pass_kernel<NBW, TP, SP, ZT, ZS>, dim3((unsigned)grid), dim3(512), lds, st, a);
 }
 
 }  // namespace
@@ -434,8 +429,7 @@ extern "C" int ttsk_dense_first_pass(const double *X, int64_t n0, int64_t Q, int
     double *slab = (double *)ws;
     if (r & 1) {
         double *pp = (double *)(ws + (size_t)grid * NB * sl64 * 8);
-        hipLaunchKernelGGL(dense_pass_pad_p, dim3((unsigned)cdiv(Q * pr, 256)), dim3(256), 0, st, P, Q, (int)r, pp);
-        TTSK_LAUNCH_CHECK();
+        if (int rc = launch(dense_pass_pad_p, dim3((unsigned)cdiv(Q * pr, 256)), dim3(256), 0, st, P, Q, (int)r, pp)) return rc;
         P = pp;
     }
     // blocks of b: each block's Z is a partial sum over its values of b
@@ -466,14 +460,12 @@ extern "C" int ttsk_dense_first_pass(const double *X, int64_t n0, int64_t Q, int
     for (int k = 0; k < kinds; ++k) {
         const int p_off = k * p_half, pcount = split ? (k == 0 ? std::min<int>(p_half, (int)r) : (int)r - p_half) : (int)r;
         if (pcount <= 0) continue;
-        hipLaunchKernelGGL(dense_pass_reduce, dim3((unsigned)cdiv(elems, 256)), dim3(256), 0, st, slab + (size_t)k * grid1 * NB * sl64, NB, TP, SP, nt,
-                           (int)nqc, nbb, (int)T, (int)r, U, p_off, pcount);
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(dense_pass_reduce, dim3((unsigned)cdiv(elems, 256)), dim3(256), 0, st, slab + (size_t)k * grid1 * NB * sl64, NB, TP, SP, nt,
+                         (int)nqc, nbb, (int)T, (int)r, U, p_off, pcount))) return rc;
     }
     if (nbb > 1) {
         const int64_t pairs = zblock / 2;               // Q T is a multiple of 128
-        hipLaunchKernelGGL(dense_pass_zsum, dim3((unsigned)cdiv(pairs, 256)), dim3(256), 0, st, (const double2 *)zout, nbb, pairs, (double2 *)Z);
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(dense_pass_zsum, dim3((unsigned)cdiv(pairs, 256)), dim3(256), 0, st, (const double2 *)zout, nbb, pairs, (double2 *)Z))) return rc;
     }
     if (prof_on()) prof_close(st);
     return TTSK_OK;

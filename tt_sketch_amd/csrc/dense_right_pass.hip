@@ -165,21 +165,14 @@ int rows_longk_try(const double *S, int64_t rows, int64_t s_row, const double *B
     if (!a.slab) return TTSK_ERR_HIP;
     const bool prof = prof_on();
     if (prof) prof_open_named(st, -2, 2.0 * rows * (double)N * K, "rows_longk_kernel");
-    static PerInit attr;
-    if (attr.first() && hipFuncSetAttribute((const void *)rows_longk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-        set_error("rows_longk: cannot raise the dynamic LDS limit");
-        return TTSK_ERR_HIP;
-    }
-    hipLaunchKernelGGL(rows_longk_kernel, dim3((unsigned)(nrb * nkc)), dim3(512), (size_t)2 * (64 + RP_BROWS) * 64 * 8, st, a);
-    int rc = hipGetLastError() == hipSuccess ? TTSK_OK : TTSK_ERR_HIP;
+    int rc = launch(rows_longk_kernel, dim3((unsigned)(nrb * nkc)), dim3(512), (size_t)2 * (64 + RP_BROWS) * 64 * 8, st, a);
     if (rc == TTSK_OK) {
         ReduceOut ro{};
         ro.C[0] = C;
         rc = launch_r_reduce(st, a.slab, (int)nkc, 64, N, (int)nrb, rows, ro, 1, c_row, 1, alpha, accumulate);
     }
     if (prof) prof_close(st);
-    if (rc != TTSK_OK) { set_error("rows_longk: launch failed"); return TTSK_ERR_HIP; }
-    return 1;
+    return rc == TTSK_OK ? 1 : rc;
 }
 
 }  // namespace ttsk

@@ -196,10 +196,8 @@ int launch_splitk_reduce(const ttsk_gemm_desc &d, const double *partial, double 
     const int64_t total = d.batch * tiles_m * tiles_n * 256;
     int64_t blocks = cdiv(total, 64);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d, partial, C, splits,
-                       tiles_m, tiles_n, rota);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d, partial, C, splits,
+                  tiles_m, tiles_n, rota);
 }
 
 static bool even(int64_t v) { return (v & 1) == 0; }
@@ -229,9 +227,8 @@ int ttsk_gemm(const ttsk_gemm_desc *dp, const double *A, const double *B, double
                 (long long)d.b_ki, (long long)d.b_n, (long long)d.c_b, (long long)d.c_m, (long long)d.c_n, d.accumulate);
     if (K == 0) {
         if (!d.accumulate) {
-            hipLaunchKernelGGL(fill3_kernel, dim3(256), dim3(256), 0, st, C, d.batch, d.M, d.N, d.c_b,
-                               d.c_m, d.c_n, 0.0);
-            TTSK_LAUNCH_CHECK();
+            if (int rc = launch(fill3_kernel, dim3(256), dim3(256), 0, st, C, d.batch, d.M, d.N, d.c_b,
+                                d.c_m, d.c_n, 0.0)) return rc;
         }
         return TTSK_OK;
     }
@@ -363,7 +360,7 @@ int ttsk_mfma_f64_peak_probe(double *tflops)
     double best = 0;
     for (int rep = 0; rep < 4; ++rep) {
         TTSK_HIP(hipEventRecord(a, st));
-        hipLaunchKernelGGL(mfma_probe_kernel, dim3(blocks), dim3(512), 0, st, sink, iters, 1.0 + rep);
+        if (int rc = launch(mfma_probe_kernel, dim3(blocks), dim3(512), 0, st, sink, iters, 1.0 + rep)) return rc;
         TTSK_HIP(hipEventRecord(b, st));
         TTSK_HIP(hipEventSynchronize(b));
         float ms = 0;
@@ -402,9 +399,7 @@ int ttsk_copy_strided(double *dst, const double *src, int ndim, const int64_t *s
     if (c.total == 0) return TTSK_OK;
     int64_t blocks = cdiv(c.total, 256);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(copy_strided_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dst, src, c);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(copy_strided_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dst, src, c);
 }
 
 int ttsk_sum_slices(double *dst, const double *src, int nb, size_t stride, size_t n, int accumulate, int stream)
@@ -415,16 +410,12 @@ int ttsk_sum_slices(double *dst, const double *src, int nb, size_t stride, size_
     if ((n & 1) || (stride & 1) || (((uintptr_t)dst | (uintptr_t)src) & 15)) {
         size_t blocks = (n + 255) / 256;
         if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(sum_slices_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dst, src, nb, stride, n, accumulate);
-        TTSK_LAUNCH_CHECK();
-        return TTSK_OK;
+        return launch(sum_slices_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dst, src, nb, stride, n, accumulate);
     }
     size_t blocks = (n / 2 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (double2 *)dst, (const double2 *)src,
-                       nb, stride / 2, n / 2, accumulate);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(sum_slices_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (double2 *)dst, (const double2 *)src,
+                  nb, stride / 2, n / 2, accumulate);
 }
 
 int ttsk_axpby(double *y, const double *x, double a, double b, size_t n, int stream)
@@ -433,9 +424,7 @@ int ttsk_axpby(double *y, const double *x, double a, double b, size_t n, int str
     if (n == 0) return TTSK_OK;
     size_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)blocks), dim3(256), 0, st, y, x, a, b, n);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(axpby_kernel, dim3((unsigned)blocks), dim3(256), 0, st, y, x, a, b, n);
 }
 
 }  // extern "C"

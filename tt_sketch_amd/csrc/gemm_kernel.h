@@ -413,10 +413,8 @@ static int launch_one(const GemmLaunch &g, hipStream_t st)
     constexpr int bm = WM * TMX * 16, bn = WN * TNX * 16;
     dim3 grid((unsigned)cdiv(g.d.N, bn), (unsigned)cdiv(g.d.M, bm), (unsigned)(g.d.batch * g.splits));
     const size_t lds = 8 * (size_t)((AKF ? bm * LDKF : BK * ldmf(bm)) + (BKF ? bn * LDKF : BK * ldmf(bn)));
-    hipLaunchKernelGGL((gemm_f64_kernel<WM, WN, TMX, TNX, AKF, BKF>), grid, dim3(256), lds, st, g.d, g.A, g.B, g.C,
-                       g.ks, g.splits, g.kchunk, g.partial, g.avec, g.bvec, g.fast_ok, g.a_extent, g.b_extent);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(gemm_f64_kernel<WM, WN, TMX, TNX, AKF, BKF>, grid, dim3(256), lds, st, g.d, g.A, g.B, g.C,
+                  g.ks, g.splits, g.kchunk, g.partial, g.avec, g.bvec, g.fast_ok, g.a_extent, g.b_extent);
 }
 
 template <bool AKF, bool BKF>

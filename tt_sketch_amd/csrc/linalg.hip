@@ -872,15 +872,8 @@ static unsigned chol_threads(int n)
 static int launch_chol(const double *G, int n, double *Rinv, double *Ginv, int *status, double cond_tol, hipStream_t st,
                        int *sticky = nullptr, double *pminmax = nullptr, int count = 1)
 {
-    static PerInit attr;
-    if (attr.first()) {
-        TTSK_HIP(hipFuncSetAttribute((const void *)chol_inv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-        TTSK_HIP(hipFuncSetAttribute((const void *)hh_sign_scale_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-    }
-    hipLaunchKernelGGL(chol_inv_kernel, dim3((unsigned)count), dim3(chol_threads(n)), (size_t)(n * (n + 1) + n) * 8, st, G, n, Rinv, Ginv, status,
-                       cond_tol, sticky, pminmax);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(chol_inv_kernel, dim3((unsigned)count), dim3(chol_threads(n)), (size_t)(n * (n + 1) + n) * 8, st, G, n, Rinv, Ginv, status,
+                  cond_tol, sticky, pminmax, (const double *)nullptr, 0, 1);
 }
 
 __global__ void add_diag_kernel(double *E, int n, double v)
@@ -931,8 +924,7 @@ static int chol_inv_any(const double *G, int n, double *Rinv, double *Ginv, int 
     TTSK_HIP(hipMemcpy2DAsync(S, (size_t)n2 * 8, G + (size_t)n1 * n + n1, (size_t)n * 8, (size_t)n2 * 8, n2, hipMemcpyDeviceToDevice, st));
     if ((rc = gemm_ex(n2, n2, n1, R12, 1, n2, R12, n2, 1, S, n2, -1.0, 1, stream))) return rc;               // S = G22 - R12^T R12
     if ((rc = launch_chol(S, n2, X22, nullptr, st2 + 1, 0.0, st, nullptr, pm + 2))) return rc;
-    hipLaunchKernelGGL(chol_combine_kernel, dim3(1), dim3(1), 0, st, pm, st2, cond_tol, status, sticky);
-    TTSK_LAUNCH_CHECK();
+    if ((rc = launch(chol_combine_kernel, dim3(1), dim3(1), 0, st, pm, st2, cond_tol, status, sticky))) return rc;
     if ((rc = gemm_ex(n1, n2, n2, R12, n2, 1, X22, n2, 1, Y, n2, 1.0, 0, stream))) return rc;                 // Y = R12 X22
     TTSK_HIP(hipMemsetAsync(Rinv, 0, (size_t)n * n * 8, st));
     TTSK_HIP(hipMemcpy2DAsync(Rinv, (size_t)n * 8, X11, (size_t)n1 * 8, (size_t)n1 * 8, n1, hipMemcpyDeviceToDevice, st));
@@ -1015,13 +1007,11 @@ static int pinv_cholesky_begin(const double *omega, int64_t l, int64_t r, double
     double *E = G;                      // n x n, free again
     if (l <= r) {
         if ((rc = gemm_ex(l, l, r, omega, r, 1, pinv, l, 1, E, l, -1.0, 0, stream))) return rc;          // E = -Omega X0
-        hipLaunchKernelGGL(add_diag_kernel, dim3(1), dim3(256), 0, st, E, (int)l, 2.0);                  // E = 2 I - Omega X0
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(add_diag_kernel, dim3(1), dim3(256), 0, st, E, (int)l, 2.0))) return rc;      // E = 2 I - Omega X0
         if ((rc = gemm_ex(r, l, l, pinv, l, 1, E, l, 1, x1, l, 1.0, 0, stream))) return rc;               // X1 = X0 E
     } else {
         if ((rc = gemm_ex(r, r, l, pinv, l, 1, omega, r, 1, E, r, -1.0, 0, stream))) return rc;          // E = -X0 Omega
-        hipLaunchKernelGGL(add_diag_kernel, dim3(1), dim3(256), 0, st, E, (int)r, 2.0);
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(add_diag_kernel, dim3(1), dim3(256), 0, st, E, (int)r, 2.0))) return rc;
         if ((rc = gemm_ex(r, l, r, E, r, 1, pinv, l, 1, x1, l, 1.0, 0, stream))) return rc;               // X1 = E X0
     }
     TTSK_HIP(hipMemcpyAsync(pinv, x1, (size_t)r * l * 8, hipMemcpyDeviceToDevice, st));
@@ -1057,12 +1047,7 @@ int qr_cholesky(double *A, int64_t m, int64_t n64, int stream, hipStream_t st, d
     if (n > CHOL_MAX || m < n) return 0;
     if (m < 2 * n64 && (size_t)m * n + n <= SMALL_QR_MAX) {
         // nearly square and small: Householder in one workgroup, no gate to fail
-        static PerInit attr;
-        if (attr.first()) {
-            TTSK_HIP(hipFuncSetAttribute((const void *)small_qr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        }
-        hipLaunchKernelGGL(small_qr_kernel, dim3(1), dim3(1024), ((size_t)m * n + n) * 8, st, A, (int)m, n);
-        TTSK_LAUNCH_CHECK();
+        if (int rc = launch(small_qr_kernel, dim3(1), dim3(1024), ((size_t)m * n + n) * 8, st, A, (int)m, n)) return rc;
         return unsigned_q ? 2 : 1;        // 2: Q carries LAPACK's signs already
     }
     double *ws = ws_in ? ws_in : (double *)scratch(stream, SCRATCH_MISC, qr_ws_elems(m, n) * 8);
@@ -1086,30 +1071,22 @@ int qr_cholesky(double *A, int64_t m, int64_t n64, int stream, hipStream_t st, d
     } else if (unsigned_q) {
         // R with positive diagonal only: the caller reconstructs the signs beside the critical path (qr_signs)
         static const int chol_expand = [] { const char *e = getenv("TTSK_CHOL_EXPAND"); return e ? atoi(e) : 1; }();
-        hipLaunchKernelGGL(chol_inv_kernel, dim3(1), dim3(256), (size_t)(n * (n + 1) + n) * 8, st, G, n, R2, (double *)nullptr,
-                           status + 1, 0.5, sticky, (double *)nullptr, (const double *)nullptr, 0, chol_expand ? 2 : 0);
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(chol_inv_kernel, dim3(1), dim3(256), (size_t)(n * (n + 1) + n) * 8, st, G, n, R2, (double *)nullptr,
+                         status + 1, 0.5, sticky, (double *)nullptr, (const double *)nullptr, 0, chol_expand ? 2 : 0))) return rc;
     } else if (n <= CHOL_SIGN_MAX) {
         // second factorisation (G ~ identity), top block of Q and the sign reconstruction in ONE kernel
         static const int chol_expand = [] { const char *e = getenv("TTSK_CHOL_EXPAND"); return e ? atoi(e) : 1; }();
-        static PerInit attr;
-        if (attr.first()) {
-            TTSK_HIP(hipFuncSetAttribute((const void *)chol_inv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-        }
-        hipLaunchKernelGGL(chol_inv_kernel, dim3(1), dim3(256), (size_t)(3 * n * (n + 1) + 2 * n) * 8, st, G, n, R2, (double *)nullptr,
-                           status + 1, 0.5, sticky, (double *)nullptr, (const double *)Q1, m == n64 ? 1 : 0, chol_expand);
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(chol_inv_kernel, dim3(1), dim3(256), (size_t)(3 * n * (n + 1) + 2 * n) * 8, st, G, n, R2, (double *)nullptr,
+                         status + 1, 0.5, sticky, (double *)nullptr, (const double *)Q1, m == n64 ? 1 : 0, chol_expand))) return rc;
     } else {
     if ((rc = chol_inv_any(G, n, R2, nullptr, status + 1, 0.5, stream, st, cws, sticky))) return rc;    // must be ~identity
     if ((rc = small_gemm(n, n, n, Q1, n, 1, R2, n, 1, Qtop, stream))) return rc;         // top block of Q
-    if (n <= CHOL_ONE) {
-        hipLaunchKernelGGL(hh_sign_scale_kernel, dim3(1), dim3(256), (size_t)(n * (n + 1) + n) * 8, st, Qtop, n,
-                           m == n64 ? 1 : 0, R2);
-    } else {
-        // beyond one workgroup's LDS: the same modified LU with the working copy in global memory (Qtop itself)
-        hipLaunchKernelGGL(hh_sign_scale_global_kernel, dim3(1), dim3(1024), 0, st, Qtop, n, m == n64 ? 1 : 0, R2);
-    }
-    TTSK_LAUNCH_CHECK();
+    if (n <= CHOL_ONE)
+        rc = launch(hh_sign_scale_kernel, dim3(1), dim3(256), (size_t)(n * (n + 1) + n) * 8, st, Qtop, n,
+                    m == n64 ? 1 : 0, R2);
+    else        // beyond one workgroup's LDS: the same modified LU with the working copy in global memory (Qtop itself)
+        rc = launch(hh_sign_scale_global_kernel, dim3(1), dim3(1024), 0, st, Qtop, n, m == n64 ? 1 : 0, R2);
+    if (rc) return rc;
     }
     if (!sticky) {
         int host_status[2] = {1, 1};
@@ -1284,13 +1261,8 @@ static int launch_cholqr2_lds(double *M, int64_t m, int n, int *status, double c
     const size_t np = 16 * (size_t)((n + 15) >> 4), mp = 16 * (size_t)((m + 15) >> 4);
     const size_t elems = mp * (np + 2) + np * (np + 1) + np;
     if (elems > CHOLQR2_LDS_MAX) return 0;
-    static PerInit attr;
-    if (attr.first()) {
-        TTSK_HIP(hipFuncSetAttribute((const void *)cholqr2_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-    }
     const size_t lds = elems * 8;
-    hipLaunchKernelGGL(cholqr2_lds_kernel, dim3(1), dim3(1024), lds, st, M, (int)m, n, status, cond_tol, sticky);
-    TTSK_LAUNCH_CHECK();
+    if (int rc = launch(cholqr2_lds_kernel, dim3(1), dim3(1024), lds, st, M, (int)m, n, status, cond_tol, sticky)) return rc;
     return 1;
 }
 
@@ -1344,16 +1316,10 @@ int qr_signs(const double *Qtop, int n, int square, const double *Sprev, int row
 {
     if (n > CHOL_ONE) {
         if (n > CHOL_MAX || !work) return 0;
-        hipLaunchKernelGGL(qr_signs_global_kernel, dim3(1), dim3(1024), 0, st, Qtop, n, square, Sprev, rows_per, work, Sout);
-        TTSK_LAUNCH_CHECK();
+        if (int rc = launch(qr_signs_global_kernel, dim3(1), dim3(1024), 0, st, Qtop, n, square, Sprev, rows_per, work, Sout)) return rc;
         return 1;
     }
-    static PerInit attr;
-    if (attr.first()) {
-        TTSK_HIP(hipFuncSetAttribute((const void *)qr_signs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-    }
-    hipLaunchKernelGGL(qr_signs_kernel, dim3(1), dim3(chol_threads(n)), (size_t)(n * (n + 1) + n) * 8, st, Qtop, n, square, Sprev, rows_per, Sout);
-    TTSK_LAUNCH_CHECK();
+    if (int rc = launch(qr_signs_kernel, dim3(1), dim3(chol_threads(n)), (size_t)(n * (n + 1) + n) * 8, st, Qtop, n, square, Sprev, rows_per, Sout)) return rc;
     return 1;
 }
 
@@ -1385,14 +1351,9 @@ int qr_signs_batch(int count, const double *const *Qtop, int n, int square, cons
                    hipStream_t st)
 {
     if (n > CHOL_ONE || count < 1 || count > 16) return 0;
-    static PerInit attr;
-    if (attr.first()) {
-        TTSK_HIP(hipFuncSetAttribute((const void *)qr_signs_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-    }
     QrSignsBatch a{};
     for (int b = 0; b < count; ++b) { a.Q[b] = Qtop[b]; a.Sprev[b] = Sprev ? Sprev[b] : nullptr; a.Sout[b] = Sout[b]; }
-    hipLaunchKernelGGL(qr_signs_batch_kernel, dim3((unsigned)count), dim3(chol_threads(n)), (size_t)(n * (n + 1) + n) * 8, st, a, n, square, rows_per);
-    TTSK_LAUNCH_CHECK();
+    if (int rc = launch(qr_signs_batch_kernel, dim3((unsigned)count), dim3(chol_threads(n)), (size_t)(n * (n + 1) + n) * 8, st, a, n, square, rows_per)) return rc;
     return 1;
 }
 
@@ -1435,9 +1396,8 @@ int qr_cholesky_batch(int count, double *const *A, int64_t m, int n, int stream,
     if ((rc = prod(tri, cA, cR1, pQ1))) return rc;                                                            // Q1 = A R1^-1
     if ((rc = prod(gram, cQ1, cQ1, pG))) return rc;                                                           // Q1^T Q1 ~ identity
     static const int chol_expand = [] { const char *e = getenv("TTSK_CHOL_EXPAND"); return e ? atoi(e) : 1; }();
-    hipLaunchKernelGGL(chol_inv_kernel, dim3((unsigned)count), dim3(256), (size_t)(n * (n + 1) + n) * 8, st, (const double *)G, n, R2, (double *)nullptr,
-                       status + count, 0.5, sticky, (double *)nullptr, (const double *)nullptr, 0, chol_expand ? 2 : 0);
-    TTSK_LAUNCH_CHECK();
+    if ((rc = launch(chol_inv_kernel, dim3((unsigned)count), dim3(256), (size_t)(n * (n + 1) + n) * 8, st, (const double *)G, n, R2, (double *)nullptr,
+                     status + count, 0.5, sticky, (double *)nullptr, (const double *)nullptr, 0, chol_expand ? 2 : 0))) return rc;
     if ((rc = prod(tri, cQ1, cR2, A))) return rc;                                                             // Q = Q1 R2^-1
     return 1;
 }
@@ -1468,8 +1428,7 @@ int apply_signs(int count, double *const *cores, const double *const *sp, const 
             f.core[q] = cores[c0 + q]; f.sp[q] = sp[c0 + q]; f.sn[q] = sn[c0 + q];
             f.k0[q] = k0[c0 + q]; f.nn[q] = nn[c0 + q]; f.k1[q] = k1[c0 + q];
         }
-        hipLaunchKernelGGL(apply_signs_kernel, dim3(160, cnt), dim3(256), 0, st, f);
-        TTSK_LAUNCH_CHECK();
+        if (int rc = launch(apply_signs_kernel, dim3(160, cnt), dim3(256), 0, st, f)) return rc;
     }
     return TTSK_OK;
 }
@@ -1482,7 +1441,6 @@ using namespace ttsk;
 static int jacobi_lds_mode(int64_t mW, int64_t nW, size_t *bytes)
 {
     static const int off = getenv("TTSK_JACOBI_GLOBAL") ? 1 : 0;
-    static PerInit attr_done;
     const size_t cap = 160 * 1024 - 256;            // 160 KB per CU minus the kernel's few static bytes
     const size_t w = (size_t)mW * nW * 8, v = (size_t)nW * nW * 8;
     const size_t small = ((size_t)nW + (nW + 1) / 2) * 8;          // sigma^2 and the sort order
@@ -1492,17 +1450,16 @@ static int jacobi_lds_mode(int64_t mW, int64_t nW, size_t *bytes)
         if (small + w + v <= cap) { mode = 2; *bytes = small + w + v; }
         else if (small + w <= cap) { mode = 1; *bytes = small + w; }
     }
-    if (attr_done.first()) {
+    static int precond_gen = -1;                    // device state: set again after a re-init
+    if (precond_gen != init_generation()) {
         if (const char *e = getenv("TTSK_JACOBI_PRECOND")) {
             const int v = atoi(e);
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(jac_precond_on), &v, sizeof(int));
+            if (hipMemcpyToSymbol(HIP_SYMBOL(jac_precond_on), &v, sizeof(int)) != hipSuccess) {
+                set_error("jacobi: cannot set TTSK_JACOBI_PRECOND on the device");
+                return -1;
+            }
         }
-        if (hipFuncSetAttribute((const void *)jacobi_pinv_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap) != hipSuccess ||
-            hipFuncSetAttribute((const void *)jacobi_pinv_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap) != hipSuccess ||
-            hipFuncSetAttribute((const void *)jacobi_pinv_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap) != hipSuccess) {
-            set_error("jacobi: cannot raise the dynamic LDS limit");
-            return -1;
-        }
+        precond_gen = init_generation();
     }
     return mode;
 }
@@ -1569,15 +1526,13 @@ int ttsk_pinv_end(const double *dev_omega, int64_t l, int64_t r, double rcond, d
     const int jm = jacobi_lds_mode(mW, nW, &jl);
     if (jm < 0) return TTSK_ERR_HIP;
     auto kern = jm == 2 ? jacobi_pinv_kernel<2> : (jm == 1 ? jacobi_pinv_kernel<1> : jacobi_pinv_kernel<0>);
-    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), jl, st, dev_omega, l, r, transposed, ws,
-                       ws + mW * nW, rcond, dev_pinv, host_rank ? drank : (int *)nullptr, (double *)nullptr,
-                       (double *)nullptr, (double *)nullptr, predicate, (int64_t)0, (int64_t)0);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && host_rank) {
-        e = hipMemcpyAsync(host_rank, drank, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (int rc = launch(kern, dim3(1), dim3(1024), jl, st, dev_omega, l, r, transposed, ws,
+                        ws + mW * nW, rcond, dev_pinv, host_rank ? drank : (int *)nullptr, (double *)nullptr,
+                        (double *)nullptr, (double *)nullptr, predicate, (int64_t)0, (int64_t)0)) return rc;
+    if (host_rank) {
+        TTSK_HIP(hipMemcpyAsync(host_rank, drank, sizeof(int), hipMemcpyDeviceToHost, st));
+        TTSK_HIP(hipStreamSynchronize(st));
     }
-    TTSK_HIP(e);
     return TTSK_OK;
 }
 
@@ -1641,15 +1596,12 @@ int ttsk_pinv_batch(int count, const double *const *dev_omegas, int64_t l, int64
     const int64_t os = count >= 2 ? Om[1] - Om[0] : 0, ps = count >= 2 ? P[1] - P[0] : 0;
     for (int b = 2; b < count && spaced; ++b) spaced = Om[b] - Om[b - 1] == os && P[b] - P[b - 1] == ps;
     if (spaced && os >= 0 && ps > 0) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(1024), jl, st, Om[0], l, r, transposed, ws, ws + mW * nW, rcond, P[0], (int *)nullptr,
-                           (double *)nullptr, (double *)nullptr, (double *)nullptr, (const int *)status, os, ps);
-        TTSK_LAUNCH_CHECK();
-        return TTSK_OK;
+        return launch(kern, dim3((unsigned)count), dim3(1024), jl, st, Om[0], l, r, transposed, ws, ws + mW * nW, rcond, P[0], (int *)nullptr,
+                      (double *)nullptr, (double *)nullptr, (double *)nullptr, (const int *)status, os, ps);
     }
     for (int b = 0; b < count; ++b) {
-        hipLaunchKernelGGL(kern, dim3(1), dim3(1024), jl, st, Om[b], l, r, transposed, ws, ws + mW * nW, rcond, P[b], (int *)nullptr,
-                           (double *)nullptr, (double *)nullptr, (double *)nullptr, (const int *)(status + b), (int64_t)0, (int64_t)0);
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(kern, dim3(1), dim3(1024), jl, st, Om[b], l, r, transposed, ws, ws + mW * nW, rcond, P[b], (int *)nullptr,
+                         (double *)nullptr, (double *)nullptr, (double *)nullptr, (const int *)(status + b), (int64_t)0, (int64_t)0))) return rc;
     }
     return TTSK_OK;
 }
@@ -1682,10 +1634,9 @@ int jacobi_pinv_spaced(int count, const double *omega, int64_t os, int64_t l, in
     const int jm = jacobi_lds_mode(mW, nW, &jl);
     if (jm < 0) return TTSK_ERR_HIP;
     if (jm != 2) return 0;
-    hipLaunchKernelGGL(jacobi_pinv_kernel<2>, dim3((unsigned)count), dim3(1024), jl, st, omega, l, r, transposed, (double *)nullptr,
-                       (double *)nullptr, pinv_rcond(l, r, -1.0), P, (int *)nullptr, (double *)nullptr, (double *)nullptr,
-                       (double *)nullptr, status, os, ps);
-    TTSK_LAUNCH_CHECK();
+    if (int rc = launch(jacobi_pinv_kernel<2>, dim3((unsigned)count), dim3(1024), jl, st, omega, l, r, transposed, (double *)nullptr,
+                        (double *)nullptr, pinv_rcond(l, r, -1.0), P, (int *)nullptr, (double *)nullptr, (double *)nullptr,
+                        (double *)nullptr, status, os, ps)) return rc;
     return 1;
 }
 
@@ -1778,16 +1729,14 @@ int ttsk_pinv_batch_deferred(int count, const double *const *dev_omegas, int64_t
         if ((rc = launch_chol(G0, n, R0, I0, status, 1.0 / 3.0e4, st, sticky, nullptr, count))) return rc;
         TTSK_PB(small_try_batch(desc(r, l, l, 1, r, l, 1, 1.0), count, Om, cI, X, stream, st));                  // X0 = Omega^T G^-1
         TTSK_PB(small_try_batch(desc(l, l, r, r, 1, l, 1, -1.0), count, Om, cX, G, stream, st));                 // E = -Omega X0
-        hipLaunchKernelGGL(add_diag_kernel, dim3((unsigned)count), dim3(256), 0, st, G0, n, 2.0);                // E = 2 I - Omega X0
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(add_diag_kernel, dim3((unsigned)count), dim3(256), 0, st, G0, n, 2.0))) return rc;      // E = 2 I - Omega X0
         TTSK_PB(small_try_batch(desc(r, l, l, l, 1, l, 1, 1.0), count, cX, cG, P, stream, st));                  // X1 = X0 E
     } else {
         TTSK_PB(small_try_batch(desc(r, r, l, 1, r, r, 1, 1.0), count, Om, Om, G, stream, st));                  // G = Omega^T Omega
         if ((rc = launch_chol(G0, n, R0, I0, status, 1.0 / 3.0e4, st, sticky, nullptr, count))) return rc;
         TTSK_PB(small_try_batch(desc(r, l, r, r, 1, 1, r, 1.0), count, cI, Om, X, stream, st));                  // X0 = G^-1 Omega^T
         TTSK_PB(small_try_batch(desc(r, r, l, l, 1, r, 1, -1.0), count, cX, Om, G, stream, st));                 // E = -X0 Omega
-        hipLaunchKernelGGL(add_diag_kernel, dim3((unsigned)count), dim3(256), 0, st, G0, n, 2.0);
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(add_diag_kernel, dim3((unsigned)count), dim3(256), 0, st, G0, n, 2.0))) return rc;
         TTSK_PB(small_try_batch(desc(r, l, r, r, 1, l, 1, 1.0), count, cG, cX, P, stream, st));                  // X1 = E X0
     }
 #undef TTSK_PB
@@ -1851,10 +1800,8 @@ int ttsk_svd_small(const double *dev_A, int64_t m, int64_t n, double *dev_US, do
     const int jm = jacobi_lds_mode(m, n, &jl);
     if (jm < 0) return TTSK_ERR_HIP;
     auto kern = jm == 2 ? jacobi_pinv_kernel<2> : (jm == 1 ? jacobi_pinv_kernel<1> : jacobi_pinv_kernel<0>);
-    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), jl, st, dev_A, m, n, 0, ws, ws + m * n, 0.0,
-                       (double *)nullptr, (int *)nullptr, dev_US, dev_S, dev_Vt, (const int *)nullptr, (int64_t)0, (int64_t)0);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(kern, dim3(1), dim3(1024), jl, st, dev_A, m, n, 0, ws, ws + m * n, 0.0,
+                  (double *)nullptr, (int *)nullptr, dev_US, dev_S, dev_Vt, (const int *)nullptr, (int64_t)0, (int64_t)0);
 }
 
 int ttsk_triu(double *A, int64_t m, int64_t n, int stream)
@@ -1862,9 +1809,7 @@ int ttsk_triu(double *A, int64_t m, int64_t n, int stream)
     TTSK_STREAM(st, stream);
     TTSK_ARG(A && m >= 1 && n >= 1, "ttsk_triu: bad argument");
     const int64_t blocks = cdiv(m * n, 256);
-    hipLaunchKernelGGL(triu_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, A, m, n);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(triu_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, A, m, n);
 }
 
 int ttsk_qr_thin(double *A, int64_t m, int64_t n, int stream)
@@ -1885,28 +1830,27 @@ int ttsk_qr_thin(double *A, int64_t m, int64_t n, int stream)
     if (!ws) return TTSK_ERR_HIP;
     double *tpart = ws, *wpart = ws + (size_t)n * nb, *Q = ws + small;
     auto blocks_at = [&](int64_t j) { return (int)cdiv(m - j, QR_ROWS); };
-    hipLaunchKernelGGL(qr_tail_norm_kernel, dim3(blocks_at(0)), dim3(256), 0, st, A, m, n, (int64_t)0, tpart);
+    int rc;
+    if ((rc = launch(qr_tail_norm_kernel, dim3(blocks_at(0)), dim3(256), 0, st, A, m, n, (int64_t)0, tpart))) return rc;
     // factorisation: reflector j from column j applied to columns j+1..n-1; the update of
     // column j also leaves the tail-norm partials of column j+1 in tpart[j+1][*]
     for (int64_t j = 0; j + 1 < n; ++j) {
         const int nbj = blocks_at(j);
-        hipLaunchKernelGGL(qr_w_kernel, dim3(nbj), dim3(256), 0, st, A, A, m, n, j, j + 1, tpart + j * nb,
-                           blocks_at(j > 0 ? j - 1 : 0), wpart);
-        hipLaunchKernelGGL(qr_update_kernel, dim3(nbj), dim3(256), 0, st, A, A, m, n, j, j + 1,
-                           tpart + j * nb, blocks_at(j > 0 ? j - 1 : 0), wpart, nbj, tpart + (j + 1) * nb);
+        if ((rc = launch(qr_w_kernel, dim3(nbj), dim3(256), 0, st, A, A, m, n, j, j + 1, tpart + j * nb,
+                         blocks_at(j > 0 ? j - 1 : 0), wpart))) return rc;
+        if ((rc = launch(qr_update_kernel, dim3(nbj), dim3(256), 0, st, A, A, m, n, j, j + 1,
+                         tpart + j * nb, blocks_at(j > 0 ? j - 1 : 0), wpart, nbj, tpart + (j + 1) * nb))) return rc;
     }
     // Q = H_0 H_1 ... H_{n-1} [I; 0]
-    hipLaunchKernelGGL(eye_kernel, dim3(1024), dim3(256), 0, st, Q, m, n);
+    if ((rc = launch(eye_kernel, dim3(1024), dim3(256), 0, st, Q, m, n))) return rc;
     for (int64_t j = n - 1; j >= 0; --j) {
         const int nbj = blocks_at(j);
         const int nbt = blocks_at(j > 0 ? j - 1 : 0);
-        hipLaunchKernelGGL(qr_w_kernel, dim3(nbj), dim3(256), 0, st, A, Q, m, n, j, j, tpart + j * nb, nbt, wpart);
-        hipLaunchKernelGGL(qr_update_kernel, dim3(nbj), dim3(256), 0, st, A, Q, m, n, j, j, tpart + j * nb, nbt,
-                           wpart, nbj, (double *)nullptr);
+        if ((rc = launch(qr_w_kernel, dim3(nbj), dim3(256), 0, st, A, Q, m, n, j, j, tpart + j * nb, nbt, wpart))) return rc;
+        if ((rc = launch(qr_update_kernel, dim3(nbj), dim3(256), 0, st, A, Q, m, n, j, j, tpart + j * nb, nbt,
+                         wpart, nbj, (double *)nullptr))) return rc;
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(A, Q, (size_t)m * n * 8, hipMemcpyDeviceToDevice, st);
-    TTSK_HIP(e);
+    TTSK_HIP(hipMemcpyAsync(A, Q, (size_t)m * n * 8, hipMemcpyDeviceToDevice, st));
     return TTSK_OK;
 }
 

@@ -1,4 +1,5 @@
 // Runtime: device selection, streams, memory, timers, hipGraph capture.
+#include <atomic>
 #include <cstring>
 #include <mutex>
 #include "common.h"
@@ -61,6 +62,46 @@ static int g_generation = 0;
 
 int init_generation() { return g_generation; }
 
+// Kernels whose dynamic-LDS limit is raised in this init generation, by address (open addressing).  A kernel is entered
+// only after its hipFuncSetAttribute succeeded; writers hold g_mu, ttsk_shutdown clears the table, and finding an entered
+// kernel takes no lock.  A full table only costs the kernels left out a locked set-up per launch.
+enum { LDS_SLOTS = 4096 };
+static std::atomic<const void *> g_lds_raised[LDS_SLOTS];
+static int g_lds_per_wg = 0;   // the device's LDS per workgroup, read at init
+
+static unsigned lds_home(const void *k) { return (unsigned)(((uintptr_t)k >> 4) * 0x9E3779B97F4A7C15ull >> 52); }   // 12 bits
+
+static bool lds_raised(const void *k)
+{
+    for (unsigned i = lds_home(k), n = 0; n < LDS_SLOTS; ++n, i = (i + 1) % LDS_SLOTS) {
+        const void *q = g_lds_raised[i].load(std::memory_order_acquire);
+        if (q == k) return true;
+        if (!q) return false;
+    }
+    return false;
+}
+
+int raise_lds_limit(const void *k, const char *file, int line)
+{
+    if (lds_raised(k)) return TTSK_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (lds_raised(k)) return TTSK_OK;
+    hipFuncAttributes fa;
+    hipError_t e = hipFuncGetAttributes(&fa, k);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, g_lds_per_wg - (int)fa.sharedSizeBytes);
+    if (e != hipSuccess) {
+        set_error("cannot raise the dynamic LDS limit of the kernel launched at %s:%d: %s", file, line, hipGetErrorString(e));
+        return TTSK_ERR_HIP;
+    }
+    for (unsigned i = lds_home(k), n = 0; n < LDS_SLOTS; ++n, i = (i + 1) % LDS_SLOTS)
+        if (!g_lds_raised[i].load(std::memory_order_relaxed)) {
+            g_lds_raised[i].store(k, std::memory_order_release);
+            break;
+        }
+    return TTSK_OK;
+}
+
 void *persistent_alloc(int key, size_t bytes, bool host, bool zero)
 {
     if (ensure_init() != TTSK_OK || key < 0 || key >= PA_SLOTS) return nullptr;
@@ -110,6 +151,7 @@ int ttsk_init(int device)
     }
     TTSK_ARG(device >= 0 && device < n, "device %d out of range (%d devices)", device, n);
     TTSK_HIP(hipSetDevice(device));
+    TTSK_HIP(hipDeviceGetAttribute(&g_lds_per_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
     for (int i = 0; i < TTSK_NUM_STREAMS; ++i) {
         TTSK_HIP(hipStreamCreateWithFlags(&g_streams[i], hipStreamNonBlocking));
         TTSK_HIP(hipEventCreate(&g_ev_start[i]));
@@ -141,6 +183,7 @@ int ttsk_shutdown(void)
         if (g_pa[k]) (void)(g_pa_host[k] ? hipHostFree(g_pa[k]) : hipFree(g_pa[k]));
         g_pa[k] = nullptr;
     }
+    for (auto &k : g_lds_raised) k.store(nullptr, std::memory_order_relaxed);
     ++g_generation;
     g_init = false;
     g_device = -1;

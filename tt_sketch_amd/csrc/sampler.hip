@@ -275,22 +275,17 @@ static unsigned grid_for(size_t n, unsigned block = 256, unsigned cap = 16384)
 }
 
 template <int MODE>
-static void launch_sample(const int64_t *idx, const IndexMap &im, size_t N, int rank_min, int w, uint64_t seed,
-                          double *out, hipStream_t st)
+static int launch_sample(const int64_t *idx, const IndexMap &im, size_t N, int rank_min, int w, uint64_t seed,
+                         double *out, hipStream_t st)
 {
-    if (w <= 32) {
-        static PerInit attr_done;       // 256 x w tile + salts + tail queue: up to 82 KB at w = 32
-        if (attr_done.first()) {
-            (void)hipFuncSetAttribute((const void *)sample_rows_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        }
+    if (w <= 32) {      // 256 x w tile + salts + tail queue: up to 82 KB at w = 32
         size_t blocks = (N + 255) / 256;
         if (blocks > (1u << 16)) blocks = 1u << 16;
-        hipLaunchKernelGGL((sample_rows_kernel<MODE>), dim3((unsigned)blocks), dim3(256), (size_t)(256 * w + w) * 8 + (size_t)256 * w * 2, st,
-                           idx, im, N, rank_min, w, seed, out);
-    } else {
-        hipLaunchKernelGGL((sample_kernel<MODE>), dim3(grid_for(N * (size_t)w, 256, 1u << 20)), dim3(256), 0, st, idx,
-                           im, N, rank_min, w, seed, out);
+        return launch(sample_rows_kernel<MODE>, dim3((unsigned)blocks), dim3(256), (size_t)(256 * w + w) * 8 + (size_t)256 * w * 2, st,
+                      idx, im, N, rank_min, w, seed, out);
     }
+    return launch(sample_kernel<MODE>, dim3(grid_for(N * (size_t)w, 256, 1u << 20)), dim3(256), 0, st, idx,
+                  im, N, rank_min, w, seed, out);
 }
 
 // out[e, :] = table[flat index of row e, :]; a workgroup takes 256 rows at a time: their flat indices once into
@@ -324,10 +319,8 @@ static int sign_dev(const int64_t *dev_idx, const IndexMap &im, size_t N, int tr
     if (N == 0 || rank_max == rank_min) return TTSK_OK;
     int8_t *ws = (int8_t *)scratch(stream, SCRATCH_MISC, N * (size_t)true_rank);
     if (!ws) return TTSK_ERR_HIP;
-    hipLaunchKernelGGL((sign_kernel<OUT>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, dev_idx, im,
-                       N, true_rank, nnz, rank_min, rank_max, seed, ws, dev_out);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(sign_kernel<OUT>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, dev_idx, im,
+                  N, true_rank, nnz, rank_min, rank_max, seed, ws, dev_out);
 }
 
 }  // namespace ttsk
@@ -352,8 +345,8 @@ int ttsk_ndtri_rate_probe(double *gsamples)
         double best = 0;
         for (int rep = 0; rep < 4; ++rep) {
             TTSK_HIP(hipEventRecord(a, st));
-            if (mode == 0) hipLaunchKernelGGL((ndtri_probe_kernel<0>), dim3(blocks), dim3(256), 0, st, sink, reps, (uint64_t)(17 + rep));
-            else hipLaunchKernelGGL((ndtri_probe_kernel<1>), dim3(blocks), dim3(256), 0, st, sink, reps, (uint64_t)(17 + rep));
+            if (int rc = launch(mode == 0 ? ndtri_probe_kernel<0> : ndtri_probe_kernel<1>, dim3(blocks), dim3(256), 0, st, sink, reps,
+                                (uint64_t)(17 + rep))) return rc;
             TTSK_HIP(hipEventRecord(b, st));
             TTSK_HIP(hipEventSynchronize(b));
             float ms = 0;
@@ -376,9 +369,9 @@ int ttsk_hash_u64(uint64_t *host_vals, size_t n)
     uint64_t *d = nullptr;
     TTSK_HIP(hipMalloc((void **)&d, n * 8));
     hipError_t e = hipMemcpyAsync(d, host_vals, n * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(hash_kernel, dim3(grid_for(n)), dim3(256), 0, st, d, n);
-        e = hipGetLastError();
+    if (e == hipSuccess && launch(hash_kernel, dim3(grid_for(n)), dim3(256), 0, st, d, n) != TTSK_OK) {
+        (void)hipFree(d);
+        return TTSK_ERR_HIP;
     }
     if (e == hipSuccess) e = hipMemcpyAsync(host_vals, d, n * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -415,16 +408,11 @@ int ttsk_sparse_normal_dev(const int64_t *dev_idx, int64_t row_stride, const int
         const size_t P = (size_t)prod;
         double *table = (double *)scratch(stream, SCRATCH_MISC, P * (size_t)w * 8);
         if (!table) return TTSK_ERR_HIP;
-        launch_sample<1>(nullptr, im, P, rank_min, w, seed, table, st);
-        TTSK_LAUNCH_CHECK();
-        hipLaunchKernelGGL(expand_rows_kernel, dim3(grid_for(N, 256, 1u << 15)), dim3(256), 0, st, dev_idx, im, N, w, table,
-                           dev_out);
-        TTSK_LAUNCH_CHECK();
-        return TTSK_OK;
+        if ((rc = launch_sample<1>(nullptr, im, P, rank_min, w, seed, table, st))) return rc;
+        return launch(expand_rows_kernel, dim3(grid_for(N, 256, 1u << 15)), dim3(256), 0, st, dev_idx, im, N, w, table,
+                      dev_out);
     }
-    launch_sample<1>(dev_idx, im, N, rank_min, w, seed, dev_out, st);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch_sample<1>(dev_idx, im, N, rank_min, w, seed, dev_out, st);
 }
 
 // The samples of EVERY possible index prefix: row f of the table is what ttsk_sparse_normal_dev returns for an index
@@ -445,10 +433,9 @@ int ttsk_sparse_normal_table(const uint64_t *shape, int m, int rank_min, int ran
     }
     const bool prof = prof_on();
     if (prof) prof_open_named(st, PROF_SAMPLER, prod * (rank_max - rank_min), "sample_rows_kernel (prefix table)");
-    launch_sample<1>(nullptr, im, (size_t)prod, rank_min, rank_max - rank_min, seed, dev_out, st);
+    rc = launch_sample<1>(nullptr, im, (size_t)prod, rank_min, rank_max - rank_min, seed, dev_out, st);
     if (prof) prof_close(st);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return rc;
 }
 
 int ttsk_sparse_sign_dev(const int64_t *dev_idx, int64_t row_stride, const int *row_order,
@@ -500,12 +487,11 @@ static int host_sample(const void *host_idx, const uint64_t *shape, int m, size_
     int status = TTSK_OK;
     if (e == hipSuccess) {
         if (mode == 0)
-            launch_sample<0>(didx, im, N, rank_min, w, seed, (double *)dout, st);
+            status = launch_sample<0>(didx, im, N, rank_min, w, seed, (double *)dout, st);
         else if (mode == 1)
-            launch_sample<1>(didx, im, N, rank_min, w, seed, (double *)dout, st);
+            status = launch_sample<1>(didx, im, N, rank_min, w, seed, (double *)dout, st);
         else
             status = sign_dev<int16_t>(didx, im, N, true_rank, rank_min, rank_max, nnz, seed, (int16_t *)dout, st, 0);
-        e = hipGetLastError();
     }
     if (e == hipSuccess && status == TTSK_OK)
         e = hipMemcpyAsync(host_out, dout, out_bytes, hipMemcpyDeviceToHost, st);
@@ -542,10 +528,8 @@ int ttsk_fill_normal(double *dev_out, size_t n, uint64_t seed, double scale, int
     TTSK_STREAM(st, stream);
     if (n == 0) return TTSK_OK;
     uint64_t key = mix64(seed ^ 0x9E3779B97F4A7C15ULL);
-    hipLaunchKernelGGL(fill_normal_kernel, dim3(grid_for(n, 2048, 1u << 16)), dim3(256), 0, st, dev_out, n,
-                       key, scale);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(fill_normal_kernel, dim3(grid_for(n, 2048, 1u << 16)), dim3(256), 0, st, dev_out, n,
+                  key, scale);
 }
 
 int ttsk_fill_normal_many(int count, double *const *dev_outs, const size_t *ns, const uint64_t *seeds,
@@ -565,8 +549,7 @@ int ttsk_fill_normal_many(int count, double *const *dev_outs, const size_t *ns, 
             nmax = a.n[i] > nmax ? a.n[i] : nmax;
         }
         if (nmax == 0) continue;
-        hipLaunchKernelGGL(fill_normal_many_kernel, dim3(grid_for(nmax, 2048, 1u << 14), (unsigned)cnt), dim3(256), 0, st, a);
-        TTSK_LAUNCH_CHECK();
+        if (int rc = launch(fill_normal_many_kernel, dim3(grid_for(nmax, 2048, 1u << 14), (unsigned)cnt), dim3(256), 0, st, a)) return rc;
     }
     return TTSK_OK;
 }

@@ -139,15 +139,13 @@ int launch_r_reduce(hipStream_t st, const double *slab, int chunks, int M, int N
     const unsigned gy = (unsigned)(nprob * m_tiles);
     static const int wide = [] { const char *e = getenv("TTSK_REDUCE_WIDE"); return e ? atoi(e) : 1; }();
     if (vec && wide && chunks >= 64 && gy * cdiv(mn / 2, 64) >= 64)
-        hipLaunchKernelGGL(skinny_r_reduce2w, dim3((unsigned)cdiv(mn / 2, 64), gy), dim3(1024), 0, st, (const double2 *)slab, chunks, M,
-                           N, m_tiles, Mtot, ro, c_m, alpha, accumulate);
-    else if (vec)
-        hipLaunchKernelGGL(skinny_r_reduce2, dim3((unsigned)cdiv(mn / 2, 16), gy), dim3(256), 0, st, (const double2 *)slab, chunks, M, N,
-                           m_tiles, Mtot, ro, c_m, alpha, accumulate);
-    else
-        hipLaunchKernelGGL(skinny_r_reduce, dim3((unsigned)cdiv(mn, 16), gy), dim3(256), 0, st, slab, chunks, M, N, m_tiles, Mtot, ro,
-                           c_m, c_n, alpha, accumulate);
-    return hipGetLastError() == hipSuccess ? TTSK_OK : TTSK_ERR_HIP;
+        return launch(skinny_r_reduce2w, dim3((unsigned)cdiv(mn / 2, 64), gy), dim3(1024), 0, st, (const double2 *)slab, chunks, M,
+                      N, m_tiles, Mtot, ro, c_m, alpha, accumulate);
+    if (vec)
+        return launch(skinny_r_reduce2, dim3((unsigned)cdiv(mn / 2, 16), gy), dim3(256), 0, st, (const double2 *)slab, chunks, M, N,
+                      m_tiles, Mtot, ro, c_m, alpha, accumulate);
+    return launch(skinny_r_reduce, dim3((unsigned)cdiv(mn, 16), gy), dim3(256), 0, st, slab, chunks, M, N, m_tiles, Mtot, ro,
+                  c_m, c_n, alpha, accumulate);
 }
 
 static int num_cu()

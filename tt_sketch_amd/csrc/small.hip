@@ -171,10 +171,9 @@ int small_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, con
     static const int ks_max = [] { const char *e = getenv("TTSK_SMALL_KSPLIT"); return e ? atoi(e) : 8; }();
     int ksplit = K >= 512 ? 8 : (K >= 256 ? 4 : (K >= 128 ? 2 : 1));
     if (ksplit > ks_max) ksplit = ks_max;
-    hipLaunchKernelGGL(small_gemm_kernel, dim3((unsigned)(count * g.tiles_m * g.tiles_n)), dim3(64 * ksplit), 0, st, g);
+    const int rc = launch(small_gemm_kernel, dim3((unsigned)(count * g.tiles_m * g.tiles_n)), dim3(64 * ksplit), 0, st, g);
     if (prof) prof_close(st);
-    TTSK_LAUNCH_CHECK();
-    return 1;
+    return rc == TTSK_OK ? 1 : rc;
 }
 
 }  // namespace ttsk

@@ -309,10 +309,8 @@ int ttsk_sparse_ttdrm_step(const double *dev_vin, int64_t rho, const double *dev
     TTSK_ARG(rho >= 1 && rhop >= 1 && n >= 1, "ttsk_sparse_ttdrm_step: bad core shape");
     TTSK_ARG(dev_vin || rho == 1, "ttsk_sparse_ttdrm_step: first mode needs rho == 1");
     if (N == 0) return TTSK_OK;
-    hipLaunchKernelGGL(sparse_ttdrm_kernel, dim3(grid_for(N * (size_t)rhop, 1u << 20)), dim3(256), 0, st,
-                       dev_vin, rho, dev_core, n, rhop, dev_idx_row, N, dev_vout);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(sparse_ttdrm_kernel, dim3(grid_for(N * (size_t)rhop, 1u << 20)), dim3(256), 0, st,
+                  dev_vin, rho, dev_core, n, rhop, dev_idx_row, N, dev_vout);
 }
 
 int ttsk_sparse_densedrm_gather(const double *dev_mat, int64_t rank, int64_t cols, const int64_t *dev_idx,
@@ -333,10 +331,8 @@ int ttsk_sparse_densedrm_gather(const double *dev_mat, int64_t rank, int64_t col
     TTSK_ARG(mult == cols, "ttsk_sparse_densedrm_gather: matrix has %lld columns, index space %lld",
              (long long)cols, (long long)mult);
     if (N == 0 || rank == 0) return TTSK_OK;
-    hipLaunchKernelGGL(sparse_dense_gather_kernel, dim3(grid_for(N * (size_t)rank, 1u << 20)), dim3(256), 0,
-                       st, dev_mat, rank, cols, dev_idx, rm, N, dev_out);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(sparse_dense_gather_kernel, dim3(grid_for(N * (size_t)rank, 1u << 20)), dim3(256), 0,
+                  st, dev_mat, rank, cols, dev_idx, rm, N, dev_out);
 }
 
 int ttsk_sparse_sort_mode(const int64_t *dev_idx_row, size_t N, int64_t n, int64_t *dev_perm, int stream)
@@ -355,8 +351,7 @@ int ttsk_sparse_sort_mode(const int64_t *dev_idx_row, size_t N, int64_t n, int64
     int64_t *keys_out = (int64_t *)ws, *vals_in = (int64_t *)(ws + N * 8);
     void *temp = ws + 2 * N * 8;
     TTSK_ARG(N < (1ull << 31), "ttsk_sparse_sort_mode: more than 2^31 nonzeros");
-    hipLaunchKernelGGL(iota_kernel, dim3(grid_for(N, 1u << 16)), dim3(256), 0, st, vals_in, N);
-    TTSK_LAUNCH_CHECK();
+    if (int rc = launch(iota_kernel, dim3(grid_for(N, 1u << 16)), dim3(256), 0, st, vals_in, N)) return rc;
     TTSK_HIP(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, dev_idx_row, keys_out, vals_in, dev_perm, (int)N, 0,
                                                 bits, st));
     return TTSK_OK;
@@ -392,23 +387,14 @@ int ttsk_sparse_psi(const double *dev_val, const int64_t *dev_idx_row, const int
             if (!part) return TTSK_ERR_HIP;
         }
         const int64_t *idxp = single ? nullptr : dev_idx_row;
-#define TTSK_PSI_GO(TL, TR)                                                                                              \
-        do {                                                                                                           \
-            if (dev_perm) hipLaunchKernelGGL((sparse_psi_mfma_kernel<TL, TR, true>), dim3((unsigned)blocks), dim3(256), 0, st, \
-                                             dev_val, idxp, dev_perm, N, dev_Lv, (int)l, dev_Rv, (int)r, n, dev_psi, chunk, part); \
-            else hipLaunchKernelGGL((sparse_psi_mfma_kernel<TL, TR, false>), dim3((unsigned)blocks), dim3(256), 0, st,  \
-                                    dev_val, idxp, dev_perm, N, dev_Lv, (int)l, dev_Rv, (int)r, n, dev_psi, chunk, part); \
-        } while (0)
-        if (tl == 1 && tr == 1) TTSK_PSI_GO(1, 1);
-        else if (tl == 1) TTSK_PSI_GO(1, 2);
-        else if (tr == 1) TTSK_PSI_GO(2, 1);
-        else TTSK_PSI_GO(2, 2);
-#undef TTSK_PSI_GO
-        TTSK_LAUNCH_CHECK();
+#define TTSK_PSI_KERN(TL, TR) (dev_perm ? sparse_psi_mfma_kernel<TL, TR, true> : sparse_psi_mfma_kernel<TL, TR, false>)
+        auto kern = tl == 1 ? (tr == 1 ? TTSK_PSI_KERN(1, 1) : TTSK_PSI_KERN(1, 2)) : (tr == 1 ? TTSK_PSI_KERN(2, 1) : TTSK_PSI_KERN(2, 2));
+#undef TTSK_PSI_KERN
+        if (int rc = launch(kern, dim3((unsigned)blocks), dim3(256), 0, st, dev_val, idxp, dev_perm, N, dev_Lv, (int)l, dev_Rv, (int)r, n,
+                            dev_psi, chunk, part)) return rc;
         if (single) {
             const int lr = (int)(l * r);
-            hipLaunchKernelGGL(sparse_part_reduce_kernel, dim3((unsigned)lr), dim3(256), 0, st, part, waves, lr, dev_psi);
-            TTSK_LAUNCH_CHECK();
+            if (int rc = launch(sparse_part_reduce_kernel, dim3((unsigned)lr), dim3(256), 0, st, part, waves, lr, dev_psi)) return rc;
         }
         return TTSK_OK;
     }
@@ -417,10 +403,8 @@ int ttsk_sparse_psi(const double *dev_val, const int64_t *dev_idx_row, const int
              (long long)(l + r));
     size_t chunk = 4096;
     size_t blocks = (N + chunk - 1) / chunk;
-    hipLaunchKernelGGL(sparse_psi_kernel, dim3((unsigned)blocks), dim3(256), lds, st, dev_val, dev_idx_row, dev_perm,
-                       N, dev_Lv, l, dev_Rv, r, n, dev_psi, chunk);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(sparse_psi_kernel, dim3((unsigned)blocks), dim3(256), lds, st, dev_val, dev_idx_row, dev_perm,
+                  N, dev_Lv, l, dev_Rv, r, n, dev_psi, chunk);
 }
 
 }  // extern "C"

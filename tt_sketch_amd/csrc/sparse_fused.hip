@@ -625,8 +625,7 @@ int ttsk_sparse_mode_order(const int64_t *dev_idx, int64_t row_stride, size_t N,
     void *temp = ws + 3 * N * 8;
     size_t blocks = (N + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(sg_key_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dev_idx, rm, (int64_t)mode_row * row_stride, N, keys, iota);
-    TTSK_LAUNCH_CHECK();
+    if ((rc = launch(sg_key_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dev_idx, rm, (int64_t)mode_row * row_stride, N, keys, iota))) return rc;
     TTSK_HIP(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, keys_out, iota, dev_perm, (int)N, 0, 40 + bits, st));
     return TTSK_OK;
 }
@@ -654,14 +653,11 @@ static int sg_mode_stream(const int64_t *dev_idx, int64_t row_stride, const int6
             set_error("ttsk_sparse_mode_stream_u32: %g prefixes / %g suffixes do not fit 32-bit records", pl, pr);
             return TTSK_ERR_UNSUPPORTED;
         }
-        hipLaunchKernelGGL(sg_stream_kernel<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, st, dev_idx, lm, rm, (int64_t)mode_row * row_stride,
-                           dev_perm, dev_val, N, (uint32_t *)dev_fl, (uint32_t *)dev_fr, dev_j, dev_v);
-    } else {
-        hipLaunchKernelGGL(sg_stream_kernel<uint64_t>, dim3((unsigned)blocks), dim3(256), 0, st, dev_idx, lm, rm, (int64_t)mode_row * row_stride,
-                           dev_perm, dev_val, N, (uint64_t *)dev_fl, (uint64_t *)dev_fr, dev_j, dev_v);
+        return launch(sg_stream_kernel<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, st, dev_idx, lm, rm, (int64_t)mode_row * row_stride,
+                      dev_perm, dev_val, N, (uint32_t *)dev_fl, (uint32_t *)dev_fr, dev_j, dev_v);
     }
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
+    return launch(sg_stream_kernel<uint64_t>, dim3((unsigned)blocks), dim3(256), 0, st, dev_idx, lm, rm, (int64_t)mode_row * row_stride,
+                  dev_perm, dev_val, N, (uint64_t *)dev_fl, (uint64_t *)dev_fr, dev_j, dev_v);
 }
 
 int ttsk_sparse_mode_stream(const int64_t *dev_idx, int64_t row_stride, const int64_t *dev_perm, size_t N, const int *l_rows,
@@ -789,36 +785,17 @@ static int sg_gauss_pass(const void *dev_fl, const void *dev_fr, int w32, const 
     a.part_psi = (double *)ws;
     a.part_om = a.part_psi + wtot * 2 * cellsP;
     a.part_j = (int *)(a.part_om + wtot * (size_t)cellsO);
-    static PerInit attr;
-    if (attr.first()) {
-        TTSK_HIP(hipFuncSetAttribute((const void *)sg_pass_kernel<1, 0, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        TTSK_HIP(hipFuncSetAttribute((const void *)sg_pass_kernel<2, 0, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        TTSK_HIP(hipFuncSetAttribute((const void *)sg_pass_kernel<2, 1, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        TTSK_HIP(hipFuncSetAttribute((const void *)sg_pass_kernel<2, 2, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        TTSK_HIP(hipFuncSetAttribute((const void *)sg_pass_kernel<2, 0, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        TTSK_HIP(hipFuncSetAttribute((const void *)sg_pass_kernel<2, 1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        TTSK_HIP(hipFuncSetAttribute((const void *)sg_pass_kernel<2, 2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-    }
     const bool prof = prof_on();
     if (prof) prof_open_named(st, PROF_SPARSE, (w32 ? 20.0 : 28.0) * (double)N, "sg_pass_kernel");
-    const dim3 grid((unsigned)blocks), wg(256);
-    if (NT == 1) hipLaunchKernelGGL((sg_pass_kernel<1, 0, 32>), grid, wg, lds, st, a);
-    else if (T == 32) {
-        if (NS == 1) hipLaunchKernelGGL((sg_pass_kernel<2, 1, 32>), grid, wg, lds, st, a);
-        else if (NS == 2) hipLaunchKernelGGL((sg_pass_kernel<2, 2, 32>), grid, wg, lds, st, a);
-        else hipLaunchKernelGGL((sg_pass_kernel<2, 0, 32>), grid, wg, lds, st, a);
-    } else {
-        if (NS == 1) hipLaunchKernelGGL((sg_pass_kernel<2, 1, 16>), grid, wg, lds, st, a);
-        else if (NS == 2) hipLaunchKernelGGL((sg_pass_kernel<2, 2, 16>), grid, wg, lds, st, a);
-        else hipLaunchKernelGGL((sg_pass_kernel<2, 0, 16>), grid, wg, lds, st, a);
-    }
-    TTSK_LAUNCH_CHECK();
+    auto kern = NT == 1    ? sg_pass_kernel<1, 0, 32>
+                : T == 32  ? (NS == 1 ? sg_pass_kernel<2, 1, 32> : NS == 2 ? sg_pass_kernel<2, 2, 32> : sg_pass_kernel<2, 0, 32>)
+                           : (NS == 1 ? sg_pass_kernel<2, 1, 16> : NS == 2 ? sg_pass_kernel<2, 2, 16> : sg_pass_kernel<2, 0, 16>);
+    int rc = launch(kern, dim3((unsigned)blocks), dim3(256), lds, st, a);
+    if (rc) return rc;
     const int64_t rb = n < 4096 ? n : 4096;
-    hipLaunchKernelGGL(sg_psi_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, st, a.part_psi, a.part_j, (int)wtot, wA, wB, n, dev_psi);
-    TTSK_LAUNCH_CHECK();
+    if ((rc = launch(sg_psi_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, st, a.part_psi, a.part_j, (int)wtot, wA, wB, n, dev_psi))) return rc;
     if (a.has_om) {
-        hipLaunchKernelGGL(sg_om_reduce_kernel, dim3((unsigned)cellsO), dim3(256), 0, st, a.part_om, (int)wtot, cellsO, dev_omega);
-        TTSK_LAUNCH_CHECK();
+        if ((rc = launch(sg_om_reduce_kernel, dim3((unsigned)cellsO), dim3(256), 0, st, a.part_om, (int)wtot, cellsO, dev_omega))) return rc;
     }
     if (prof) prof_close(st);
     return TTSK_OK;

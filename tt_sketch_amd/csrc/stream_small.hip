@@ -4,22 +4,9 @@
 
 namespace ttsk {
 
-template <int NF, int STR, int UNR>
-static int launch_ss_one(const StreamSmall &a, size_t lds, int grid, hipStream_t st)
-{
-    auto kern = stream_small_kernel<NF, STR, 5, UNR>;
-    static PerInit attr_done;
-    if (attr_done.first()) {
-        TTSK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, a);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
-}
-
 static int launch_ss(const StreamSmall &a, int nf, int str, int unr, size_t lds, int grid, hipStream_t st)
 {
-#define TTSK_SS_CASE(NF, STR) if (nf == NF && str == STR) return unr == 25 ? launch_ss_one<NF, STR, 25>(a, lds, grid, st) : launch_ss_one<NF, STR, 5>(a, lds, grid, st);
+#define TTSK_SS_CASE(NF, STR) if (nf == NF && str == STR) return launch(unr == 25 ? stream_small_kernel<NF, STR, 5, 25> : stream_small_kernel<NF, STR, 5, 5>, dim3((unsigned)grid), dim3(512), lds, st, a);
     TTSK_SS_CASE(1, 0) TTSK_SS_CASE(1, 1) TTSK_SS_CASE(1, 2) TTSK_SS_CASE(2, 0) TTSK_SS_CASE(2, 1) TTSK_SS_CASE(2, 2)
     TTSK_SS_CASE(3, 0) TTSK_SS_CASE(3, 1) TTSK_SS_CASE(3, 2) TTSK_SS_CASE(4, 0) TTSK_SS_CASE(4, 1) TTSK_SS_CASE(4, 2)
     TTSK_SS_CASE(5, 0) TTSK_SS_CASE(5, 1) TTSK_SS_CASE(5, 2) TTSK_SS_CASE(6, 0) TTSK_SS_CASE(6, 1) TTSK_SS_CASE(6, 2)
@@ -92,22 +79,9 @@ int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st)
     return rc == TTSK_OK ? 1 : (rc == 1 ? 0 : rc);
 }
 
-template <int NF, int STR, int UNR>
-static int launch_sss_one(const StreamSmallSum &a, size_t lds, int grid, hipStream_t st)
-{
-    auto kern = stream_small_sum_kernel<NF, STR, 5, UNR>;
-    static PerInit attr_done;
-    if (attr_done.first()) {
-        TTSK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, a);
-    TTSK_LAUNCH_CHECK();
-    return TTSK_OK;
-}
-
 static int launch_sss(const StreamSmallSum &a, int nf, int str, int unr, size_t lds, int grid, hipStream_t st)
 {
-#define TTSK_SSS_CASE(NF, STR) if (nf == NF && str == STR) return unr == 25 ? launch_sss_one<NF, STR, 25>(a, lds, grid, st) : launch_sss_one<NF, STR, 5>(a, lds, grid, st);
+#define TTSK_SSS_CASE(NF, STR) if (nf == NF && str == STR) return launch(unr == 25 ? stream_small_sum_kernel<NF, STR, 5, 25> : stream_small_sum_kernel<NF, STR, 5, 5>, dim3((unsigned)grid), dim3(512), lds, st, a);
     TTSK_SSS_CASE(1, 0) TTSK_SSS_CASE(1, 1) TTSK_SSS_CASE(1, 2) TTSK_SSS_CASE(2, 0) TTSK_SSS_CASE(2, 1) TTSK_SSS_CASE(2, 2)
     TTSK_SSS_CASE(3, 0) TTSK_SSS_CASE(3, 1) TTSK_SSS_CASE(3, 2)
 #undef TTSK_SSS_CASE

@@ -259,9 +259,8 @@ int svd_jacobi_grid(const double *A, int64_t m, int64_t n, double *US, double *S
         TTSK_HIP(hipStreamWaitEvent(st, busy[i], 0));
     }
     TTSK_HIP(hipMemsetAsync(ctl, 0, sizeof(GridCtl), st));
-    hipLaunchKernelGGL(svd_grid_load_kernel, dim3((unsigned)cdiv(n, 32), (unsigned)cdiv(m, 32)), dim3(256), 0, st, A, (int)m,
-                       (int)n, W, V);
-    TTSK_LAUNCH_CHECK();
+    if (int rc = launch(svd_grid_load_kernel, dim3((unsigned)cdiv(n, 32), (unsigned)cdiv(m, 32)), dim3(256), 0, st, A, (int)m,
+                        (int)n, W, V)) return rc;
     {
         // cooperative launch: the runtime checks that the whole grid can be resident at once and refuses otherwise
         int mi = (int)m, ni = (int)n, sweeps = 60;
@@ -290,9 +289,8 @@ int svd_jacobi_grid(const double *A, int64_t m, int64_t n, double *US, double *S
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return h[(size_t)x] > h[(size_t)y]; });
     TTSK_HIP(hipMemcpyAsync(ord, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(svd_grid_store_kernel, dim3((unsigned)cdiv(n, 32), (unsigned)cdiv(m, 32)), dim3(256), 0, st, W, V, sig2,
-                       ord, (int)m, (int)n, US, S, Vt);
-    TTSK_LAUNCH_CHECK();
+    if (int rc = launch(svd_grid_store_kernel, dim3((unsigned)cdiv(n, 32), (unsigned)cdiv(m, 32)), dim3(256), 0, st, W, V, sig2,
+                        ord, (int)m, (int)n, US, S, Vt)) return rc;
     TTSK_HIP(hipStreamSynchronize(st));            // `order` is pageable host memory of this frame
     return TTSK_OK;
 }

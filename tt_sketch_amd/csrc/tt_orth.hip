@@ -379,8 +379,7 @@ static int orth_batch_fused(int count, int d, const int64_t *n, const int64_t *s
     }
     CK(fix_cores(d - 1));
     CK(ttsk_stream_wait(stream, aux));
-    hipLaunchKernelGGL(orth_spread_flag_kernel, dim3(1), dim3(64), 0, st, sticky, dev_status, count);
-    TTSK_LAUNCH_CHECK();
+    if ((rc = launch(orth_spread_flag_kernel, dim3(1), dim3(64), 0, st, sticky, dev_status, count))) return rc;
 #undef CK
     return 1;
 }
@@ -420,15 +419,14 @@ int ttsk_tt_orth_sketch_batch(int count, int d, const int64_t *n, const int64_t 
         used[q] = used[qa] = true;
         int *sticky = deferred_flag(q);
         if (!sticky) return TTSK_ERR_HIP;
-        if (q != stream) hipLaunchKernelGGL(orth_take_flag_kernel, dim3(1), dim3(64), 0, stream_of(q), sticky, dev_status + b);
+        if (q != stream && (rc = launch(orth_take_flag_kernel, dim3(1), dim3(64), 0, stream_of(q), sticky, dev_status + b))) return rc;
     }
     auto one = [&](int b) -> int {
         const int q = pair_of(b);
         int r = ttsk_tt_orth_sketch(d, n, s, lt, rt, X + (size_t)b * d, DL, DR, cores_out + (size_t)b * d,
                                     omega_out ? omega_out + (size_t)b * (d - 1) : nullptr, q);
         if (r < 0) return r;
-        hipLaunchKernelGGL(orth_take_flag_kernel, dim3(1), dim3(64), 0, stream_of(q), deferred_flag(q), dev_status + b);
-        return hipGetLastError() == hipSuccess ? TTSK_OK : TTSK_ERR_HIP;
+        return launch(orth_take_flag_kernel, dim3(1), dim3(64), 0, stream_of(q), deferred_flag(q), dev_status + b);
     };
     // (Queuing the tensors of each stream pair from a thread of their own was measured: 0.65 against 0.67 ms per tensor at C3,
     // batch 8 -- the host's 0.4 ms per sketch is not what binds, the device-side sum of ~90 small kernels per sketch is; not kept.)
