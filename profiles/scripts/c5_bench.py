@@ -22,4 +22,3 @@ def T(f, reps=5):
     return min(ts) * 1e3, out
 ms, stt = T(lambda: stream_sketch(X, (l,) * (d - 1), (r,) * (d - 1), left_drm=left, right_drm=right))
 print(f"C5 stream_sketch(TensorSum of {nt} TT rank {s}, d={d}, n={n}) l={l} r={r}: {ms:.2f} ms  -> {nt * d / ms * 1e3:.0f} TT-cores/s")
-os.environ["TTSK_SKINNY"] = "1"

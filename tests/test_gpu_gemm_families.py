@@ -28,8 +28,7 @@ nb * m_tiles * chunks, where chunks shrinks as nb grows), and the first group is
 picks the operand variant.  A rejection therefore happens for the first group or not at all; the first-group case is
 the generic path.
 
-No environment switch is set: the families are reached through shapes and strides alone (the TTSK_* switches are
-read once per process).
+The families are reached through shapes and strides alone: the library has no switch that selects among them.
 """
 import ctypes
 import re
@@ -169,41 +168,41 @@ CASES = [
          tags=("rl:padded_rows",)),
     Case("rl_n33_odd_c", RL, "mk,nk->mn", dense(64, 4096), dense(33, 4096), framed(64, 33), acc=1,
          tags=("rl:N=33",)),
-    # just outside its cover: skinny_r.  K % 64 != 0: gk variant (k contiguous on both sides, skinny.hip:248 `gk`),
-    # no swap (:235), 7 x 2 tiles > SKR_KSPLIT_TILES: nsub 1 (:297); 65 chunks of 64 (:273), the last one 4 long
+    # just outside its cover: skinny_r.  K % 64 != 0: gk variant (k contiguous on both sides, skinny.hip:231 `gk`),
+    # no swap (:221), 7 x 2 tiles > SKR_KSPLIT_TILES: nsub 1 (:282); 65 chunks of 64 (:258), the last one 4 long
     Case("rlx_k_not_64", SR(7, 2), "mk,nk->mn", dense(100, 4100), dense(20, 4100), framed(100, 20),
          tags=("rl-out:K%64", "sr:gk", "sr:nsub1", "sr:chunks_ragged", "sr:noswap")),
-    # A one element into its buffer (8-byte aligned): rows_longk and gk (:248) refuse it, generic variant (:244); nsub 8
+    # A one element into its buffer (8-byte aligned): rows_longk and gk (:231) refuse it, generic variant (:228); nsub 8
     Case("rlx_off8", SR(4, 1), "mk,nk->mn", dense(64, 4096, off=1), dense(16, 4096), framed(64, 16),
          tags=("rl-out:off8", "sr:gen_off8", "sr:nsub8")),
     Case("rlx_n49", SR(6, 4), "mk,nk->mn", dense(90, 4096), dense(49, 4096), framed(90, 49), alpha=-3.0, acc=1,
          tags=("rl-out:N=49", "sr:gk")),
     # ---------------------------------------------------------------- skinny_r (skinny.hip try_r)
-    # m / n contiguous, even extents and strides, aligned: the pair variant (skinny.hip:227 a_pair, b_pair); no swap; nsub 8
+    # m / n contiguous, even extents and strides, aligned: the pair variant (skinny.hip:211 a_pair, b_pair); no swap; nsub 8
     Case("sr_pair_noswap", SR(4, 2), "kp,kq->pq", dense(4160, 64), dense(4160, 32), framed(64, 32), alpha=0.5, acc=1,
          tags=("sr:pair", "sr:noswap", "sr:nsub8")),
-    # 6 N tiles > 2 M tiles: swap (:235); 6 x 2 = SKR_KSPLIT_TILES: still nsub 8 (:297)
+    # 6 N tiles > 2 M tiles: swap (:221); 6 x 2 = SKR_KSPLIT_TILES: still nsub 8 (:282)
     Case("sr_pair_swap", SR(6, 2), "kp,kq->pq", dense(5000, 32), dense(5000, 96), framed(32, 96), alpha=-3.0, acc=1,
          tags=("sr:pair", "sr:swap", "sr:nsub8")),
     # M = 300: three row tiles of 128, the last 44 rows; K = 4097 just above the limit, last chunk 1 long; nsub 1
     Case("sr_ragged_tile_k4097", SR(8, 2), "kp,kq->pq", dense(4097, 300), dense(4097, 20), framed(300, 20),
          tags=("sr:pair", "sr:ragged_tile", "sr:big>128", "sr:K4097", "sr:chunks_ragged", "sr:nsub1")),
-    # odd M: not pairable (:227), generic variant for both sides (:244), swap (4 N tiles > 3 M tiles)
+    # odd M: not pairable (:211), generic variant for both sides (:228), swap (4 N tiles > 3 M tiles)
     Case("sr_gen_odd_m", SR(4, 3), "kp,kq->pq", dense(6000, 33), dense(6000, 64), framed(33, 64),
          tags=("sr:gen_oddM", "sr:swap")),
-    # odd row stride of A (65): not pairable (:227), generic variant (:244)
+    # odd row stride of A (65): not pairable (:211), generic variant (:228)
     Case("sr_gen_odd_stride", SR(4, 1), "kp,kq->pq", dense(4200, 64, pad=1), dense(4200, 16), framed(64, 16),
          alpha=2.0, acc=1, tags=("sr:gen_oddstride",)),
     Case("sr_gen_odd_nmt7", SR(7, 1), "kp,kq->pq", dense(4500, 111), dense(4500, 9), framed(111, 9),
          tags=("sr:gen_oddM",)),
-    # (q, k) with k a slice of a longer axis: Ko = 9, Ki = 600 do not merge, rebase = 0 (:266); swap
+    # (q, k) with k a slice of a longer axis: Ko = 9, Ki = 600 do not merge, rebase = 0 (:249); swap
     Case("sr_ko_nonuniform", SR(4, 3), "qkp,qkm->pm", sliced((9, 700, 34), (0, 3, 0), (9, 600, 34)),
          sliced((9, 650, 50), (0, 10, 0), (9, 600, 50)), framed(34, 50), alpha=0.5, acc=1,
          tags=("sr:ko_nonuniform", "sr:pair", "sr:swap")),
-    # Ko = 4 x Ki = 1100 with uniform strides: ttsk_gemm merges them into one K before try_r, rebase = 1 (:266)
+    # Ko = 4 x Ki = 1100 with uniform strides: ttsk_gemm merges them into one K before try_r, rebase = 1 (:249)
     Case("sr_ko_uniform_desc", SR(3, 3), DESC, V((1, 48, 4, 1100), (0, 1, 1100 * 48, 48)),
          V((1, 4, 1100, 40), (0, 1100 * 40, 40, 1)), _c2(48, 40), via="desc", tags=("sr:rebase", "sr:pair")),
-    # k contiguous on both sides, big side 130 > 128 (two row tiles, the second 2 rows): gk variant (:248), swap
+    # k contiguous on both sides, big side 130 > 128 (two row tiles, the second 2 rows): gk variant (:231), swap
     Case("sr_gk_swap_big", SR(8, 3), "pk,qk->pq", dense(40, 6000), dense(130, 6000), framed(40, 130), alpha=0.5,
          acc=1, tags=("sr:gk", "sr:swap", "sr:ragged_tile", "sr:big>128", "sr:rebase")),
     # a transposed C (c_n != 1) through the scalar slab reduce, nmt 5

@@ -122,6 +122,21 @@ def test_one_call_with_a_different_rank_in_every_mode(tsa, monkeypatch):
     _close(got, want)
 
 
+def test_hmt_one_call_nearly_square_interior_unfolding(tsa, monkeypatch):
+    """An interior unfolding less than twice as tall as wide (3 x 3 rows, rank 8): each QR signs its own Q instead of the
+    sign reconstruction beside the chain (tt_orth.hip `beside`), same cores as the oracle."""
+    shape, r = (3, 3, 3, 3), (3, 8, 3)
+    rng = np.random.default_rng(13)
+    cores = orc.random_tt(shape, r, rng)                  # TT ranks = sketch ranks: every unfolding of full rank
+    rd = orc.random_tt_drm(shape, r, True, rng)
+    right = tsa.TensorTrainDRM(r, shape, True, seed=2, cores=[np.array(c) for c in rd.cores])
+    hits = _one_call_ran(tsa, monkeypatch)
+    got = [np.asarray(c) for c in tsa.hmt_sketch(tsa.TensorTrain(cores), r, drm=right).cores]
+    assert hits == ([True] if ONE_CALL else [])
+    want, _ = orc.general_sketch("tt", cores, None, rd, "hmt")
+    _close(got, want)
+
+
 @pytest.mark.parametrize("l,r", [(140, 150), (100, 200)])
 def test_one_call_ranks_beyond_128(tsa, monkeypatch, l, r):
     """two-block Cholesky factors, sign reconstruction with its working copy in global memory (129 .. 256 columns)"""
@@ -287,6 +302,7 @@ def test_assembly_matches_lstsq_for_ill_conditioned_omega(tsa, monkeypatch, dire
     ((30, 28, 26, 24, 22), 12, 8, 16, 9),        # more tensors than stream pairs: a second tensor queues behind the first on a pair
     ((64, 50, 50, 64), 33, 17, 40, 4),
     ((200, 200, 200), 60, 50, 64, 3),
+    ((12, 20, 20, 12), 10, 8, 10, 5),            # n_0 = 12 < 2 l: outside the fused batch's cover, the tensors as concurrent chains
 ])
 def test_orthogonal_sketch_batch_every_tensor_vs_oracle(tsa, shape, s_in, l, r, count):
     """every tensor of the batch entry by entry against the oracle (sketch_dispatch.py:160-193), and

@@ -626,7 +626,10 @@ def test_sketch_of_a_sum_in_one_call(tsa):
                                      ((64, 64, 64, 64), (100, 100, 100), (50, 50, 50), (100, 100, 100), 4),
                                      # TT ranks beyond 48: Psi of the sum in one launch, accumulators kept over the terms (stream_small_sum_kernel)
                                      ((70, 66, 68, 40), (52, 57, 49), (26, 28, 30), (54, 58, 70), 3),
-                                     ((40, 150, 30), (150, 60), (20, 40), (110, 45), 5)]:
+                                     ((40, 150, 30), (150, 60), (20, 40), (110, 45), 5),
+                                     # TT rank 50 > 48 beside a right rank of 5 (< 8) and rows l n = 240 (< 1024): outside
+                                     # stream_small_sum_kernel's cover, Psi per term and one ttsk_sum_slices (tt_fused.hip)
+                                     ((30, 40, 40, 30), (30, 50, 30), (6, 6, 6), (5, 5, 5), 4)]:
         ld, rd = orc.random_tt_drm(shape, lr, False, rng), orc.random_tt_drm(shape, rr, True, rng)
         if len(shape) == 5:
             ld.rank_min, ld.rank_max = (1, 0, 2, 0), (4, 6, 6, 5)

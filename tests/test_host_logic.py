@@ -337,3 +337,34 @@ def test_every_launch_goes_through_the_one_checked_helper():
     assert where(r"\bPerInit\b") == []
     assert where(r"static\s+bool\s+attr_done") == []
     assert where(r"\bTTSK_LAUNCH_CHECK\b") == []
+
+
+def _outside_lab_blocks(text):
+    """text with every line inside `#ifdef TTSK_LAB` ... (`#else` | `#endif`) blanked: what the shipped library compiles."""
+    import re
+    out, stack = [], []                  # one entry per open #if: True while inside the lab branch of a TTSK_LAB test
+    for line in text.splitlines():
+        d = line.strip()
+        if re.match(r"#\s*if", d):
+            stack.append(bool(re.match(r"#\s*(ifdef\s+TTSK_LAB\b|if\s+defined\s*\(?\s*TTSK_LAB\b)", d)))
+        elif re.match(r"#\s*(else|elif)", d) and stack:
+            stack[-1] = False
+        elif re.match(r"#\s*endif", d) and stack:
+            stack.pop()
+        out.append("" if any(stack) else line)
+    return "\n".join(out)
+
+
+def test_shipped_library_reads_no_ab_switches():
+    """The A/B switches of libttsk were folded to their defaults: outside the lab build (-DTTSK_LAB) the only environment
+    variables csrc/ reads are TTSK_SINGLE_STREAM (bench.py's roofline pass) and TTSK_GEMM_TRACE (prints only)."""
+    import glob
+    import re
+    csrc = os.path.join(os.path.dirname(nat.__file__), "csrc")
+    calls, named = [], []
+    for p in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")):
+        text = _outside_lab_blocks(open(p).read())
+        calls += re.findall(r"\bgetenv\s*\(", text)
+        named += re.findall(r"\bgetenv\s*\(\s*\"(\w+)\"\s*\)", text)
+    assert len(named) == len(calls) >= 2          # every read names its variable literally
+    assert set(named) == {"TTSK_SINGLE_STREAM", "TTSK_GEMM_TRACE"}, sorted(set(named))

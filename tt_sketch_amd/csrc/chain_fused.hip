@@ -41,17 +41,9 @@ static void tile_split(int r, int &nf, int &str)
     else { nf += 1; str = 0; }
 }
 
-// TTSK_CHAIN_FUSED: 0 = never, 1 = when it pays (default), 2 = whenever the shape is covered (tests)
-static int cf_mode()
-{
-    static int m = [] { const char *e = getenv("TTSK_CHAIN_FUSED"); return e ? atoi(e) : 1; }();
-    return m;
-}
-
 int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force)
 {
-    const int mode = force ? 2 : cf_mode();
-    if (!mode || c.nb < 1 || c.nb > SK_MAXB) return 0;
+    if (c.nb < 1 || c.nb > SK_MAXB) return 0;
     if (c.J < 1 || c.J > 112 || c.K1 < 1 || c.K1 > 128 || c.A < 4 || c.A2 < 4 || c.n < 1) return 0;
     if ((c.A2 & 1) || ((uintptr_t)c.E & 15)) return 0;                 // 16-byte units of E rows
     int nq, sq, nn, sn;
@@ -71,7 +63,7 @@ int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool for
     const int KB1 = unr == 25 ? pad25 : pad5, KB2 = nq * 4 + sq;       // k-blocks of the two phases
     // the loader brings A x A2 doubles per slice while phase A runs K1 deep: a short phase A cannot hide it, and
     // there is little T to keep on chip anyway (the two-launch form is then the faster one: measured on C5)
-    if (mode == 1 && 2 * c.K1 < c.A) return 0;
+    if (!force && 2 * c.K1 < c.A) return 0;
     a.AP = 16 * nq + 4 * sq;
     a.A2P = c.A2;
     if (a.AP < 4 * KB2) return 0;

@@ -20,13 +20,6 @@ static int cs_num_cu()
     return n;
 }
 
-// TTSK_CHAIN_SUM: 0 = never, 1 = default
-static int cs_mode()
-{
-    static int m = [] { const char *e = getenv("TTSK_CHAIN_SUM"); return e ? atoi(e) : 1; }();
-    return m;
-}
-
 // ---- the wave table of phase B -----------------------------------------------------------------------------------
 // The (NRT x NNF) full tiles are cut into one or two row bands, each band into rectangles of the bodies the kernel
 // instantiates; the strip column (NS 4-wide strips, all row tiles) is a piece of its own or rides on a (1, 1) / (1, 3)
@@ -157,7 +150,7 @@ static bool wave_table_search(int NRT, int NNF, int NS, ChainSumRole *role)
 int chain_sum_try(const ChainSumArgs &cc, int stream, hipStream_t st, bool force)
 {
     const ChainStepArgs &c = cc.s;
-    if ((!cs_mode() && !force) || c.nb < 1 || c.nb > SK_MAXB) return 0;
+    if (c.nb < 1 || c.nb > SK_MAXB) return 0;
     constexpr int JS = 5, KB1 = 5;                      // the instantiated structure: J, K1 <= 20
     if (c.J < 1 || c.J > 4 * JS || c.K1 < 1 || c.K1 > 4 * KB1 || c.A < 4 || c.A > 128 || c.A2 < 4 || c.A2 > 128 || c.n < 1) return 0;
     if ((c.A2 & 1) || ((uintptr_t)c.E & 15)) return 0;                 // 16-byte units of E rows
@@ -227,9 +220,7 @@ int chain_sum_try(const ChainSumArgs &cc, int stream, hipStream_t st, bool force
     // any price: (i) a workgroup gets at least ~32 k cycles of matrix-pipe time (one and a half times its fixed cost), (ii) a quarter of
     // the CUs is left to the kernel of the other chain, which the sketch drivers always have in flight beside this one.
     // (C5: 24 ranges of 5-6 slices for the right step and 16 of 8 for the left one instead of 32 of 4 each: 0.41 -> 0.39 ms
-    // per sketch with two in flight, a single call unchanged.)  TTSK_CS_NR / TTSK_CS_NR_LEFT (lab): the count itself.
-    static const int nr_env = [] { const char *e = getenv("TTSK_CS_NR"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
-    static const int nr_left_env = [] { const char *e = getenv("TTSK_CS_NR_LEFT"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
+    // per sketch with two in flight, a single call unchanged.)
     int nr = cus / a.ngroups;
     {
         const int NRT = (tpw * JP + 15) / 16;
@@ -237,8 +228,6 @@ int chain_sum_try(const ChainSumArgs &cc, int stream, hipStream_t st, bool force
         const int min_slices = (int)(32000.0 / slice_cyc) + 1;
         nr = std::min(std::max(1, 3 * cus / 4 / a.ngroups), std::max(1, c.n / min_slices));
     }
-    if (a.T && nr_left_env) nr = nr_left_env;
-    else if (!a.T && nr_env) nr = nr_env;
     if (nr >= 8) nr = nr / 8 * 8;
     if (nr < 1) nr = 1;
     if (nr > c.n) nr = c.n;

@@ -49,13 +49,6 @@ static void cw_tile_split(int r, int &nf, int &str)
     else { nf += 1; str = 0; }
 }
 
-// TTSK_CHAIN_WIDE: 0 = never, 1 = when it pays (default), 2 = whenever the shape is covered
-static int cw_mode()
-{
-    static int m = [] { const char *e = getenv("TTSK_CHAIN_WIDE"); return e ? atoi(e) : 1; }();
-    return m;
-}
-
 // Row tiles -> waves.  Wave w sits on SIMD w & 3 (two waves per SIMD); the tiles are dealt so that the SIMDs
 // carry equal shares, SIMD 3 the lightest one: its second wave is the loader.  Returns false if the rows do not fit.
 // tpw > 1: `tpw` tensors per workgroup, each with ceil(NT / 2) (or NT) waves of its own, in order.
@@ -98,8 +91,7 @@ static bool cw_wave_table(int NT, bool mt2_ok, int tpw, ChainWide &a, bool &uses
 
 int chain_wide_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force)
 {
-    const int mode = force ? 2 : cw_mode();
-    if (!mode || c.nb < 1 || c.nb > SK_MAXB) return 0;
+    if (c.nb < 1 || c.nb > SK_MAXB) return 0;
     if (c.J < 1 || c.K1 < 1 || c.A < 1 || c.A2 < 1 || c.n < 1) return 0;
     if (((uintptr_t)c.E & 7) || c.x_j < 0 || c.x_k < 0 || c.x_c < 0 || c.w_c < c.A) return 0;
     int nn, sn;
@@ -155,8 +147,8 @@ int chain_wide_try(const ChainStepArgs &c, int stream, hipStream_t st, bool forc
     if (ci < 0) return 0;
     // TT rank much smaller than the DRM rank (C5: 20 against 50 / 100): the two-launch form merges the rows of ALL tensors
     // of the batch into one long-K product (no 20 -> 32 row padding) and wins -- measured per right step: 81 us against 101 us
-    // with seven tensors per workgroup here (128 us with one); TTSK_CHAIN_WIDE=2 takes this kernel anyway
-    if (mode == 1 && 2 * c.K1 < c.A) return 0;
+    // with seven tensors per workgroup here (128 us with one); `force` (ttsk_chain_step_wide) takes this kernel anyway
+    if (!force && 2 * c.K1 < c.A) return 0;
     if (!cw_wave_table(NT, CW_NQ[ci] <= 3 && out_mt2, tpw, a, uses_mt2)) return 0;
     a.tpw = tpw;
     a.nac = nac;

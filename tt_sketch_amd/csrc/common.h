@@ -19,8 +19,6 @@ void *scratch(int stream, int slot, size_t bytes);
 // another device gets fresh ones.  nullptr on failure.
 enum { PA_PINV_HOST = 0, PA_PINV_DEV, PA_DEFERRED, PA_PINV_BATCH_VD, PA_DEFERRED_PINNED, PA_SLOTS };
 void *persistent_alloc(int key, size_t bytes, bool host, bool zero);
-// bumped by ttsk_shutdown: per-function set-up on the device (symbols) is repeated after a re-init, maybe on another device
-int init_generation();
 
 #define TTSK_HIP(call)                                                          \
     do {                                                                        \
@@ -52,8 +50,8 @@ struct LaunchAt {
     LaunchAt(hipStream_t s, const char *f = __builtin_FILE(), int l = __builtin_LINE()) : st(s), file(f), line(l) {}
 };
 
-// runtime.hip: raises kern's dynamic-LDS limit to the device's LDS per workgroup minus its static LDS, once per init
-// generation; lock-free once raised.
+// runtime.hip: raises kern's dynamic-LDS limit to the device's LDS per workgroup minus its static LDS, once per init;
+// lock-free once raised.
 int raise_lds_limit(const void *kern, const char *file, int line);
 
 // Every kernel launch of the library goes through here: the dynamic-LDS limit (lds > 0), the launch, its check.

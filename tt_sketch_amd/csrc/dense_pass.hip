@@ -384,8 +384,7 @@ extern "C" int ttsk_dense_first_pass(const double *X, int64_t n0, int64_t Q, int
     using namespace ttsk;
     TTSK_ARG(X && C && P && Z && U, "ttsk_dense_first_pass: NULL operand");
     TTSK_ARG(n0 > 0 && Q > 0 && T > 0 && ll > 0 && r > 0, "ttsk_dense_first_pass: empty extent");
-    static const int on = [] { const char *e = getenv("TTSK_DENSE_ONE_PASS"); return e ? atoi(e) : 1; }();
-    if (!on || (n0 & 31) || n0 > 64 * 64 || (T & 15) || (Q & 7) || ll > 32 || r > 64 || Q * T >= (1ll << 27) ||
+    if ((n0 & 31) || n0 > 64 * 64 || (T & 15) || (Q & 7) || ll > 32 || r > 64 || Q * T >= (1ll << 27) ||
         (((uintptr_t)X | (uintptr_t)P | (uintptr_t)Z) & 15)) {
         set_error("ttsk_dense_first_pass: shape outside the kernel's cover (first mode a multiple of 32, last mode a multiple "
                   "of 16, middle extent a multiple of 8, left rank <= 32, right rank <= 64)");
@@ -399,8 +398,7 @@ extern "C" int ttsk_dense_first_pass(const double *X, int64_t n0, int64_t Q, int
     // of b, the matrix work stays proportional to the ranks, and the tile is read twice, the kinds of a (t range, q range) one
     // dispatch round apart on one XCD.  Otherwise (first mode a multiple of 32 only): blocks of 32 with wider accumulators.
     // just beyond 20 / 40 (r <= 44, ll <= 24): one more strip of either still fits one kind of workgroup (11 spilled registers, outside the step loop)
-    static const int one_kind_on = [] { const char *e = getenv("TTSK_DP_ONE_KIND"); return e ? atoi(e) : 1; }();
-    const bool one_kind = one_kind_on && !(n0 & 63) && (r > 40 || ll > 20) && r <= 44 && ll <= 24;
+    const bool one_kind = !(n0 & 63) && (r > 40 || ll > 20) && r <= 44 && ll <= 24;
     const bool split = !one_kind && !(n0 & 63) && (r > 40 || ll > 20);
     const int p_half = split ? (int)((r + 1) / 2 + 3) / 4 * 4 : 0, z_half = split ? (int)((ll + 1) / 2 + 3) / 4 * 4 : 0;
     const int ushape = split ? (p_half <= 24 ? 3 : 4) : r <= 40 ? 0 : r <= 48 ? 1 : 2;
@@ -412,8 +410,6 @@ extern "C" int ttsk_dense_first_pass(const double *X, int64_t n0, int64_t Q, int
     // q ranges: about 256 workgroups for one block of b, about 1024 over all blocks otherwise (several rounds over the CUs even
     // out the ranges); a multiple of 8, and not more than there are tiles
     int64_t nqc = 8 * std::max<int64_t>(1, (nbb == 1 ? 32 : (128 + nbb * nt / 2) / (nbb * nt)) / (nbb == 1 ? nt : 1));
-    static const int nqc_env = [] { const char *e = getenv("TTSK_DP_NQC"); return e ? atoi(e) : 0; }();   // A/B runs
-    if (nqc_env > 0 && nbb > 1) nqc = 8 * cdiv(nqc_env, 8);
     nqc = std::min<int64_t>(nqc, 8 * cdiv(Q / 8, 8));          // at least one tile for most chunks
     const int64_t grid1 = (int64_t)nbb * nt * nqc, grid = grid1 * kinds;
     const int64_t sl64 = (4 * TP + SP) * 64;

@@ -147,8 +147,7 @@ int rp_num_cu()
 int rows_longk_try(const double *S, int64_t rows, int64_t s_row, const double *B, int N, int64_t b_row, int64_t K, double *C,
                    int64_t c_row, double alpha, int accumulate, int stream, hipStream_t st)
 {
-    static const int on = [] { const char *e = getenv("TTSK_ROWS_LONGK"); return e ? atoi(e) : 1; }();
-    if (!on || rows < 1 || N < 1 || N > RP_BROWS || K < 4096 || (K & 63) || (s_row & 1) || (b_row & 1) || s_row < K || b_row < K) return 0;
+    if (rows < 1 || N < 1 || N > RP_BROWS || K < 4096 || (K & 63) || (s_row & 1) || (b_row & 1) || s_row < K || b_row < K) return 0;
     if (((uintptr_t)S | (uintptr_t)B) & 15) return 0;
     const int64_t nrb = (rows + 63) / 64;
     if (nrb > (1 << 20)) return 0;

@@ -170,14 +170,10 @@ struct GemmPlan {
 
 static GemmPlan plan_gemm(int64_t M, int64_t N)
 {
-    // Tiles per wave in the skinny families are capped (default 4): smaller workgroups leave room
+    // Tiles per wave in the skinny families are capped at 4: smaller workgroups leave room
     // for 3-4 of them per CU, and co-resident workgroups are what hides the load latency of these
     // short-K products (one wave per SIMD cannot overlap its own loads with its MFMAs).
-    static int cap = [] {
-        const char *e = getenv("TTSK_MAX_TILES");
-        int v = e ? atoi(e) : 4;
-        return v < 1 ? 1 : (v > 8 ? 8 : v);
-    }();
+    constexpr int cap = 4;
     GemmPlan p;
     auto split = [&](int64_t X) {            // tiles per wave so that rows*tiles covers ceil(X/16) evenly
         const int need = (int)cdiv(X, 16);
@@ -258,12 +254,11 @@ int ttsk_gemm(const ttsk_gemm_desc *dp, const double *A, const double *B, double
         // a long contraction batched over an index that only one operand carries (the per-slice right products of
         // dense_sketch.py: P^T X_b for every slice b of the tensor): up to SK_MAXB problems per launch of the long-K
         // chain kernel instead of the generic tiles (C2's Psi_0 pass: 2.76 -> 2.59 ms)
-        static int on = [] { const char *e = getenv("TTSK_GEMM_BATCH_LONGK"); return e ? atoi(e) : 1; }();
         ttsk_gemm_desc n = d;
         n.batch = 1; n.a_b = n.b_b = n.c_b = 0;
         if (n.Ki == 1) { n.Ki = n.Ko; n.Ko = 1; n.a_ki = n.a_ko; n.b_ki = n.b_ko; }
         else if (n.Ko > 1 && n.a_ko == n.Ki * n.a_ki && n.b_ko == n.Ki * n.b_ki) { n.Ki *= n.Ko; n.Ko = 1; }
-        bool done = on != 0;
+        bool done = true;
         for (int64_t b0 = 0; b0 < d.batch && done; b0 += SK_MAXB) {
             const int cnt = (int)(d.batch - b0 < SK_MAXB ? d.batch - b0 : SK_MAXB);
             const double *Ap[SK_MAXB], *Bp[SK_MAXB];

@@ -399,7 +399,7 @@ struct GemmLaunch {
     ttsk_gemm_desc d;
     const double *A, *B, *ks;
     double *C, *partial;
-    int family, tiles;      // family 0: 2x2 waves of 2x2 tiles; 1: 1x4 waves of tiles x 1; 2: 4x1 waves of 1 x tiles
+    int family, tiles;      // tiles: 1..4; family 0: 2x2 waves of 2x2 tiles; 1: 1x4 waves of tiles x 1; 2: 4x1 waves of 1 x tiles
     int splits, avec, bvec, fast_ok;
     int64_t kchunk;
     int bm, bn;
@@ -426,22 +426,14 @@ int launch_gemm_layout(const GemmLaunch &g, hipStream_t st)
         case 1: return launch_one<1, 4, 1, 1, AKF, BKF>(g, st);
         case 2: return launch_one<1, 4, 2, 1, AKF, BKF>(g, st);
         case 3: return launch_one<1, 4, 3, 1, AKF, BKF>(g, st);
-        case 4: return launch_one<1, 4, 4, 1, AKF, BKF>(g, st);
-        case 5: return launch_one<1, 4, 5, 1, AKF, BKF>(g, st);
-        case 6: return launch_one<1, 4, 6, 1, AKF, BKF>(g, st);
-        case 7: return launch_one<1, 4, 7, 1, AKF, BKF>(g, st);
-        default: return launch_one<1, 4, 8, 1, AKF, BKF>(g, st);
+        default: return launch_one<1, 4, 4, 1, AKF, BKF>(g, st);
         }
     }
     switch (g.tiles) {
     case 1: return launch_one<4, 1, 1, 1, AKF, BKF>(g, st);
     case 2: return launch_one<4, 1, 1, 2, AKF, BKF>(g, st);
     case 3: return launch_one<4, 1, 1, 3, AKF, BKF>(g, st);
-    case 4: return launch_one<4, 1, 1, 4, AKF, BKF>(g, st);
-    case 5: return launch_one<4, 1, 1, 5, AKF, BKF>(g, st);
-    case 6: return launch_one<4, 1, 1, 6, AKF, BKF>(g, st);
-    case 7: return launch_one<4, 1, 1, 7, AKF, BKF>(g, st);
-    default: return launch_one<4, 1, 1, 8, AKF, BKF>(g, st);
+    default: return launch_one<4, 1, 1, 4, AKF, BKF>(g, st);
     }
 }
 

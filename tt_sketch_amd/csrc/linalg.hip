@@ -152,8 +152,6 @@ __device__ void jac_qr_rt(double *Wc, const int mW, const int nW, const int tid,
     __syncthreads();
 }
 
-__constant__ int jac_precond_on = 1;     // TTSK_JACOBI_PRECOND=0 clears it (host: jacobi_lds_mode)
-
 // ---------------------------------------------------------------- Jacobi SVD pinv
 // W: mW x nW (mW >= nW) column-major in Wc (column j at Wc + j*mW), V: nW x nW column-major.
 // On exit P[i*ldp_i + k*ldp_k] = sum_{j kept} Wc_j[i] * V_j[k] / sigma_j^2.
@@ -203,7 +201,7 @@ __global__ __launch_bounds__(1024) void jacobi_pinv_kernel(const double *__restr
     // rank-15 100 x 50 sketch -- and the columns are nW instead of mW long).  The right singular vectors are then
     // the normalised columns of the converged matrix, and W V is recomputed from the input.  1.1 -> 0.54 ms for that
     // sketch; the factor mode (svd_US) keeps the plain iteration with its high relative accuracy.
-    const bool precond = svd_US == nullptr && jac_precond_on;
+    const bool precond = svd_US == nullptr;
     __shared__ double s_beta;
     if (precond) jac_qr_rt(Wc, mW, nW, tid, blockDim.x, &s_beta);
     const int rows = precond ? nW : mW;          // length of the columns the sweeps rotate (column stride stays mW)
@@ -589,7 +587,7 @@ __device__ __forceinline__ void chol_lds(double *A, double *xd, const int n, con
     }
 }
 
-// Launched with 256 threads, or with 1024 (n <= 64, chol_threads()): the extra twelve waves take part in the recurrence
+// Launched with 256 threads, or with 1024 (n <= 128, chol_threads()): the extra twelve waves take part in the recurrence
 // only -- one row per 16-lane group instead of four, twelve more waves to hide the LDS round trips behind -- and leave.
 __global__ __launch_bounds__(1024) void chol_inv_kernel(const double *__restrict__ G, int n, double *__restrict__ Rinv,
                                                        double *__restrict__ Ginv, int *__restrict__ status,
@@ -865,8 +863,7 @@ static int small_gemm(int64_t M, int64_t N, int64_t K, const double *A, int64_t 
 
 static unsigned chol_threads(int n)
 {
-    static const int wide = [] { const char *e = getenv("TTSK_CHOL_WIDE"); return e ? atoi(e) : 1; }();
-    return (wide && n <= (wide == 1 ? 128 : 64)) ? 1024u : 256u;
+    return n <= 128 ? 1024u : 256u;
 }
 
 static int launch_chol(const double *G, int n, double *Rinv, double *Ginv, int *status, double cond_tol, hipStream_t st,
@@ -932,12 +929,6 @@ static int chol_inv_any(const double *G, int n, double *Rinv, double *Ginv, int 
     if ((rc = gemm_ex(n1, n2, n1, X11, n1, 1, Y, n2, 1, Rinv + n1, n, -1.0, 0, stream))) return rc;           // X12 = -X11 Y
     if (Ginv && (rc = gemm_ex(n, n, n, Rinv, n, 1, Rinv, 1, n, Ginv, n, 1.0, 0, stream))) return rc;          // G^-1 = X X^T
     return TTSK_OK;
-}
-
-bool fast_solves()
-{
-    static int v = [] { const char *e = getenv("TTSK_FAST_SOLVES"); return e ? atoi(e) : 1; }();
-    return v != 0;
 }
 
 // pinv(Omega) through the normal equations; 1 = done, 0 = rejected (caller runs the Jacobi SVD)
@@ -1054,8 +1045,7 @@ int qr_cholesky(double *A, int64_t m, int64_t n64, int stream, hipStream_t st, d
     if (!ws) return TTSK_ERR_HIP;
     double *Q1 = ws, *G = Q1 + (size_t)m * n, *R1 = G + n * n, *R2 = R1 + n * n, *Qtop = R2 + n * n;
     int *status = (int *)(Qtop + n * n);
-    static const int small_on = [] { const char *e = getenv("TTSK_CHOLQR2_LDS"); return e ? atoi(e) : 1; }();
-    if (unsigned_q && sticky && small_on) {
+    if (unsigned_q && sticky) {
         // small enough for one workgroup's LDS: the whole CholeskyQR2 in one launch
         const int fr = launch_cholqr2_lds(A, m, n, status, 1e-6, sticky, st);
         if (fr) return fr;
@@ -1070,14 +1060,12 @@ int qr_cholesky(double *A, int64_t m, int64_t n64, int stream, hipStream_t st, d
         if ((rc = chol_inv_any(G, n, R2, nullptr, status + 1, 0.5, stream, st, cws, sticky))) return rc;    // must be ~identity
     } else if (unsigned_q) {
         // R with positive diagonal only: the caller reconstructs the signs beside the critical path (qr_signs)
-        static const int chol_expand = [] { const char *e = getenv("TTSK_CHOL_EXPAND"); return e ? atoi(e) : 1; }();
         if ((rc = launch(chol_inv_kernel, dim3(1), dim3(256), (size_t)(n * (n + 1) + n) * 8, st, G, n, R2, (double *)nullptr,
-                         status + 1, 0.5, sticky, (double *)nullptr, (const double *)nullptr, 0, chol_expand ? 2 : 0))) return rc;
+                         status + 1, 0.5, sticky, (double *)nullptr, (const double *)nullptr, 0, 2))) return rc;
     } else if (n <= CHOL_SIGN_MAX) {
         // second factorisation (G ~ identity), top block of Q and the sign reconstruction in ONE kernel
-        static const int chol_expand = [] { const char *e = getenv("TTSK_CHOL_EXPAND"); return e ? atoi(e) : 1; }();
         if ((rc = launch(chol_inv_kernel, dim3(1), dim3(256), (size_t)(3 * n * (n + 1) + 2 * n) * 8, st, G, n, R2, (double *)nullptr,
-                         status + 1, 0.5, sticky, (double *)nullptr, (const double *)Q1, m == n64 ? 1 : 0, chol_expand))) return rc;
+                         status + 1, 0.5, sticky, (double *)nullptr, (const double *)Q1, m == n64 ? 1 : 0, 1))) return rc;
     } else {
     if ((rc = chol_inv_any(G, n, R2, nullptr, status + 1, 0.5, stream, st, cws, sticky))) return rc;    // must be ~identity
     if ((rc = small_gemm(n, n, n, Q1, n, 1, R2, n, 1, Qtop, stream))) return rc;         // top block of Q
@@ -1395,9 +1383,8 @@ int qr_cholesky_batch(int count, double *const *A, int64_t m, int n, int stream,
     if ((rc = launch_chol(G, n, R1, nullptr, status, 1e-6, st, sticky, nullptr, count))) return rc;           // kappa(A) up to ~1e6
     if ((rc = prod(tri, cA, cR1, pQ1))) return rc;                                                            // Q1 = A R1^-1
     if ((rc = prod(gram, cQ1, cQ1, pG))) return rc;                                                           // Q1^T Q1 ~ identity
-    static const int chol_expand = [] { const char *e = getenv("TTSK_CHOL_EXPAND"); return e ? atoi(e) : 1; }();
     if ((rc = launch(chol_inv_kernel, dim3((unsigned)count), dim3(256), (size_t)(n * (n + 1) + n) * 8, st, (const double *)G, n, R2, (double *)nullptr,
-                     status + count, 0.5, sticky, (double *)nullptr, (const double *)nullptr, 0, chol_expand ? 2 : 0))) return rc;
+                     status + count, 0.5, sticky, (double *)nullptr, (const double *)nullptr, 0, 2))) return rc;
     if ((rc = prod(tri, cQ1, cR2, A))) return rc;                                                             // Q = Q1 R2^-1
     return 1;
 }
@@ -1440,28 +1427,13 @@ using namespace ttsk;
 // where the Jacobi working set lives: 2 = W and V in LDS, 1 = W only, 0 = global scratch
 static int jacobi_lds_mode(int64_t mW, int64_t nW, size_t *bytes)
 {
-    static const int off = getenv("TTSK_JACOBI_GLOBAL") ? 1 : 0;
     const size_t cap = 160 * 1024 - 256;            // 160 KB per CU minus the kernel's few static bytes
     const size_t w = (size_t)mW * nW * 8, v = (size_t)nW * nW * 8;
     const size_t small = ((size_t)nW + (nW + 1) / 2) * 8;          // sigma^2 and the sort order
-    int mode = 0;
+    if (small + w + v <= cap) { *bytes = small + w + v; return 2; }
+    if (small + w <= cap) { *bytes = small + w; return 1; }
     *bytes = small;
-    if (!off) {
-        if (small + w + v <= cap) { mode = 2; *bytes = small + w + v; }
-        else if (small + w <= cap) { mode = 1; *bytes = small + w; }
-    }
-    static int precond_gen = -1;                    // device state: set again after a re-init
-    if (precond_gen != init_generation()) {
-        if (const char *e = getenv("TTSK_JACOBI_PRECOND")) {
-            const int v = atoi(e);
-            if (hipMemcpyToSymbol(HIP_SYMBOL(jac_precond_on), &v, sizeof(int)) != hipSuccess) {
-                set_error("jacobi: cannot set TTSK_JACOBI_PRECOND on the device");
-                return -1;
-            }
-        }
-        precond_gen = init_generation();
-    }
-    return mode;
+    return 0;
 }
 
 extern "C" {
@@ -1484,7 +1456,7 @@ int ttsk_pinv_begin(const double *dev_omega, int64_t l, int64_t r, double rcond,
     TTSK_ARG(l >= 1 && r >= 1, "ttsk_pinv: bad shape (%lld, %lld)", (long long)l, (long long)r);
     TTSK_ARG((r >= l ? l : r) <= 1024, "ttsk_pinv: min(l, r) = %lld > 1024 unsupported", (long long)(r >= l ? l : r));
     g_pinv_began[stream] = 0;
-    if (fast_solves() && pinv_rcond(l, r, rcond) <= 1e-4) {
+    if (pinv_rcond(l, r, rcond) <= 1e-4) {
         const int fr = pinv_cholesky_begin(dev_omega, l, r, dev_pinv, stream, st);
         if (fr < 0) return fr;
         g_pinv_began[stream] = fr;
@@ -1524,7 +1496,6 @@ int ttsk_pinv_end(const double *dev_omega, int64_t l, int64_t r, double rcond, d
     int *drank = (int *)(ws + mW * nW + nW * nW);
     size_t jl = 0;
     const int jm = jacobi_lds_mode(mW, nW, &jl);
-    if (jm < 0) return TTSK_ERR_HIP;
     auto kern = jm == 2 ? jacobi_pinv_kernel<2> : (jm == 1 ? jacobi_pinv_kernel<1> : jacobi_pinv_kernel<0>);
     if (int rc = launch(kern, dim3(1), dim3(1024), jl, st, dev_omega, l, r, transposed, ws,
                         ws + mW * nW, rcond, dev_pinv, host_rank ? drank : (int *)nullptr, (double *)nullptr,
@@ -1539,7 +1510,7 @@ int ttsk_pinv_end(const double *dev_omega, int64_t l, int64_t r, double rcond, d
 // The pseudo-inverses of `count` matrices of ONE shape with ttsk_pinv's contract (gelsd's truncation on rejection), every
 // stage of the fast attempt ONE batched launch and the Jacobi kernels queued behind it, each with its own matrix's verdict
 // as predicate: 3 + count launches instead of 6 count (assemble_sketched_tt: the launches are what its d - 1 independent
-// pseudo-inverses cost).  No read-back.  TTSK_ERR_UNSUPPORTED: min(l, r) > 128, count > 32, TTSK_FAST_SOLVES=0.
+// pseudo-inverses cost).  No read-back.  TTSK_ERR_UNSUPPORTED: min(l, r) > 128, count > 32.
 int ttsk_pinv_batch(int count, const double *const *dev_omegas, int64_t l, int64_t r, double *const *dev_pinvs, int stream)
 {
     TTSK_STREAM(st, stream);
@@ -1547,7 +1518,7 @@ int ttsk_pinv_batch(int count, const double *const *dev_omegas, int64_t l, int64
     const int n = (int)(l < r ? l : r);
     // verdicts outside the scratch arena (the Jacobi kernel works there)
     int *vd = (int *)persistent_alloc(PA_PINV_BATCH_VD, TTSK_NUM_STREAMS * SK_MAXB * sizeof(int), false, false);
-    if (!fast_solves() || !vd || n > CHOL_ONE || pinv_rcond(l, r, -1.0) > 1e-4) {
+    if (!vd || n > CHOL_ONE || pinv_rcond(l, r, -1.0) > 1e-4) {
         set_error("ttsk_pinv_batch: (%lld x %lld) is outside the batched fast path", (long long)l, (long long)r);
         return TTSK_ERR_UNSUPPORTED;
     }
@@ -1587,7 +1558,6 @@ int ttsk_pinv_batch(int count, const double *const *dev_omegas, int64_t l, int64
     // rejected ones: the Jacobi kernel on the untouched input (it leaves at once where the attempt was accepted)
     size_t jl = 0;
     const int jm = jacobi_lds_mode(mW, nW, &jl);
-    if (jm < 0) return TTSK_ERR_HIP;
     auto kern = jm == 2 ? jacobi_pinv_kernel<2> : (jm == 1 ? jacobi_pinv_kernel<1> : jacobi_pinv_kernel<0>);
     const double rcond = pinv_rcond(l, r, -1.0);
     // equally spaced inputs and outputs, matrices that live in LDS (no shared global scratch): ONE launch, a workgroup per matrix
@@ -1620,7 +1590,7 @@ int chol_inv_batch(const double *G, int n, double *Rinv, double *Ginv, int *stat
 
 bool pinv_batch_fast(int64_t l, int64_t r)
 {
-    return fast_solves() && (l < r ? l : r) <= CHOL_ONE && pinv_rcond(l, r, -1.0) <= 1e-4;
+    return (l < r ? l : r) <= CHOL_ONE && pinv_rcond(l, r, -1.0) <= 1e-4;
 }
 
 // the Jacobi kernel behind the batched attempt, ONE launch, workgroup b on omega + b * os -> P + b * ps, predicated on
@@ -1632,7 +1602,6 @@ int jacobi_pinv_spaced(int count, const double *omega, int64_t os, int64_t l, in
     const int64_t mW = transposed ? r : l, nW = transposed ? l : r;
     size_t jl = 0;
     const int jm = jacobi_lds_mode(mW, nW, &jl);
-    if (jm < 0) return TTSK_ERR_HIP;
     if (jm != 2) return 0;
     if (int rc = launch(jacobi_pinv_kernel<2>, dim3((unsigned)count), dim3(1024), jl, st, omega, l, r, transposed, (double *)nullptr,
                         (double *)nullptr, pinv_rcond(l, r, -1.0), P, (int *)nullptr, (double *)nullptr, (double *)nullptr,
@@ -1657,7 +1626,7 @@ int ttsk_pinv(const double *dev_omega, int64_t l, int64_t r, double rcond, doubl
 // CholeskyQR2.  The verdicts of the factorisations (Omega not of full rank / too ill conditioned, Psi_mat Omega^+ too
 // ill conditioned) are NOT waited for: a rejection sets the stream's deferred flag and the numbers in Q are then
 // meaningless; the caller reads the flag once at the end (ttsk_deferred_status) and repeats the sketch on the robust
-// kernels (ttsk_pinv / ttsk_qr_thin).  TTSK_ERR_UNSUPPORTED: ranks beyond 256 or TTSK_FAST_SOLVES=0.
+// kernels (ttsk_pinv / ttsk_qr_thin).  TTSK_ERR_UNSUPPORTED: ranks beyond 256.
 int ttsk_orth_step(const double *dev_psi, int64_t m, int64_t r2, const double *dev_omega, int64_t l, double *dev_q, int stream)
 {
     TTSK_STREAM(st, stream);
@@ -1666,7 +1635,7 @@ int ttsk_orth_step(const double *dev_psi, int64_t m, int64_t r2, const double *d
     TTSK_ARG(k >= 1 && m >= k, "ttsk_orth_step: cannot orthogonalise a %lld x %lld unfolding", (long long)m, (long long)k);
     int *sticky = deferred_flag(stream);
     const int64_t nmin = dev_omega ? (l < r2 ? l : r2) : 0;
-    if (!fast_solves() || !sticky || k > CHOL_MAX || nmin > CHOL_MAX || (dev_omega && pinv_rcond(l, r2, -1.0) > 1e-4)) {
+    if (!sticky || k > CHOL_MAX || nmin > CHOL_MAX || (dev_omega && pinv_rcond(l, r2, -1.0) > 1e-4)) {
         set_error("ttsk_orth_step: (%lld x %lld, rank %lld) is outside the fast path", (long long)m, (long long)r2, (long long)k);
         return TTSK_ERR_UNSUPPORTED;
     }
@@ -1697,7 +1666,7 @@ int ttsk_pinv_batch_deferred(int count, const double *const *dev_omegas, int64_t
     TTSK_ARG(count >= 1 && count <= SK_MAXB && dev_omegas && dev_pinvs && l >= 1 && r >= 1, "ttsk_pinv_batch_deferred: bad argument");
     int *sticky = deferred_flag(stream);
     const int n = (int)(l < r ? l : r);
-    if (!fast_solves() || !sticky || n > CHOL_ONE || pinv_rcond(l, r, -1.0) > 1e-4) {
+    if (!sticky || n > CHOL_ONE || pinv_rcond(l, r, -1.0) > 1e-4) {
         set_error("ttsk_pinv_batch_deferred: (%lld x %lld) is outside the batched fast path", (long long)l, (long long)r);
         return TTSK_ERR_UNSUPPORTED;
     }
@@ -1750,7 +1719,7 @@ int ttsk_orth_step_pinv(const double *dev_psi, int64_t m, int64_t r2, const doub
     TTSK_ARG(dev_psi && dev_pinv && dev_q && m >= 1 && r2 >= 1 && l >= 1, "ttsk_orth_step_pinv: bad argument");
     TTSK_ARG(m >= l, "ttsk_orth_step_pinv: cannot orthogonalise a %lld x %lld unfolding", (long long)m, (long long)l);
     int *sticky = deferred_flag(stream);
-    if (!fast_solves() || !sticky || l > CHOL_MAX) {
+    if (!sticky || l > CHOL_MAX) {
         set_error("ttsk_orth_step_pinv: rank %lld is outside the fast path", (long long)l);
         return TTSK_ERR_UNSUPPORTED;
     }
@@ -1790,15 +1759,12 @@ int ttsk_svd_small(const double *dev_A, int64_t m, int64_t n, double *dev_US, do
     TTSK_ARG(dev_A && dev_US && dev_S && dev_Vt, "ttsk_svd_small: NULL argument");
     TTSK_ARG(m >= n && n >= 1 && n <= 8192 && m <= (1 << 20), "ttsk_svd_small: need m >= n, 1 <= n <= 8192, got (%lld, %lld)",
              (long long)m, (long long)n);
-    // beyond one workgroup's reach (or from TTSK_SVD_GRID_FROM columns on: tests): the whole-chip kernel of svd_grid.hip
-    static const int64_t grid_from = [] { const char *e = getenv("TTSK_SVD_GRID_FROM"); return e ? atoll(e) : 1025ll; }();
-    if (n >= grid_from) return svd_jacobi_grid(dev_A, m, n, dev_US, dev_S, dev_Vt, stream, st);
-    TTSK_ARG(n <= 1024, "ttsk_svd_small: the one-workgroup kernel takes n <= 1024");
+    // beyond one workgroup's reach: the whole-chip kernel of svd_grid.hip
+    if (n > 1024) return svd_jacobi_grid(dev_A, m, n, dev_US, dev_S, dev_Vt, stream, st);
     double *ws = (double *)scratch(stream, SCRATCH_MISC, (size_t)(m * n + n * n) * 8);
     if (!ws) return TTSK_ERR_HIP;
     size_t jl = 0;
     const int jm = jacobi_lds_mode(m, n, &jl);
-    if (jm < 0) return TTSK_ERR_HIP;
     auto kern = jm == 2 ? jacobi_pinv_kernel<2> : (jm == 1 ? jacobi_pinv_kernel<1> : jacobi_pinv_kernel<0>);
     return launch(kern, dim3(1), dim3(1024), jl, st, dev_A, m, n, 0, ws, ws + m * n, 0.0,
                   (double *)nullptr, (int *)nullptr, dev_US, dev_S, dev_Vt, (const int *)nullptr, (int64_t)0, (int64_t)0);
@@ -1818,11 +1784,9 @@ int ttsk_qr_thin(double *A, int64_t m, int64_t n, int stream)
     TTSK_ARG(A, "ttsk_qr_thin: NULL argument");
     TTSK_ARG(m >= n && n >= 1, "ttsk_qr_thin: need m >= n >= 1, got (%lld, %lld)", (long long)m,
              (long long)n);
-    if (fast_solves()) {
-        const int fr = qr_cholesky(A, m, n, stream, st);
-        if (fr < 0) return fr;
-        if (fr == 1) return TTSK_OK;
-    }
+    const int fr = qr_cholesky(A, m, n, stream, st);
+    if (fr < 0) return fr;
+    if (fr == 1) return TTSK_OK;
     // scratch: tpart[n][nb] (tail-norm partials per pivot column), wpart[nb][n], Q[m*n]
     const int64_t nb = cdiv(m, QR_ROWS);
     const size_t small = (size_t)n * nb + (size_t)nb * n;

@@ -6,7 +6,6 @@
 
 namespace ttsk {
 
-bool fast_solves();                      // TTSK_FAST_SOLVES != 0
 int *deferred_flag(int stream);          // the stream's sticky rejection word (ttsk_deferred_status reads and clears it)
 size_t qr_ws_elems(int64_t m, int n);    // doubles of workspace qr_cholesky needs
 // thin QR in place by CholeskyQR2 with LAPACK's column signs; 1 = queued, 0 = outside the fast path, < 0 = error.

@@ -58,11 +58,8 @@ void *scratch(int s, int slot, size_t bytes)
 
 static void *g_pa[PA_SLOTS];
 static bool g_pa_host[PA_SLOTS];
-static int g_generation = 0;
 
-int init_generation() { return g_generation; }
-
-// Kernels whose dynamic-LDS limit is raised in this init generation, by address (open addressing).  A kernel is entered
+// Kernels whose dynamic-LDS limit is raised since the last init, by address (open addressing).  A kernel is entered
 // only after its hipFuncSetAttribute succeeded; writers hold g_mu, ttsk_shutdown clears the table, and finding an entered
 // kernel takes no lock.  A full table only costs the kernels left out a locked set-up per launch.
 enum { LDS_SLOTS = 4096 };
@@ -184,7 +181,6 @@ int ttsk_shutdown(void)
         g_pa[k] = nullptr;
     }
     for (auto &k : g_lds_raised) k.store(nullptr, std::memory_order_relaxed);
-    ++g_generation;
     g_init = false;
     g_device = -1;
     return TTSK_OK;

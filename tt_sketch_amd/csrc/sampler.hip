@@ -395,7 +395,6 @@ int ttsk_sparse_normal_dev(const int64_t *dev_idx, int64_t row_stride, const int
     // function of (flat prefix index, column, seed) only, so every possible prefix is sampled once and the rows are
     // copied out -- 0.25 instead of 0.78 ms per mode at C4.  Only without the reference's 32-bit wrap of the
     // multipliers (fast_lazy_gaussian.pyx:60-71), i.e. when the flat index really is < prod(shape).
-    static const int dedupe = [] { const char *e = getenv("TTSK_SPARSE_DEDUPE"); return e ? atoi(e) : 1; }();
     const int w = rank_max - rank_min;
     struct ProfScope {      // device time of the whole sampling pass (work unit: Gaussian samples delivered)
         hipStream_t st; bool on;
@@ -404,7 +403,7 @@ int ttsk_sparse_normal_dev(const int64_t *dev_idx, int64_t row_stride, const int
     } prof_scope(st, (double)tot);
     double prod = 1.0;
     for (int i = 0; i < m; ++i) prod *= (double)shape[i];
-    if (dedupe && w <= 32 && prod * 4.0 <= (double)N && prod < 16777216.0) {
+    if (w <= 32 && prod * 4.0 <= (double)N && prod < 16777216.0) {
         const size_t P = (size_t)prod;
         double *table = (double *)scratch(stream, SCRATCH_MISC, P * (size_t)w * 8);
         if (!table) return TTSK_ERR_HIP;

@@ -137,8 +137,7 @@ int launch_r_reduce(hipStream_t st, const double *slab, int chunks, int M, int N
     bool vec = c_n == 1 && !(N & 1) && !(c_m & 1) && !((uintptr_t)slab & 15);
     for (int b = 0; b < nprob && vec; ++b) vec = !((uintptr_t)ro.C[b] & 15);
     const unsigned gy = (unsigned)(nprob * m_tiles);
-    static const int wide = [] { const char *e = getenv("TTSK_REDUCE_WIDE"); return e ? atoi(e) : 1; }();
-    if (vec && wide && chunks >= 64 && gy * cdiv(mn / 2, 64) >= 64)
+    if (vec && chunks >= 64 && gy * cdiv(mn / 2, 64) >= 64)
         return launch(skinny_r_reduce2w, dim3((unsigned)cdiv(mn / 2, 64), gy), dim3(1024), 0, st, (const double2 *)slab, chunks, M,
                       N, m_tiles, Mtot, ro, c_m, alpha, accumulate);
     if (vec)
@@ -159,35 +158,23 @@ static int num_cu()
     return n;
 }
 
-static int skinny_mode()
-{
-    static int m = [] {
-        const char *e = getenv("TTSK_SKINNY");
-        return e ? atoi(e) : 1;
-    }();
-    return m;
-}
-
 // C[m, j] = alpha sum_k W[k, m] S[j, k]
 static int run_s(SkinnyS a, hipStream_t st, int *prof, double flops)
 {
     const int npt = (int)cdiv(a.P, 16);
     const int kb = (a.K + 3) / 4;
     const int64_t nrb = a.U == 1 ? cdiv(a.J, 16) : cdiv(a.U, 16 >> a.tvl) * cdiv(a.V, 1 << a.tvl);
-    static int wgdiv = [] { const char *e = getenv("TTSK_S_SPLIT"); return e ? atoi(e) : 1; }();
-    // CUs one problem of the batch can count on (TTSK_S_SPLIT=0: every problem spreads over all CUs)
-    const int cus = (wgdiv && num_cu() / a.nb > 0) ? num_cu() / a.nb : num_cu();
+    // CUs one problem of the batch can count on
+    const int cus = num_cu() / a.nb > 0 ? num_cu() / a.nb : num_cu();
     // mode (see skinny_s_kernel): rounds of workgroups over the CUs x tile strips per SIMD and round.
     // Mode 2 loads no fragment twice and measured ~10 % faster at equal strip counts, so the others
     // have to beat it by more than that; ties between them go to the one without the shared block.
-    static int mode_force = [] { const char *e = getenv("TTSK_S_MODE"); return e ? atoi(e) : -1; }();
     const int64_t g4 = cdiv(nrb, 4), g5 = cdiv(nrb, 5), g8 = cdiv(nrb, 8);
     const int64_t t4 = cdiv(g4, cus) * npt, t5 = cdiv(g5, cus) * (npt + (npt > 4 ? 2 : 1)), t8 = cdiv(g8, cus) * 2 * npt;
     int spt = 2;
     int64_t best = t8;
     if (t4 * 112 < best * 100) { best = t4 * 112 / 100; spt = 0; }
     if (t5 * 112 < best * 100 && t5 < t4) { best = t5 * 112 / 100; spt = 1; }
-    if (mode_force >= 0 && mode_force <= 2) spt = mode_force;
     const int64_t groups = spt == 2 ? g8 : (spt == 1 ? g5 : g4);
     a.groups = (int)groups;
     const int ldw = ldmf(16 * npt);
@@ -199,9 +186,8 @@ static int run_s(SkinnyS a, hipStream_t st, int *prof, double flops)
     a.wpp = (int)(groups < cus ? groups : cus);
     const int grid = a.wpp * a.nb;
     // partial last tile of W with <= 8 valid columns: 4-wide strips instead of a padded 16x16x4 tile
-    static int strips_on = [] { const char *e = getenv("TTSK_S_STRIPS"); return e ? atoi(e) : 1; }();
     const int rem = (int)(a.P % 16);
-    const int str = (strips_on && rem > 0 && rem <= 8) ? (rem + 3) / 4 : 0;
+    const int str = (rem > 0 && rem <= 8) ? (rem + 3) / 4 : 0;
     if (prof) prof_open(st, flops, 3, str * 1000 + npt * 100 + spt, str > 0, dring == 4);
 #define TTSK_S_GO(D) (str == 2 ? launch_skinny_s_depth<D, 2>(a, npt, spt, lds, grid, st) \
                       : str == 1 ? launch_skinny_s_depth<D, 1>(a, npt, spt, lds, grid, st) \
@@ -242,8 +228,7 @@ static int try_r(const ttsk_gemm_desc &d, int nb, const double *const *A, const 
     if (r.a_gen || r.b_gen) r.a_gen = r.b_gen = 1;     // one generic variant: both sides through plain tiles
     // ... or its 16-byte form when kappa is contiguous on both sides (single-level kappa, even strides / K,
     // 16-byte aligned bases)
-    static int gk_on = [] { const char *e = getenv("TTSK_R_GK"); return e ? atoi(e) : 1; }();
-    bool gk = gk_on && r.a_gen && d.Ko == 1 && r.a_ki == 1 && r.b_ki == 1 && !(K & 1) && !(r.a_m & 1) && !(r.b_n & 1);
+    bool gk = r.a_gen && d.Ko == 1 && r.a_ki == 1 && r.b_ki == 1 && !(K & 1) && !(r.a_m & 1) && !(r.b_n & 1);
     for (int b = 0; b < nb && gk; ++b)
         if (((uintptr_t)A[b] | (uintptr_t)B[b]) & 15) gk = false;
     // a lane's row offset inside a tile (15 rows) has to fit 32 bits next to the kappa walk
@@ -263,7 +248,9 @@ static int try_r(const ttsk_gemm_desc &d, int nb, const double *const *A, const 
     if (d.Ko > 1 && r.a_ko == d.Ki * r.a_ki && r.b_ko == d.Ki * r.b_ki) r.Ki = K;   // uniform walk
     r.rebase = r.Ki == K ? 1 : 0;
     if (gk && r.rebase) r.a_gen = r.b_gen = 2;
+#ifdef TTSK_LAB
     { const char *e = getenv("TTSK_SK_STAMPS"); r.stamps = e ? (long long *)strtoull(e, nullptr, 0) : nullptr; }
+#endif
     r.a_extent = (big - 1) * r.a_m + (d.Ko - 1) * r.a_ko + (d.Ki - 1) * r.a_ki + 1;
     r.b_extent = (r.N - 1) * r.b_n + (d.Ko - 1) * r.b_ko + (d.Ki - 1) * r.b_ki + 1;
     const int cus = num_cu() / nb > 0 ? num_cu() / nb : 1;
@@ -329,7 +316,7 @@ int skinny_try(const ttsk_gemm_desc &d, const double *A, const double *B, double
 int skinny_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, const double *const *B,
                      double *const *C, int stream, hipStream_t st)
 {
-    if (!skinny_mode() || nb < 1 || nb > SK_MAXB) return 0;
+    if (nb < 1 || nb > SK_MAXB) return 0;
     if (d.batch == 1) {
         const int rr = try_r(d, nb, A, B, C, stream, st);
         if (rr != 0) return rr;
@@ -372,7 +359,9 @@ int skinny_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, co
     s.K = (int)K;
     s.alpha = d.alpha;
     s.accumulate = d.accumulate;
+#ifdef TTSK_LAB
     { const char *e = getenv("TTSK_SK_STAMPS"); s.stamps = e ? (long long *)strtoull(e, nullptr, 0) : nullptr; }
+#endif
     s.s_extent = (d.batch - 1) * s.s_u + ((int64_t)s.V - 1) * s.s_j + (K - 1) * s.s_k + 1;
     s.w_extent = (K - 1) * s.w_k + (s.P - 1) * s.w_m + 1;
     s.c_u = d.batch == 1 ? 0 : d.c_b;

@@ -121,21 +121,12 @@ __global__ __launch_bounds__(512) void small_gemm_kernel(SmallG a)
         for (int t = 0; t < 4; ++t) st8(rc, off[q][t], acc[q][t]);
 }
 
-static int small_mode()
-{
-    static int m = [] {
-        const char *e = getenv("TTSK_SMALL");
-        return e ? atoi(e) : 1;
-    }();
-    return m;
-}
-
 // d: single contracted index (Ko == 1); nb pointer triples, or one triple with a uniformly strided d.batch
 int small_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, const double *const *B, double *const *C,
                     int stream, hipStream_t st)
 {
     (void)stream;
-    if (!small_mode() || d.Ko != 1) return 0;
+    if (d.Ko != 1) return 0;
     const int64_t K = d.Ki;
     int64_t count = nb;
     if (d.batch > 1) {
@@ -168,9 +159,7 @@ int small_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, con
     g.accumulate = d.accumulate;
     const bool prof = prof_on();
     if (prof) prof_open(st, 2.0 * count * (double)d.M * (double)d.N * (double)K, 5, 0, false, false);
-    static const int ks_max = [] { const char *e = getenv("TTSK_SMALL_KSPLIT"); return e ? atoi(e) : 8; }();
-    int ksplit = K >= 512 ? 8 : (K >= 256 ? 4 : (K >= 128 ? 2 : 1));
-    if (ksplit > ks_max) ksplit = ks_max;
+    const int ksplit = K >= 512 ? 8 : (K >= 256 ? 4 : (K >= 128 ? 2 : 1));
     const int rc = launch(small_gemm_kernel, dim3((unsigned)(count * g.tiles_m * g.tiles_n)), dim3(64 * ksplit), 0, st, g);
     if (prof) prof_close(st);
     return rc == TTSK_OK ? 1 : rc;

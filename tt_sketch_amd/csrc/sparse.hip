@@ -372,9 +372,8 @@ int ttsk_sparse_psi(const double *dev_val, const int64_t *dev_idx_row, const int
         ~ProfScope() { if (on) prof_close(st); }
     } prof_scope(st, 8.0 * (double)N * (double)((dev_Lv ? l : 0) + (dev_Rv ? r : 0) + 1 + (dev_idx_row ? 1 : 0) + (dev_perm ? 1 : 0)));
     // MFMA kernel: small ranks, and either one slice or mode-sorted input with long slices
-    static int mfma_on = [] { const char *e = getenv("TTSK_SPARSE_MFMA"); return e ? atoi(e) : 1; }();
     const bool single = dev_idx_row == nullptr || n == 1;
-    if (mfma_on && l <= 32 && r <= 32 && N < (1ull << 40) && (single || (dev_perm && N / (size_t)n >= 32))) {
+    if (l <= 32 && r <= 32 && N < (1ull << 40) && (single || (dev_perm && N / (size_t)n >= 32))) {
         const int tl = l <= 16 ? 1 : 2, tr = r <= 16 ? 1 : 2;
         // waves: ~8 per SIMD for the scatter case, one per SIMD slot pair when every wave leaves a partial block
         const size_t want = single ? 2048 : 16384;

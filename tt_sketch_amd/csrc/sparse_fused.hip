@@ -738,8 +738,7 @@ static int sg_gauss_pass(const void *dev_fl, const void *dev_fr, int w32, const 
     const int NT = widest > 16 ? 2 : 1;
     int wmax = 1;
     for (int i = 0; i < 3; ++i) wmax = a.f[i].w > wmax ? a.f[i].w : wmax;
-    static const int edges_on = [] { const char *e = getenv("TTSK_SG_EDGES"); return e ? atoi(e) : 1; }();
-    const int NS = (NT == 2 && edges_on && wmax > 16 && wmax <= 24) ? (wmax <= 20 ? 1 : 2) : 0;   // strips beyond the first 16 columns
+    const int NS = (NT == 2 && wmax > 16 && wmax <= 24) ? (wmax <= 20 ? 1 : 2) : 0;   // strips beyond the first 16 columns
 #ifdef TTSK_LAB
     { const char *e = getenv("TTSK_SG_LAB"); a.lab = e ? atoi(e) : 0; }
 #endif
@@ -755,10 +754,9 @@ static int sg_gauss_pass(const void *dev_fl, const void *dev_fr, int w32, const 
         return (size_t)v;
     }();
     // tile of 32 nonzeros; of 16 where 32 would leave LDS for one wide workgroup per CU only
-    static const int t16_on = [] { const char *e = getenv("TTSK_SG_T16"); return e ? atoi(e) : 1; }();
     const size_t fixed = 16 * NT * 24 + 64;
     int T = SG_T;
-    if (NT == 2 && t16_on && (size_t)(156 * 1024) / (sg_per_wave(a.tcols, SG_T * a.tab, a.qcols, SG_T) * 32 + fixed) < 2) T = 16;
+    if (NT == 2 && (size_t)(156 * 1024) / (sg_per_wave(a.tcols, SG_T * a.tab, a.qcols, SG_T) * 32 + fixed) < 2) T = 16;
     for (int i = 0; i < 3; ++i)
         if (a.f[i].kind == 1) a.off[i] *= T;
     a.tab *= T;

@@ -29,8 +29,7 @@ static int ss_num_cu()
 int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st)
 {
     (void)stream;
-    static int on = [] { const char *e = getenv("TTSK_STREAM_SMALL"); return e ? atoi(e) : 1; }();
-    if (!on || c.nb < 1 || c.nb > SK_MAXB) return 0;
+    if (c.nb < 1 || c.nb > SK_MAXB) return 0;
     if (c.K1 < 1 || c.A < 4 || c.J < 1024) return 0;
     if (c.s_j < c.K1 || c.w_c < c.A || c.c_j < c.A) return 0;
     const int kb = (c.K1 + 3) / 4;
@@ -91,8 +90,7 @@ static int launch_sss(const StreamSmallSum &a, int nf, int str, int unr, size_t 
 int stream_small_sum_try(const StreamSmallSumArgs &c, int stream, hipStream_t st)
 {
     (void)stream;
-    static int on = [] { const char *e = getenv("TTSK_STREAM_SMALL_SUM"); return e ? atoi(e) : 1; }();
-    if (!on || c.nb < 2 || c.K1 < 1 || c.A < 8 || c.J < 1024) return 0;
+    if (c.nb < 2 || c.K1 < 1 || c.A < 8 || c.J < 1024) return 0;
     if (c.s_j < c.K1 || c.w_c < c.A || c.c_j < c.A || c.s_b < 0 || c.w_b < 0) return 0;
     if (((uintptr_t)c.S | (uintptr_t)c.W | (uintptr_t)c.C) & 7) return 0;
     const int kb = (c.K1 + 3) / 4;

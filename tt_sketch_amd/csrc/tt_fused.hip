@@ -297,16 +297,14 @@ static int tt_sketch_core(int nb, int d, const int64_t *n, const int64_t *s, con
     if (sum) tot += blk(nb * szP0);
     // sum mode, larger TT ranks: Psi_mu per tensor (the streamed kernel), then one sum -- faster than the generic
     // tiles on a contracted index of nb * s (measured: s = 60, 100); one block per stream of the Psi phase
-    static const int sum_psi_split = [] { const char *e = getenv("TTSK_SUM_PSI_SPLIT"); return e ? atoi(e) : 48; }();
+    constexpr int sum_psi_split = 48;
     // (small TT ranks: the same blocks take the partial Psi of the K chunks of the one product over (tensor, rank), below)
-    static const int sum_psi_chunks = [] { const char *e = getenv("TTSK_SUM_PSI_CHUNKS"); return e ? atoi(e) : 1; }();
     size_t szPs = 0;
     if (sum)
-        for (int mu = 1; mu < d - 1; ++mu)
-            if (s[mu + 1] > sum_psi_split || sum_psi_chunks) {
-                const size_t v = even((size_t)(l_hi[mu - 1] - l_lo[mu - 1]) * n[mu] * (r_hi[d - 2 - mu] - r_lo[d - 2 - mu]));
-                szPs = v > szPs ? v : szPs;
-            }
+        for (int mu = 1; mu < d - 1; ++mu) {
+            const size_t v = even((size_t)(l_hi[mu - 1] - l_lo[mu - 1]) * n[mu] * (r_hi[d - 2 - mu] - r_lo[d - 2 - mu]));
+            szPs = v > szPs ? v : szPs;
+        }
     const size_t offPs = tot;
     tot += 2 * blk(nb * szPs);
     double *ws0 = (double *)scratch(stream, SCRATCH_DRIVER, tot * 8);
@@ -318,7 +316,6 @@ static int tt_sketch_core(int nb, int d, const int64_t *n, const int64_t *s, con
     // "merged" needs the tensors of a chain matrix exactly behind one another
     auto packedL = [&](int mu) { return szL[mu] == (size_t)s[mu + 1] * lt[mu + 1]; };
     auto packedR = [&](int j) { return szR[j] == (size_t)s[d - 1 - j] * rt[j + 1]; };
-    static const int merge_on = [] { const char *e = getenv("TTSK_TT_MERGE"); return e ? atoi(e) : 1; }();
     std::vector<int> t_inter(d, 0);     // T[mu] stored interleaved: T[(q,k)][(b,p')], row length nb * s[mu+1]
     auto Xc = [&](int b, int mu) { return X[(size_t)b * d + mu]; };
     auto outb = [&](int b) { return out + (size_t)b * out_stride; };
@@ -354,7 +351,7 @@ static int tt_sketch_core(int nb, int d, const int64_t *n, const int64_t *s, con
         }
         // otherwise two launches.  T[q, k, b, p''] = sum_p Rc_b[p,q] X_b[p'',k,p]: a product batched over k whose
         // batch index joins the streamed index, written interleaved over the tensors (row (q,k), columns (b,p'')) ...
-        const bool merged = merge_on && nb > 1 && packedR(j) && (int64_t)nb * sn * rho * nn <= (int64_t)nb * szTR;
+        const bool merged = nb > 1 && packedR(j) && (int64_t)nb * sn * rho * nn <= (int64_t)nb * szTR;
         const int64_t ldt = merged ? (int64_t)nb * sn : sn;
         for (int b = 0; b < nb; ++b) { p.A[b] = Rp(b, j - 1); p.B[b] = Xc(b, mu); p.C[b] = merged ? TRp(0) + (size_t)b * sn : TRp(b); }
         ttsk_gemm_desc g1{};
@@ -410,7 +407,7 @@ static int tt_sketch_core(int nb, int d, const int64_t *n, const int64_t *s, con
             if (fz == 0) {
                 // stacked-terms kernel: T goes out interleaved over the terms for the Psi of a sum (one product over (term,
                 // rank)), per term otherwise
-                const bool inter = sum && merge_on && nb > 1 && packedL(mu);
+                const bool inter = sum && nb > 1 && packedL(mu);
                 ChainSumArgs ca{cs, nullptr, 0, 0, 0};
                 if (!co) {
                     ca.Tint = inter ? ws0 + offT[mu] : Tp0(0, mu);
@@ -426,7 +423,7 @@ static int tt_sketch_core(int nb, int d, const int64_t *n, const int64_t *s, con
             if (fz < 0) return fz;
             if (fz == 1) return TTSK_OK;
         }
-        const bool merged = merge_on && nb > 1 && mu < d - 1 && packedL(mu);
+        const bool merged = nb > 1 && mu < d - 1 && packedL(mu);
         if (merged) {
             // T[q, k, b, p'] = sum_p Lc_b[p,q] X_b[p,k,p'] interleaved over the tensors (batched over k) ...
             t_inter[mu] = 1;
@@ -526,7 +523,7 @@ static int tt_sketch_core(int nb, int d, const int64_t *n, const int64_t *s, con
                 // Psi[(q,k), c] = sum_{b, p'} T_b[(q,k), p'] R_b[p', c]: (b, p') is one contracted index when both
                 // operands hold the tensors behind one another, a two-level one otherwise
                 bool chunked = false;
-                if (t_inter[mu] && packedR(jr) && sum_psi_chunks && l * nn >= 1024 && l * nn < (1ll << 30)) {
+                if (t_inter[mu] && packedR(jr) && l * nn >= 1024 && l * nn < (1ll << 30)) {
                     // K = nb * sp (640 at C5) in chunks whose R image fits the LDS of the streamed kernel (stream_small.h:
                     // fragments of T straight from memory, R in LDS, no barrier after staging): the chunks are the
                     // "problems" of one launch, their partial Psi meet in one sum.  (One product on the generic tiles: 52 us
@@ -723,7 +720,7 @@ static int tt_sketch_core(int nb, int d, const int64_t *n, const int64_t *s, con
         // ... and the interior Psi of the sum, all modes of one shape: the K chunks of EVERY mode as the problems of ONE launch of
         // the streamed kernel (4 modes x 4 chunks at C5: 800 workgroups instead of four launches of 200 on two streams)
         bool psi_batched = false;
-        if (sum && sum_psi_chunks && d >= 4) {
+        if (sum && d >= 4) {
             const int64_t sp = s[2], nn = n[1], l = l_hi[0] - l_lo[0], r = r_hi[d - 3] - r_lo[d - 3], ldr = rt[d - 2];
             bool same = l * nn >= 1024 && l * nn < (1ll << 30);
             for (int mu = 1; mu < d - 1 && same; ++mu) {

@@ -54,7 +54,7 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
     int *sticky = deferred_flag(stream);
     auto rr = [&](int mu) { return rt[d - 1 - mu]; };                          // right sketch rank of mode mu < d - 1
     auto kk = [&](int mu) { return mu < 0 ? (int64_t)1 : (orth ? lt[mu + 1] : rr(mu)); };   // rank of the output cores
-    bool ok = fast_solves() && sticky != nullptr;
+    bool ok = sticky != nullptr;
     int64_t mmax = 0, kmax = 0, smax = 0, tmax = 0;
     for (int mu = 0; mu < d; ++mu) {
         TTSK_ARG(n[mu] >= 1 && s[mu + 1] >= 1 && X[mu] && cores_out[mu], "ttsk_tt_orth_sketch: bad mode %d", mu);
@@ -69,7 +69,7 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
         kmax = std::max(kmax, kk(mu));
     }
     if (!ok || d - 1 > SK_MAXB) {
-        set_error("ttsk_tt_orth_sketch: outside the one-call path (ranks, shapes or TTSK_FAST_SOLVES=0)");
+        set_error("ttsk_tt_orth_sketch: outside the one-call path (ranks or shapes)");
         return TTSK_ERR_UNSUPPORTED;
     }
     int rc;
@@ -136,15 +136,13 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
     // with it the rows (b, i) of the next unfolding, which changes neither that unfolding's R nor Q~ beyond the same row
     // flips -- and the sign reconstruction of every mode (an n-step elimination in one workgroup) runs on the helper
     // stream beside the next mode's products.  One pass over the cores at the end applies S_{mu-1} (rows) and S_mu (columns).
-    static const int signs_beside = [] { const char *e = getenv("TTSK_ORTH_SIGNS_BESIDE"); return e ? atoi(e) : 1; }();
-    bool beside = signs_beside && kmax <= QR_CHOL_MAX_N;
+    bool beside = kmax <= QR_CHOL_MAX_N;
     for (int mu = 1; mu < d - 1; ++mu) beside = beside && kk(mu - 1) * n[mu] >= 2 * kk(mu);   // (the one-workgroup Householder QR of a nearly square unfolding signs its Q itself: only mode 0 may take it)
     const int aux = (stream + 1) % TTSK_NUM_STREAMS;
     TTSK_STREAM(st_aux, aux);
     double *Lc = Lb, *Ln = Lb + szL;                      // Q-chain (s[mu] x k_{mu-1}) of this mode / of the next one
     std::vector<const double *> Sg(d, nullptr);           // signs of mode mu (nullptr: none / all ones)
     // core[a, i, b] *= S_{mu-1}[a] S_mu[b] on the helper stream, behind the sign kernels and behind the main stream's work so far
-    static const int fix_beside = [] { const char *e = getenv("TTSK_ORTH_FIX_BESIDE"); return e ? atoi(e) : 1; }();
     auto fix_core = [&](int mu) -> int {
         const double *spv = mu > 0 ? Sg[mu - 1] : nullptr, *snv = mu < d - 1 ? Sg[mu] : nullptr;
         if (!spv && !snv) return TTSK_OK;
@@ -185,11 +183,9 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
         // next chain matrix Ln[p', q'] = sum_{(q,i)} T[(q,i), p'] Q[(q,i), q']
         CK(gemm2(sp, k, m, Tm, 1, sp, Q, k, 1, Ln, stream));
         std::swap(Lc, Ln);
-        if (beside && fix_beside) CK(fix_core(mu));       // the chain has read Q~ for the last time
+        if (beside) CK(fix_core(mu));                     // the chain has read Q~ for the last time
     }
     if (beside) {
-        if (!fix_beside)
-            for (int mu = 0; mu < d - 1; ++mu) CK(fix_core(mu));
         CK(fix_core(d - 1));
         CK(ttsk_stream_wait(stream, aux));
     }
@@ -225,8 +221,7 @@ static int orth_batch_fused(int count, int d, const int64_t *n, const int64_t *s
 {
     TTSK_STREAM(st, stream);
     const bool orth = DL != nullptr;
-    static const int on = [] { const char *e = getenv("TTSK_ORTH_BATCH_FUSED"); return e ? atoi(e) : 1; }();
-    if (!on || count < 2 || count > 16 || d < 2 || d - 1 > SK_MAXB || !fast_solves()) return 0;
+    if (count < 2 || count > 16 || d < 2 || d - 1 > SK_MAXB) return 0;
     int *sticky = deferred_flag(stream);
     if (!sticky) return 0;
     auto rr = [&](int mu) { return rt[d - 1 - mu]; };
@@ -457,9 +452,7 @@ int ttsk_tt_assemble(int d, const int64_t *n, const int64_t *lr, const int64_t *
         TTSK_ARG(omega[k] && work[k] && lr[k] >= 1 && rr[k] >= 1, "ttsk_tt_assemble: bad Omega %d", k);
         batched = batched && lr[k] == lr[0] && rr[k] == rr[0];
     }
-    static const int batch_on = [] { const char *e = getenv("TTSK_ASSEMBLE_BATCH"); return e ? atoi(e) : 1; }();
-    static const int refine = [] { const char *e = getenv("TTSK_ASSEMBLE_REFINE"); return e ? atoi(e) : 1; }();
-    if (batched && batch_on) {
+    if (batched) {
         rc = ttsk_pinv_batch(d - 1, omega, lr[0], rr[0], work, stream);
         if (rc == TTSK_ERR_UNSUPPORTED) batched = false;
         else if (rc < 0) return rc;
@@ -486,13 +479,13 @@ int ttsk_tt_assemble(int d, const int64_t *n, const int64_t *lr, const int64_t *
         const int nb = (int)G.size();
         const int64_t m = lr[0] * n[1], l = lr[0], r = rr[0];
         if (nb >= 2 && nb <= SK_MAXB) {
-            double *Rall = refine ? (double *)scratch(stream, SCRATCH_ORTH, (size_t)nb * m * r * 8) : nullptr;
-            if (refine && !Rall) return TTSK_ERR_HIP;
+            double *Rall = (double *)scratch(stream, SCRATCH_ORTH, (size_t)nb * m * r * 8);
+            if (!Rall) return TTSK_ERR_HIP;
             const double *A[SK_MAXB], *B[SK_MAXB], *Om[SK_MAXB], *Rc[SK_MAXB];
             double *C[SK_MAXB], *R[SK_MAXB];
             for (int b = 0; b < nb; ++b) {
                 A[b] = psi[G[b]]; B[b] = work[G[b]]; C[b] = cores_out[G[b]]; Om[b] = omega[G[b]];
-                R[b] = Rall ? Rall + (size_t)b * m * r : nullptr; Rc[b] = R[b];
+                R[b] = Rall + (size_t)b * m * r; Rc[b] = R[b];
             }
             auto desc = [](int64_t M, int64_t N, int64_t K, double alpha, int acc) {
                 ttsk_gemm_desc g{};
@@ -504,27 +497,25 @@ int ttsk_tt_assemble(int d, const int64_t *n, const int64_t *lr, const int64_t *
             if (rc < 0) return rc;
             if (rc == 1) {
                 for (int b = 0; b < nb; ++b) grouped[G[b]] = 1;
-                if (refine) {
-                    // R <- Psi: the interior cores of a packed sketch lie behind one another: one copy
-                    bool adjacent = true;
-                    for (int b = 1; b < nb; ++b) adjacent = adjacent && A[b] == A[b - 1] + (size_t)m * r;
-                    if (adjacent) {
-                        TTSK_HIP(hipMemcpyAsync(R[0], A[0], (size_t)nb * m * r * 8, hipMemcpyDeviceToDevice, st));
-                    } else {
-                        for (int b = 0; b < nb; ++b)
-                            TTSK_HIP(hipMemcpyAsync(R[b], A[b], (size_t)m * r * 8, hipMemcpyDeviceToDevice, st));
-                    }
-                    const double *Cc[SK_MAXB];
-                    for (int b = 0; b < nb; ++b) Cc[b] = C[b];
-                    rc = skinny_try_batch(desc(m, r, l, -1.0, 1), nb, Cc, Om, R, stream, st);           // R = Psi - C Omega
-                    if (rc < 0) return rc;
-                    if (rc == 0)
-                        for (int b = 0; b < nb; ++b) CK(gemm2(m, r, l, C[b], l, 1, Om[b], r, 1, R[b], stream, -1.0, 1));
-                    rc = skinny_try_batch(desc(m, l, r, 1.0, 1), nb, Rc, B, C, stream, st);              // C += R P
-                    if (rc < 0) return rc;
-                    if (rc == 0)
-                        for (int b = 0; b < nb; ++b) CK(gemm2(m, l, r, R[b], r, 1, B[b], l, 1, C[b], stream, 1.0, 1));
+                // R <- Psi: the interior cores of a packed sketch lie behind one another: one copy
+                bool adjacent = true;
+                for (int b = 1; b < nb; ++b) adjacent = adjacent && A[b] == A[b - 1] + (size_t)m * r;
+                if (adjacent) {
+                    TTSK_HIP(hipMemcpyAsync(R[0], A[0], (size_t)nb * m * r * 8, hipMemcpyDeviceToDevice, st));
+                } else {
+                    for (int b = 0; b < nb; ++b)
+                        TTSK_HIP(hipMemcpyAsync(R[b], A[b], (size_t)m * r * 8, hipMemcpyDeviceToDevice, st));
                 }
+                const double *Cc[SK_MAXB];
+                for (int b = 0; b < nb; ++b) Cc[b] = C[b];
+                rc = skinny_try_batch(desc(m, r, l, -1.0, 1), nb, Cc, Om, R, stream, st);           // R = Psi - C Omega
+                if (rc < 0) return rc;
+                if (rc == 0)
+                    for (int b = 0; b < nb; ++b) CK(gemm2(m, r, l, C[b], l, 1, Om[b], r, 1, R[b], stream, -1.0, 1));
+                rc = skinny_try_batch(desc(m, l, r, 1.0, 1), nb, Rc, B, C, stream, st);              // C += R P
+                if (rc < 0) return rc;
+                if (rc == 0)
+                    for (int b = 0; b < nb; ++b) CK(gemm2(m, l, r, R[b], r, 1, B[b], l, 1, C[b], stream, 1.0, 1));
             }
         }
     }
@@ -551,25 +542,21 @@ int ttsk_tt_assemble(int d, const int64_t *n, const int64_t *lr, const int64_t *
             const int64_t m = (k ? lr[k - 1] : 1) * n[k];
             TTSK_ARG(psi[k] && cores_out[k], "ttsk_tt_assemble: NULL core %d", k);
             CK(gemm2(m, lr[k], rr[k], psi[k], rr[k], 1, work[k], lr[k], 1, cores_out[k], q));
-            if (refine) {
-                double *R = (double *)scratch(q, SCRATCH_DRIVER, (size_t)m * rr[k] * 8);
-                if (!R) return TTSK_ERR_HIP;
-                TTSK_HIP(hipMemcpyAsync(R, psi[k], (size_t)m * rr[k] * 8, hipMemcpyDeviceToDevice, stream_of(q)));
-                CK(gemm2(m, rr[k], lr[k], cores_out[k], lr[k], 1, omega[k], rr[k], 1, R, q, -1.0, 1));       // R = Psi - C Omega
-                CK(gemm2(m, lr[k], rr[k], R, rr[k], 1, work[k], lr[k], 1, cores_out[k], q, 1.0, 1));         // C += R P
-            }
+            double *R = (double *)scratch(q, SCRATCH_DRIVER, (size_t)m * rr[k] * 8);
+            if (!R) return TTSK_ERR_HIP;
+            TTSK_HIP(hipMemcpyAsync(R, psi[k], (size_t)m * rr[k] * 8, hipMemcpyDeviceToDevice, stream_of(q)));
+            CK(gemm2(m, rr[k], lr[k], cores_out[k], lr[k], 1, omega[k], rr[k], 1, R, q, -1.0, 1));       // R = Psi - C Omega
+            CK(gemm2(m, lr[k], rr[k], R, rr[k], 1, work[k], lr[k], 1, cores_out[k], q, 1.0, 1));         // C += R P
         } else {
             // C_{k+1}[c, (i, b)] = sum_a P_k[c, a] Psi_{k+1}[a, (i, b)]
             const int64_t cols = n[k + 1] * (k + 1 < d - 1 ? rr[k + 1] : 1);
             TTSK_ARG(psi[k + 1] && cores_out[k + 1], "ttsk_tt_assemble: NULL core %d", k + 1);
             CK(gemm2(rr[k], cols, lr[k], work[k], lr[k], 1, psi[k + 1], cols, 1, cores_out[k + 1], q));
-            if (refine) {
-                double *R = (double *)scratch(q, SCRATCH_DRIVER, (size_t)lr[k] * cols * 8);
-                if (!R) return TTSK_ERR_HIP;
-                TTSK_HIP(hipMemcpyAsync(R, psi[k + 1], (size_t)lr[k] * cols * 8, hipMemcpyDeviceToDevice, stream_of(q)));
-                CK(gemm2(lr[k], cols, rr[k], omega[k], rr[k], 1, cores_out[k + 1], cols, 1, R, q, -1.0, 1)); // R = Psi - Omega C
-                CK(gemm2(rr[k], cols, lr[k], work[k], lr[k], 1, R, cols, 1, cores_out[k + 1], q, 1.0, 1));   // C += P R
-            }
+            double *R = (double *)scratch(q, SCRATCH_DRIVER, (size_t)lr[k] * cols * 8);
+            if (!R) return TTSK_ERR_HIP;
+            TTSK_HIP(hipMemcpyAsync(R, psi[k + 1], (size_t)lr[k] * cols * 8, hipMemcpyDeviceToDevice, stream_of(q)));
+            CK(gemm2(lr[k], cols, rr[k], omega[k], rr[k], 1, cores_out[k + 1], cols, 1, R, q, -1.0, 1)); // R = Psi - Omega C
+            CK(gemm2(rr[k], cols, lr[k], work[k], lr[k], 1, R, cols, 1, cores_out[k + 1], q, 1.0, 1));   // C += P R
         }
     }
     const int e = direction == 0 ? d - 1 : 0;                                   // the core that is copied

@@ -173,8 +173,8 @@ def _right_product(S: DevArray, B) -> DevArray:
     return contract("bq,mq->bm", S, _mat(B))
 
 
-# beyond mode 0 the fused pair only pays on a large left product (C2: 2.7 GB); TTSK_DENSE_PAIR_MIN_BYTES for A/B runs
-_PAIR_MIN_BYTES = int(os.environ.get("TTSK_DENSE_PAIR_MIN_BYTES", 1 << 28))
+# beyond mode 0 the fused pair only pays on a large left product (C2: 2.7 GB)
+_PAIR_MIN_BYTES = 1 << 28
 
 
 def _first_pass(A, B, X, mu: int = 0) -> bool:
@@ -184,8 +184,6 @@ def _first_pass(A, B, X, mu: int = 0) -> bool:
     import ctypes
     from .. import _native as nat
     if not (isinstance(A, ChainedUnfolding) and A.depth == mu and isinstance(B, ChainedUnfolding) and B.prev is not None):
-        return False
-    if os.environ.get("TTSK_DENSE_ONE_PASS", "1") == "0":
         return False
     if mu == 0:
         S, rows = X, int(X.shape[0])

@@ -126,8 +126,7 @@ def _mode_stream(tensor: SparseTensor, mu: int):
         nat.call("ttsk_sparse_mode_order", ctypes.c_void_p(idx.ptr), N, ctypes.c_size_t(N), ints(r_rows), _u64(r_shape or [1]),
                  len(r_rows), int(order[mu]), int(tensor.shape[mu]), ctypes.c_void_p(perm.ptr), 0)
         # 32-bit flat indices where every prefix / suffix extent stays below 2^31 (20 instead of 28 bytes per record and pass)
-        small = (int(np.prod(l_shape or [1], dtype=object)) < 2**31 and int(np.prod(r_shape or [1], dtype=object)) < 2**31
-                 and os.environ.get("TTSK_SPARSE_U32", "1") != "0")
+        small = int(np.prod(l_shape or [1], dtype=object)) < 2**31 and int(np.prod(r_shape or [1], dtype=object)) < 2**31
         words = (N + 1) // 2 if small else N
         fl, fr = DevArray.empty((words,), dtype=np.int64), DevArray.empty((words,), dtype=np.int64)
         jj = DevArray.empty(((N + 1) // 2,), dtype=np.int64)          # int32 records
