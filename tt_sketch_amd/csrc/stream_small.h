@@ -313,4 +313,8 @@ struct StreamSmallArgs {
 };
 int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st);
 
+// the fewest equal chunks (<= max_chunks, SK_MAXB) of whole k-blocks into which a contraction of length K splits so that
+// a chunk's W image (A columns) fits the kernel's LDS in one column chunk: the problems of one launch; 0 = none
+int stream_small_chunks(int64_t K, int64_t A, int max_chunks);
+
 }  // namespace ttsk

@@ -78,6 +78,13 @@ int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st)
     return rc == TTSK_OK ? 1 : (rc == 1 ? 0 : rc);
 }
 
+int stream_small_chunks(int64_t K, int64_t A, int max_chunks)
+{
+    for (int t = 1; t <= max_chunks && t <= SK_MAXB; ++t)
+        if (K % t == 0 && (K / t) % 4 == 0 && 4 * (K / t / 4 + 6) * ((A + 3) / 4 * 4) * 8 <= 150 * 1024) return t;
+    return 0;
+}
+
 static int launch_sss(const StreamSmallSum &a, int nf, int str, int unr, size_t lds, int grid, hipStream_t st)
 {
 #define TTSK_SSS_CASE(NF, STR) if (nf == NF && str == STR) return launch(unr == 25 ? stream_small_sum_kernel<NF, STR, 5, 25> : stream_small_sum_kernel<NF, STR, 5, 5>, dim3((unsigned)grid), dim3(512), lds, st, a);
