@@ -245,6 +245,52 @@ def test_assemble_one_call_d12_mixed_mode_sizes(tsa, monkeypatch, direction):
         assert tsa.TensorTrain(one).error(X) < 1e-8
 
 
+@pytest.mark.parametrize("entry", ["ttsk_pinv_batch", "ttsk_pinv_batch_deferred"])
+@pytest.mark.parametrize("l,r", [(10, 600), (600, 10)])
+def test_pinv_batch_declines_a_stage_beyond_the_small_kernel_before_queuing(tsa, entry, l, r):
+    """(10, 600): the Gram product (10 x 10) fits the batched small kernel, the solve (600 x 10) does not.  The batched
+    entries check every stage before the first launch: TtskUnsupported, the outputs untouched."""
+    from tt_sketch_amd import _native as nat
+    from tt_sketch_amd.device import as_dev
+    rng = np.random.default_rng(8)
+    ds = [as_dev(rng.standard_normal((l, r))) for _ in range(3)]
+    outs = [as_dev(np.full((r, l), 7.0)) for _ in ds]
+    P = ctypes.c_void_p
+    with pytest.raises(nat.TtskUnsupported):
+        nat.call(entry, 3, (P * 3)(*[x.ptr for x in ds]), l, r, (P * 3)(*[o.ptr for o in outs]), 0)
+    for o in outs:
+        assert (o.get() == 7.0).all()
+
+
+@pytest.mark.parametrize("direction", ["right", "left"])
+@pytest.mark.parametrize("l,r", [(10, 600), (600, 10)])
+def test_assemble_one_call_with_omega_beyond_the_batched_pseudo_inverse(tsa, monkeypatch, direction, l, r):
+    """Omega of one shape whose solve the batched small kernel declines: ttsk_tt_assemble's batched pseudo-inverses decline
+    before queuing anything and the pairs take the path of their own -- the cores of the pair-by-pair path (sketch.py:400-443)."""
+    from tt_sketch_amd import sketch
+    from tt_sketch_amd.sketch import assemble_sketched_tt
+    from tt_sketch_amd.sketch_container import SketchContainer
+    rng = np.random.default_rng(29)
+    n, d = (7, 8, 9), 3
+    Om = [rng.standard_normal((l, r)) for _ in range(d - 1)]
+    Psi = [rng.standard_normal((1 if mu == 0 else l, n[mu], 1 if mu == d - 1 else r)) for mu in range(d)]
+    sk = SketchContainer([np.array(p) for p in Psi], [np.array(o) for o in Om])
+    hits = []
+    real = sketch._assemble_one_call
+
+    def spy(*a, **k):
+        out = real(*a, **k)
+        hits.append(out is not None)
+        return out
+    monkeypatch.setattr(sketch, "_assemble_one_call", spy)
+    one = [np.asarray(c) for c in assemble_sketched_tt(sk, direction=direction)]
+    assert hits == [True]
+    monkeypatch.setenv("TTSK_ASSEMBLE_ONE_CALL", "0")
+    pairs = [np.asarray(c) for c in assemble_sketched_tt(sk, direction=direction)]
+    for a, b in zip(one, pairs):
+        assert a.shape == b.shape and np.abs(a - b).max() <= 1e-10 * max(1.0, np.abs(b).max())
+
+
 @pytest.mark.parametrize("direction", ["right", "left"])
 def test_assembly_matches_lstsq_for_ill_conditioned_omega(tsa, monkeypatch, direction):
     """Omega with singular values from 1 down to 1e-4 (what the sketches of TT-GMRES iterates look like): the assembled

@@ -3,9 +3,9 @@
 // ttsk_tt_assemble; per Omega shape the launches are a fixed handful whatever the batch size:
 //
 //   1. gram:   every Omega_{b,k} copied into one contiguous staging buffer and its Gram matrix formed (one launch);
-//   2. chol:   the batched Cholesky inverse of all Gram matrices (linalg.hip's chol_inv_kernel, one launch);
+//   2. chol:   the batched Cholesky inverse of all Gram matrices (cholesky.hip's chol_inv_kernel, one launch);
 //   3. solve:  X = Omega^T G^-1 (l <= r) or G^-1 Omega^T, the normal-equations pseudo-inverse (one launch);
-//   4. jacobi: linalg.hip's one-sided Jacobi pseudo-inverse, a workgroup per matrix, each predicated on its own Cholesky
+//   4. jacobi: jacobi.hip's one-sided Jacobi pseudo-inverse, a workgroup per matrix, each predicated on its own Cholesky
 //      verdict (one launch; it leaves at once where the attempt was accepted): a rank-deficient or ill-conditioned Omega
 //      takes the robust path on the device, alone, without a read-back -- ttsk_pinv_batch's numerics, no 32-matrix limit;
 //   5. apply:  the fused refined product below (one launch per 16 groups of equally spaced pairs).
@@ -259,16 +259,6 @@ __global__ __launch_bounds__(AB_THREADS) void assemble_solve_kernel(int l, int r
     }
 }
 
-int gemm1(int64_t M, int64_t N, int64_t K, const double *A, int64_t a_m, int64_t a_k, const double *B, int64_t b_k, int64_t b_n,
-          double *C, int stream, double alpha, int accumulate)
-{
-    ttsk_gemm_desc g{};
-    g.batch = 1; g.M = M; g.N = N; g.Ko = 1; g.Ki = K;
-    g.a_m = a_m; g.a_ki = a_k; g.b_ki = b_k; g.b_n = b_n; g.c_m = N; g.c_n = 1;
-    g.alpha = alpha; g.accumulate = accumulate;
-    return ttsk_gemm(&g, A, B, C, nullptr, stream);
-}
-
 // one pair's operands, before grouping
 struct AbPair {
     const double *psi, *om;
@@ -308,15 +298,15 @@ int apply_fallback(const std::vector<AbPair> &pairs, int64_t l, int64_t r, int d
         double *R = (double *)scratch(stream, SCRATCH_DRIVER, (size_t)p.m * (direction == 0 ? r : l) * 8);
         if (!R) return TTSK_ERR_HIP;
         if (direction == 0) {
-            if ((rc = gemm1(p.m, l, r, p.psi, r, 1, p.work, l, 1, p.c, stream, 1.0, 0))) return rc;            // C = Psi P
+            if ((rc = gemm_plain(p.m, l, r, p.psi, r, 1, p.work, l, 1, p.c, stream, 1.0, 0))) return rc;            // C = Psi P
             TTSK_HIP(hipMemcpyAsync(R, p.psi, (size_t)p.m * r * 8, hipMemcpyDeviceToDevice, st));
-            if ((rc = gemm1(p.m, r, l, p.c, l, 1, p.om, r, 1, R, stream, -1.0, 1))) return rc;                 // R = Psi - C Omega
-            if ((rc = gemm1(p.m, l, r, R, r, 1, p.work, l, 1, p.c, stream, 1.0, 1))) return rc;                // C += R P
+            if ((rc = gemm_plain(p.m, r, l, p.c, l, 1, p.om, r, 1, R, stream, -1.0, 1))) return rc;                 // R = Psi - C Omega
+            if ((rc = gemm_plain(p.m, l, r, R, r, 1, p.work, l, 1, p.c, stream, 1.0, 1))) return rc;                // C += R P
         } else {
-            if ((rc = gemm1(r, p.m, l, p.work, l, 1, p.psi, p.m, 1, p.c, stream, 1.0, 0))) return rc;          // C = P Psi
+            if ((rc = gemm_plain(r, p.m, l, p.work, l, 1, p.psi, p.m, 1, p.c, stream, 1.0, 0))) return rc;          // C = P Psi
             TTSK_HIP(hipMemcpyAsync(R, p.psi, (size_t)l * p.m * 8, hipMemcpyDeviceToDevice, st));
-            if ((rc = gemm1(l, p.m, r, p.om, r, 1, p.c, p.m, 1, R, stream, -1.0, 1))) return rc;               // R = Psi - Omega C
-            if ((rc = gemm1(r, p.m, l, p.work, l, 1, R, p.m, 1, p.c, stream, 1.0, 1))) return rc;              // C += P R
+            if ((rc = gemm_plain(l, p.m, r, p.om, r, 1, p.c, p.m, 1, R, stream, -1.0, 1))) return rc;               // R = Psi - Omega C
+            if ((rc = gemm_plain(r, p.m, l, p.work, l, 1, R, p.m, 1, p.c, stream, 1.0, 1))) return rc;              // C += P R
         }
     }
     return TTSK_OK;

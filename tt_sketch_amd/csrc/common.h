@@ -99,4 +99,31 @@ int svd_jacobi_grid(const double *A, int64_t m, int64_t n, double *US, double *S
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// The one place a ttsk_gemm_desc is filled: one problem (batch = 1), C[m, n] (strides c_m, c_n) (+)= alpha sum_{ko, ki}
+// A[m, ko, ki] B[ko, ki, n] with the element strides given ...
+inline ttsk_gemm_desc gemm_desc2(int64_t M, int64_t N, int64_t Ko, int64_t Ki, int64_t a_m, int64_t a_ko, int64_t a_ki, int64_t b_ko,
+                                 int64_t b_ki, int64_t b_n, int64_t c_m, int64_t c_n, int accumulate, double alpha = 1.0)
+{
+    ttsk_gemm_desc d{};
+    d.batch = 1; d.M = M; d.N = N; d.Ko = Ko; d.Ki = Ki;
+    d.a_m = a_m; d.a_ko = a_ko; d.a_ki = a_ki;
+    d.b_ko = b_ko; d.b_ki = b_ki; d.b_n = b_n;
+    d.c_m = c_m; d.c_n = c_n;
+    d.alpha = alpha; d.accumulate = accumulate; d.split_k = 0;
+    return d;
+}
+// ... and the plain product: one contracted index of length K, C row-major with row stride c_m (0: N)
+inline ttsk_gemm_desc gemm_desc(int64_t M, int64_t N, int64_t K, int64_t a_m, int64_t a_k, int64_t b_k, int64_t b_n, double alpha = 1.0,
+                                int accumulate = 0, int64_t c_m = 0)
+{
+    return gemm_desc2(M, N, 1, K, a_m, 0, a_k, 0, b_k, b_n, c_m ? c_m : N, 1, accumulate, alpha);
+}
+// that plain product through ttsk_gemm
+inline int gemm_plain(int64_t M, int64_t N, int64_t K, const double *A, int64_t a_m, int64_t a_k, const double *B, int64_t b_k,
+                      int64_t b_n, double *C, int stream, double alpha = 1.0, int accumulate = 0, int64_t c_m = 0)
+{
+    const ttsk_gemm_desc d = gemm_desc(M, N, K, a_m, a_k, b_k, b_n, alpha, accumulate, c_m);
+    return ttsk_gemm(&d, A, B, C, nullptr, stream);
+}
+
 }  // namespace ttsk

@@ -731,9 +731,15 @@ int launch_r_reduce(hipStream_t st, const double *slab, int chunks, int M, int N
 // 1 = launched, 0 = shape not covered (caller falls through to the generic kernel), < 0 = error
 int skinny_try(const ttsk_gemm_desc &d, const double *A, const double *B, double *C, const double *k_scale,
                int stream, hipStream_t st);
-// small products (small.hip): nb pointer triples, or one triple with a uniformly strided d.batch
+// small products (small.hip): nb pointer triples, or one triple with a uniformly strided d.batch; small_batch_covers: whether
+// small_try_batch launches that shape (its answer depends on the descriptor and nb alone)
+bool small_batch_covers(const ttsk_gemm_desc &d, int nb);
 int small_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, const double *const *B, double *const *C,
                     int stream, hipStream_t st);
+// the same product for each of `count` problems: the batched chain kernel (skinny_try_batch) where it covers the shape, else
+// the batched small kernel, else one ttsk_gemm per problem (small.hip).  TTSK_OK or < 0.
+int gemm_each(const ttsk_gemm_desc &d, int count, const double *const *A, const double *const *B, double *const *C, int stream,
+              hipStream_t st);
 // the same product for nb <= SK_MAXB problems of one shape (the tensors of a batch) in one launch
 int skinny_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, const double *const *B,
                      double *const *C, int stream, hipStream_t st);

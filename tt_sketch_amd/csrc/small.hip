@@ -121,23 +121,40 @@ __global__ __launch_bounds__(512) void small_gemm_kernel(SmallG a)
         for (int t = 0; t < 4; ++t) st8(rc, off[q][t], acc[q][t]);
 }
 
+// elements from each operand's base to its last element + 1 (A, B, C)
+static void small_extents(const ttsk_gemm_desc &d, int64_t e[3])
+{
+    e[0] = (d.M - 1) * d.a_m + (d.Ki - 1) * d.a_ki + 1;
+    e[1] = (d.N - 1) * d.b_n + (d.Ki - 1) * d.b_ki + 1;
+    e[2] = (d.M - 1) * d.c_m + (d.N - 1) * d.c_n + 1;
+}
+
 // d: single contracted index (Ko == 1); nb pointer triples, or one triple with a uniformly strided d.batch
+bool small_batch_covers(const ttsk_gemm_desc &d, int nb)
+{
+    if (d.Ko != 1) return false;
+    const int64_t K = d.Ki;
+    int64_t count = nb;
+    if (d.batch > 1) {
+        if (nb != 1) return false;
+        count = d.batch;
+    }
+    if (count < 1 || count > SK_MAXB) return false;
+    if (K < 1 || K > 1024 || d.M > 512 || d.N > 512) return false;
+    if (2.0 * d.M * d.N * K > 48e6) return false;        // beyond a few MFLOP the tiled kernels win
+    if (d.a_m < 0 || d.a_ki < 0 || d.b_ki < 0 || d.b_n < 0 || d.c_m < 0 || d.c_n < 0) return false;
+    if (d.batch > 1 && (d.a_b < 0 || d.b_b < 0 || d.c_b < 0)) return false;
+    int64_t e[3];
+    small_extents(d, e);
+    return (e[0] + 64 * d.a_ki) * 8 < (1ll << 32) - 64 && (e[1] + 64 * d.b_ki) * 8 < (1ll << 32) - 64 && e[2] * 8 < (1ll << 32) - 64;
+}
+
 int small_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, const double *const *B, double *const *C,
                     int stream, hipStream_t st)
 {
     (void)stream;
-    if (d.Ko != 1) return 0;
-    const int64_t K = d.Ki;
-    int64_t count = nb;
-    if (d.batch > 1) {
-        if (nb != 1) return 0;
-        count = d.batch;
-    }
-    if (count < 1 || count > SK_MAXB) return 0;
-    if (K < 1 || K > 1024 || d.M > 512 || d.N > 512) return 0;
-    if (2.0 * d.M * d.N * K > 48e6) return 0;            // beyond a few MFLOP the tiled kernels win
-    if (d.a_m < 0 || d.a_ki < 0 || d.b_ki < 0 || d.b_n < 0 || d.c_m < 0 || d.c_n < 0) return 0;
-    if (d.batch > 1 && (d.a_b < 0 || d.b_b < 0 || d.c_b < 0)) return 0;
+    if (!small_batch_covers(d, nb)) return 0;
+    const int64_t K = d.Ki, count = d.batch > 1 ? d.batch : nb;
     SmallG g{};
     g.nb = (int)count;
     for (int b = 0; b < count; ++b) {
@@ -149,12 +166,9 @@ int small_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, con
     g.tiles_m = (int)cdiv(d.M, 16);
     g.tiles_n = (int)cdiv(d.N, 32);
     g.a_m = d.a_m; g.a_k = d.a_ki; g.b_k = d.b_ki; g.b_n = d.b_n; g.c_m = d.c_m; g.c_n = d.c_n;
-    g.a_extent = (d.M - 1) * d.a_m + (K - 1) * d.a_ki + 1;
-    g.b_extent = (d.N - 1) * d.b_n + (K - 1) * d.b_ki + 1;
-    g.c_extent = (d.M - 1) * d.c_m + (d.N - 1) * d.c_n + 1;
-    if ((g.a_extent + 64 * d.a_ki) * 8 >= (1ll << 32) - 64 || (g.b_extent + 64 * d.b_ki) * 8 >= (1ll << 32) - 64 ||
-        g.c_extent * 8 >= (1ll << 32) - 64)
-        return 0;
+    int64_t e[3];
+    small_extents(d, e);
+    g.a_extent = e[0]; g.b_extent = e[1]; g.c_extent = e[2];
     g.alpha = d.alpha;
     g.accumulate = d.accumulate;
     const bool prof = prof_on();
@@ -163,6 +177,17 @@ int small_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, con
     const int rc = launch(small_gemm_kernel, dim3((unsigned)(count * g.tiles_m * g.tiles_n)), dim3(64 * ksplit), 0, st, g);
     if (prof) prof_close(st);
     return rc == TTSK_OK ? 1 : rc;
+}
+
+int gemm_each(const ttsk_gemm_desc &d, int count, const double *const *A, const double *const *B, double *const *C, int stream,
+              hipStream_t st)
+{
+    int rc = skinny_try_batch(d, count, A, B, C, stream, st);
+    if (rc == 0) rc = small_try_batch(d, count, A, B, C, stream, st);
+    if (rc != 0) return rc < 0 ? rc : TTSK_OK;
+    for (int b = 0; b < count; ++b)
+        if ((rc = ttsk_gemm(&d, A[b], B[b], C[b], nullptr, stream))) return rc;
+    return TTSK_OK;
 }
 
 }  // namespace ttsk

@@ -1,4 +1,4 @@
-// One-sided Jacobi SVD on the whole chip, for factors beyond the one-workgroup kernel of linalg.hip
+// One-sided Jacobi SVD on the whole chip, for factors beyond the one-workgroup kernel of jacobi.hip
 // (n > 1024 columns): the classical TT-SVD of a dense tensor (reference tt_svd.py:10-49 takes LAPACK's
 // SVD of every unfolding) meets (r n) x (r n) triangular factors with r n in the thousands.
 //

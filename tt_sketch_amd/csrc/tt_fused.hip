@@ -94,18 +94,6 @@ static void prof_flush()
 // The launches of a scope carry profiling class `cls`; everything outside such a scope is class NCLS - 1.
 struct ProfClass { explicit ProfClass(int cls) { g_cls = cls; } ~ProfClass() { g_cls = NCLS - 1; } };
 
-static ttsk_gemm_desc desc2(int64_t M, int64_t N, int64_t Ko, int64_t Ki, int64_t a_m, int64_t a_ko, int64_t a_ki,
-                            int64_t b_ko, int64_t b_ki, int64_t b_n, int64_t c_m, int64_t c_n, int accumulate)
-{
-    ttsk_gemm_desc d{};
-    d.batch = 1; d.M = M; d.N = N; d.Ko = Ko; d.Ki = Ki;
-    d.a_m = a_m; d.a_ko = a_ko; d.a_ki = a_ki;
-    d.b_ko = b_ko; d.b_ki = b_ki; d.b_n = b_n;
-    d.c_m = c_m; d.c_n = c_n;
-    d.alpha = 1.0; d.accumulate = accumulate; d.split_k = 0;
-    return d;
-}
-
 // C (+)= A * B as described by d, tagged with its profiling class.
 static int gemm(int cls, const ttsk_gemm_desc &d, const double *A, const double *B, double *C, int stream)
 {
@@ -288,7 +276,7 @@ static int right_step(const Ctx &c, int j)
     if (j == 0) {
         // Rc_0[p'',q'] = sum_k X[p'',k,0] E[0,k,q']
         for (int b = 0; b < nb; ++b) { p.A[b] = c.Xc(b, mu); p.B[b] = c.DR[j]; p.C[b] = c.Rp(b, j); }
-        CK(gemm_batch(5, nb, desc2(sn, rhop, 1, nn, nn * sp, 0, sp, 0, rhop, 1, rhop, 1, 0), p, c.stream, c.st));
+        CK(gemm_batch(5, nb, gemm_desc2(sn, rhop, 1, nn, nn * sp, 0, sp, 0, rhop, 1, rhop, 1, 0), p, c.stream, c.st));
         return TTSK_OK;
     }
     // first choice: both products in one launch, T never written (chain_fused.h)
@@ -302,7 +290,7 @@ static int right_step(const Ctx &c, int j)
     const bool merged = nb > 1 && c.packedR(j) && (int64_t)nb * sn * rho * nn <= (int64_t)nb * c.szTR;
     const int64_t ldt = merged ? (int64_t)nb * sn : sn;
     for (int b = 0; b < nb; ++b) { p.A[b] = c.Rp(b, j - 1); p.B[b] = c.Xc(b, mu); p.C[b] = merged ? c.TRp(0) + (size_t)b * sn : c.TRp(b); }
-    ttsk_gemm_desc g1 = desc2(rho, sn, 1, sp, 1, 0, rho, 0, 1, nn * sp, nn * ldt, 1, 0);
+    ttsk_gemm_desc g1 = gemm_desc2(rho, sn, 1, sp, 1, 0, rho, 0, 1, nn * sp, nn * ldt, 1, 0);
     g1.batch = nn; g1.b_b = sp; g1.c_b = ldt;
     const int fast = gemm_batch(0, nb, g1, p, c.stream, c.st, !merged);
     if (fast < 0) return fast;
@@ -311,19 +299,19 @@ static int right_step(const Ctx &c, int j)
         // ... so that Rn_all[(b,p''), q'] = sum_{q,k} T[(q,k), (b,p'')] E[q,k,q'] is ONE long product: E is read
         // once, not once per tensor
         q.A[0] = c.TRp(0); q.B[0] = c.DR[j]; q.C[0] = c.Rp(0, j);
-        CK(gemm_batch(1, 1, desc2((int64_t)nb * sn, rhop, rho, nn, 1, nn * ldt, ldt, nn * rhop, rhop, 1, rhop, 1, 0), q,
+        CK(gemm_batch(1, 1, gemm_desc2((int64_t)nb * sn, rhop, rho, nn, 1, nn * ldt, ldt, nn * rhop, rhop, 1, rhop, 1, 0), q,
                       c.stream, c.st));
         return TTSK_OK;
     }
     for (int b = 0; b < nb; ++b) { q.A[b] = c.TRp(b); q.B[b] = c.DR[j]; q.C[b] = c.Rp(b, j); }
     if (fast == 1) {
         // Rn[p'', q'] = sum_{q,k} T[q,k,p''] E[q,k,q']
-        CK(gemm_batch(1, nb, desc2(sn, rhop, rho, nn, 1, nn * sn, sn, nn * rhop, rhop, 1, rhop, 1, 0), q, c.stream, c.st));
+        CK(gemm_batch(1, nb, gemm_desc2(sn, rhop, rho, nn, 1, nn * sn, sn, nn * rhop, rhop, 1, rhop, 1, 0), q, c.stream, c.st));
     } else {
         // T[q, p'', k] = sum_p Rc[p,q] X[p'',k,p]    (M=q, N=(p'',k), K=p)
-        CK(gemm_batch(0, nb, desc2(rho, sn * nn, 1, sp, 1, 0, rho, 0, 1, sp, sn * nn, 1, 0), p, c.stream, c.st));
+        CK(gemm_batch(0, nb, gemm_desc2(rho, sn * nn, 1, sp, 1, 0, rho, 0, 1, sp, sn * nn, 1, 0), p, c.stream, c.st));
         // Rn[p'', q'] = sum_{q,k} T[q,p'',k] E[q,k,q']
-        CK(gemm_batch(1, nb, desc2(sn, rhop, rho, nn, nn, sn * nn, 1, nn * rhop, rhop, 1, rhop, 1, 0), q, c.stream, c.st));
+        CK(gemm_batch(1, nb, gemm_desc2(sn, rhop, rho, nn, nn, sn * nn, 1, nn * rhop, rhop, 1, rhop, 1, 0), q, c.stream, c.st));
     }
     return TTSK_OK;
 }
@@ -338,7 +326,7 @@ static int left_step(Ctx &c, int mu)
     if (mu == 0) {
         // L_0[p',q'] = sum_k X_0[0,k,p'] D_0[0,k,q']
         for (int b = 0; b < nb; ++b) { p.A[b] = c.Xc(b, 0); p.B[b] = c.DL[0]; p.C[b] = c.Lp(b, 0); }
-        CK(gemm_batch(5, nb, desc2(sp, lt[1], 1, nn, 1, 0, sp, 0, lt[1], 1, lt[1], 1, 0), p, c.aux, c.st_aux));
+        CK(gemm_batch(5, nb, gemm_desc2(sp, lt[1], 1, nn, 1, 0, sp, 0, lt[1], 1, lt[1], 1, 0), p, c.aux, c.st_aux));
         return TTSK_OK;
     }
     const int64_t lfull = lt[mu];
@@ -365,25 +353,25 @@ static int left_step(Ctx &c, int mu)
         const int64_t ldt = (int64_t)nb * sp;
         double *T0 = c.Tp0(0, mu);
         for (int b = 0; b < nb; ++b) { p.A[b] = c.Lp(b, mu - 1); p.B[b] = c.Xc(b, mu); p.C[b] = T0 + (size_t)b * sp; }
-        ttsk_gemm_desc g1 = desc2(lfull, sp, 1, sn, 1, 0, lfull, 0, nn * sp, 1, nn * ldt, 1, 0);
+        ttsk_gemm_desc g1 = gemm_desc2(lfull, sp, 1, sn, 1, 0, lfull, 0, nn * sp, 1, nn * ldt, 1, 0);
         g1.batch = nn; g1.b_b = sp; g1.c_b = ldt;
         CK(gemm_batch(2, nb, g1, p, c.aux, c.st_aux));
         // ... and L_all[(b,p'), q'] = sum_{q,k} T[(q,k), (b,p')] D[q,k,q'] as one long product
         BatchPtrs q{};
         q.A[0] = T0; q.B[0] = c.DL[mu]; q.C[0] = c.Lp(0, mu);
-        CK(gemm_batch(3, 1, desc2((int64_t)nb * sp, lt[mu + 1], lfull, nn, 1, nn * ldt, ldt, nn * lt[mu + 1], lt[mu + 1], 1,
+        CK(gemm_batch(3, 1, gemm_desc2((int64_t)nb * sp, lt[mu + 1], lfull, nn, 1, nn * ldt, ldt, nn * lt[mu + 1], lt[mu + 1], 1,
                                   lt[mu + 1], 1, 0), q, c.aux, c.st_aux));
         return TTSK_OK;
     }
     // T[q,k,p'] = sum_p Lc[p,q] X[p,k,p']      (M=q (all lfull columns), N=(k,p'), K=p)
     for (int b = 0; b < nb; ++b) { p.A[b] = c.Lp(b, mu - 1); p.B[b] = c.Xc(b, mu); p.C[b] = c.Tp0(b, mu); }
-    CK(gemm_batch(mu == d - 1 ? 5 : 2, nb, desc2(lfull, nn * sp, 1, sn, 1, 0, lfull, 0, nn * sp, 1, nn * sp, 1, 0), p,
+    CK(gemm_batch(mu == d - 1 ? 5 : 2, nb, gemm_desc2(lfull, nn * sp, 1, sn, 1, 0, lfull, 0, nn * sp, 1, nn * sp, 1, 0), p,
                   c.aux, c.st_aux));
     if (mu < d - 1) {
         // L_mu[p',q'] = sum_{q,k} T[q,k,p'] D[q,k,q']
         BatchPtrs q{};
         for (int b = 0; b < nb; ++b) { q.A[b] = c.Tp0(b, mu); q.B[b] = c.DL[mu]; q.C[b] = c.Lp(b, mu); }
-        CK(gemm_batch(3, nb, desc2(sp, lt[mu + 1], 1, lfull * nn, 1, 0, sp, 0, lt[mu + 1], 1, lt[mu + 1], 1, 0), q,
+        CK(gemm_batch(3, nb, gemm_desc2(sp, lt[mu + 1], 1, lfull * nn, 1, 0, sp, 0, lt[mu + 1], 1, lt[mu + 1], 1, 0), q,
                       c.aux, c.st_aux));
     }
     return TTSK_OK;
@@ -445,8 +433,8 @@ static int psi_sum_one_product(const Ctx &c, int mu, int q)
             if (rc == 1) return nch > 1 ? ttsk_sum_slices(psi, blk0, nch, c.szPs, (size_t)(l * nn * r), c.accumulate, q) : TTSK_OK;
         }
     }
-    return gemm(4, one_index ? desc2(l * nn, r, 1, (int64_t)nb * sp, ldt, 0, 1, 0, ldr, 1, r, 1, c.accumulate)
-                             : desc2(l * nn, r, nb, sp, ldt, c.t_inter[mu] ? sp : (int64_t)c.szT[mu], 1, (int64_t)c.szR[jr], ldr, 1,
+    return gemm(4, one_index ? gemm_desc2(l * nn, r, 1, (int64_t)nb * sp, ldt, 0, 1, 0, ldr, 1, r, 1, c.accumulate)
+                             : gemm_desc2(l * nn, r, nb, sp, ldt, c.t_inter[mu] ? sp : (int64_t)c.szT[mu], 1, (int64_t)c.szR[jr], ldr, 1,
                                      r, 1, c.accumulate), c.Tslice(0, mu), c.Rslice(0, jr), psi, q);
 }
 
@@ -466,7 +454,7 @@ static int psi_omega(const Ctx &c, int mu, int q, bool do_psi, bool do_omega)
         // Psi_0[0,k,c] = sum_{p'} X_0[0,k,p'] R_0[p',c].  Of a sum: the cores X_b,0 are anywhere in memory: per-tensor
         // products into the workspace, then one sum
         for (int b = 0; b < nb; ++b) { p.A[b] = c.Xc(b, 0); p.B[b] = c.Rslice(b, jr); p.C[b] = c.sum ? c.P0(b) : c.outb(b) + c.psi_at[0]; }
-        CK(gemm_batch(5, nb, desc2(nn, r, 1, sp, sp, 0, 1, 0, ldr, 1, r, 1, c.sum ? 0 : c.accumulate), p, q, stq));
+        CK(gemm_batch(5, nb, gemm_desc2(nn, r, 1, sp, sp, 0, 1, 0, ldr, 1, r, 1, c.sum ? 0 : c.accumulate), p, q, stq));
         if (c.sum) CK(ttsk_sum_slices(c.out + c.psi_at[0], c.P0(0), nb, c.szP0, (size_t)(nn * r), c.accumulate, q));
     } else if (mu == d - 1) {
         // last mode: Psi_{d-1}[q,k,0] = T[q,k,0], of a sum sum_b T_b[q,k,0]
@@ -498,7 +486,7 @@ static int psi_omega(const Ctx &c, int mu, int q, bool do_psi, bool do_omega)
             const int acc = c.sum ? 0 : c.accumulate;
             const StreamSmallArgs ss{nb, 0 /* J: psi_stream */, (int)sp, (int)r, p.A, ldt, p.B, ldr, p.C, r, acc};
             CK(psi_stream(stream_small_try, ss, l * nn, q, stq));
-            if (rc == 0) CK(gemm_batch(4, nb, desc2(l * nn, r, 1, sp, ldt, 0, 1, 0, ldr, 1, r, 1, acc), p, q, stq));
+            if (rc == 0) CK(gemm_batch(4, nb, gemm_desc2(l * nn, r, 1, sp, ldt, 0, 1, 0, ldr, 1, r, 1, acc), p, q, stq));
             if (c.sum) CK(ttsk_sum_slices(c.out + c.psi_at[mu], blk0, nb, c.szPs, (size_t)(l * nn * r), c.accumulate, q));
         }
     }
@@ -506,12 +494,12 @@ static int psi_omega(const Ctx &c, int mu, int q, bool do_psi, bool do_omega)
     const int64_t l = c.lw(mu);
     if (c.sum)   // Omega[q, c] = sum_{b, p} L_b[p, q] R_b[p, c]
         return gemm(5, c.packedL(mu) && c.packedR(jr)
-                           ? desc2(l, r, 1, (int64_t)nb * sp, 1, 0, c.lt[mu + 1], 0, ldr, 1, r, 1, c.accumulate)
-                           : desc2(l, r, nb, sp, 1, (int64_t)c.szL[mu], c.lt[mu + 1], (int64_t)c.szR[jr], ldr, 1, r, 1, c.accumulate),
+                           ? gemm_desc2(l, r, 1, (int64_t)nb * sp, 1, 0, c.lt[mu + 1], 0, ldr, 1, r, 1, c.accumulate)
+                           : gemm_desc2(l, r, nb, sp, 1, (int64_t)c.szL[mu], c.lt[mu + 1], (int64_t)c.szR[jr], ldr, 1, r, 1, c.accumulate),
                     c.Lslice(0, mu), c.Rslice(0, jr), c.out + c.om_at[mu], q);
     // Omega_mu = L_mu[:, lo:hi]^T R_mu[:, lo:hi]; the workspace blocks and the outputs of a
     // batch are equally spaced, so the nb products are one batched launch
-    ttsk_gemm_desc od = desc2(l, r, 1, sp, 1, 0, c.lt[mu + 1], 0, ldr, 1, r, 1, c.accumulate);
+    ttsk_gemm_desc od = gemm_desc2(l, r, 1, sp, 1, 0, c.lt[mu + 1], 0, ldr, 1, r, 1, c.accumulate);
     od.batch = nb; od.a_b = (int64_t)c.szL[mu]; od.b_b = (int64_t)c.szR[jr]; od.c_b = c.out_stride;
     return gemm(5, od, c.Lslice(0, mu), c.Rslice(0, jr), c.outb(0) + c.om_at[mu], q);
 }
@@ -548,7 +536,7 @@ static int tail_grouped(const Ctx &c, bool ends_early)
         for (int b = 0; b < nb; ++b, ++cnt) {
             o.A[cnt] = c.Lslice(b, mu); o.B[cnt] = c.Rslice(b, d - 2 - mu); o.C[cnt] = c.outb(b) + c.om_at[mu];
         }
-    CK(gemm_batch(5, cnt, desc2(l, r, 1, sp, 1, 0, c.lt[1], 0, ldr, 1, r, 1, c.accumulate), o, c.aux, c.st_aux));
+    CK(gemm_batch(5, cnt, gemm_desc2(l, r, 1, sp, 1, 0, c.lt[1], 0, ldr, 1, r, 1, c.accumulate), o, c.aux, c.st_aux));
     if (!ends_early) CK(psi_omega(c, 0, c.aux, true, false));
     CK(psi_omega(c, d - 1, c.stream, true, false));
     return 1;
@@ -569,7 +557,7 @@ static int tail_sum(const Ctx &c, bool &om_batched, bool &psi_batched)
         BatchPtrs o{};
         for (int mu = 0; mu < d - 1; ++mu) { o.A[mu] = c.Lslice(0, mu); o.B[mu] = c.Rslice(0, d - 2 - mu); o.C[mu] = c.out + c.om_at[mu]; }
         const int64_t l = c.lw(0), r = c.rw(d - 2);
-        CK(gemm_batch(5, d - 1, desc2(l, r, 1, (int64_t)nb * c.s[1], 1, 0, c.lt[1], 0, c.rt[d - 1], 1, r, 1, c.accumulate), o, c.aux, c.st_aux));
+        CK(gemm_batch(5, d - 1, gemm_desc2(l, r, 1, (int64_t)nb * c.s[1], 1, 0, c.lt[1], 0, c.rt[d - 1], 1, r, 1, c.accumulate), o, c.aux, c.st_aux));
         om_batched = true;
     }
     // ... and the interior Psi: the K chunks of EVERY mode as the problems of ONE launch of the streamed kernel (4 modes x
@@ -773,7 +761,7 @@ int tt_chains_batch(int nb, int d, const int64_t *n, const int64_t *s, const int
             o.A[cnt] = c.Lp(b, mu); o.B[cnt] = c.Rp(b, d - 2 - mu); o.C[cnt] = out->omega[(size_t)b * (d - 1) + mu];
             if (chain_pairs_one_shape && ++cnt < SK_MAXB && !(b == nb - 1 && mu == d - 2)) continue;
             const int64_t l = lt[mu + 1], r = rt[d - 1 - mu];
-            CK(gemm_batch(5, chain_pairs_one_shape ? cnt : 1, desc2(l, r, 1, s[mu + 1], 1, 0, l, 0, r, 1, r, 1, 0), o, stream, st));
+            CK(gemm_batch(5, chain_pairs_one_shape ? cnt : 1, gemm_desc2(l, r, 1, s[mu + 1], 1, 0, l, 0, r, 1, r, 1, 0), o, stream, st));
             cnt = 0;
         }
     return TTSK_OK;

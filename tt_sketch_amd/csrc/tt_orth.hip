@@ -23,20 +23,6 @@
 
 using namespace ttsk;
 
-namespace {
-
-int gemm2(int64_t M, int64_t N, int64_t K, const double *A, int64_t a_m, int64_t a_k, const double *B, int64_t b_k, int64_t b_n,
-          double *C, int stream, double alpha = 1.0, int accumulate = 0)
-{
-    ttsk_gemm_desc d{};
-    d.batch = 1; d.M = M; d.N = N; d.Ko = 1; d.Ki = K;
-    d.a_m = a_m; d.a_ki = a_k; d.b_ki = b_k; d.b_n = b_n; d.c_m = N; d.c_n = 1;
-    d.alpha = alpha; d.accumulate = accumulate;
-    return ttsk_gemm(&d, A, B, C, nullptr, stream);
-}
-
-}  // namespace
-
 extern "C" {
 
 int ttsk_pinv_batch_deferred(int count, const double *const *dev_omegas, int64_t l, int64_t r, double *const *dev_pinvs, int stream);
@@ -63,8 +49,8 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
         smax = std::max(smax, s[mu + 1]);
         if (mu == d - 1) break;
         TTSK_ARG(DR[mu] && rt[mu + 1] >= 1 && (!orth || (DL[mu] && lt[mu + 1] >= 1 && omega_out[mu])), "ttsk_tt_orth_sketch: bad DRM core %d", mu);
-        ok = ok && kk(mu) <= QR_CHOL_MAX_N && m >= kk(mu);
-        if (orth) ok = ok && std::min(lt[mu + 1], rr(mu)) <= QR_CHOL_MAX_N;
+        ok = ok && kk(mu) <= CHOL_MAX_N && m >= kk(mu);
+        if (orth) ok = ok && std::min(lt[mu + 1], rr(mu)) <= CHOL_MAX_N;
         mmax = std::max(mmax, m);
         kmax = std::max(kmax, kk(mu));
     }
@@ -81,7 +67,7 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
     CK(tt_chains(d, n, s, lt, rt, X, DL, DR, &ch, stream));
     // ---- workspace of this driver
     auto blk = [](size_t v) { return (v + 31) & ~(size_t)31; };
-    // (the d - 1 pseudo-inverses as batched launches when the Omega share one shape with min(l, r) <= 128)
+    // (the d - 1 pseudo-inverses as batched launches when the Omega share one shape that ttsk_pinv_batch_deferred covers)
     bool one_shape = orth;
     size_t pmax = 0, pws = 0;
     int64_t lmax = 1;
@@ -91,11 +77,11 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
         pws = std::max(pws, pinv_deferred_ws_elems(lt[mu + 1], rr(mu)));
         lmax = std::max(lmax, lt[mu + 1]);
     }
-    one_shape = one_shape && std::min(lt[1], rr(0)) <= 128;
+    one_shape = one_shape && pinv_batch_covers(d - 1, lt[1], rr(0), true);
     const size_t szP = orth ? blk(pmax) : 0, szW = orth ? blk((size_t)smax * lmax) : 0;
     const size_t szL = blk((size_t)smax * kmax), szT = blk((size_t)tmax);
     const size_t szQ = blk(qr_ws_elems(mmax, (int)kmax));
-    const size_t szS = blk((size_t)kmax), szSW = kmax > 128 ? blk((size_t)kmax * kmax) : 0, szPW = one_shape ? 0 : blk(pws);
+    const size_t szS = blk((size_t)kmax), szSW = kmax > CHOL_ONE_N ? blk((size_t)kmax * kmax) : 0, szPW = one_shape ? 0 : blk(pws);
     double *ws = (double *)scratch(stream, SCRATCH_ORTH, ((size_t)(d - 1) * (szP + szW + szS) + 2 * szL + szT + szQ + szSW + szPW) * 8);
     if (!ws) return TTSK_ERR_HIP;
     double *P0 = ws, *W0 = P0 + (size_t)(d - 1) * szP, *Lb = W0 + (size_t)(d - 1) * szW, *T = Lb + 2 * szL, *qws = T + szT, *Sb = qws + szQ;
@@ -120,14 +106,11 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
         for (int mu = 0; mu < d - 1; ++mu) { A[mu] = ch.Rc[d - 2 - mu]; B[mu] = pv[mu]; C[mu] = W0 + (size_t)mu * szW; W[mu] = C[mu]; }
         int done = 0;
         if (one_shape) {
-            ttsk_gemm_desc g{};
-            g.batch = 1; g.M = s[1]; g.N = lt[1]; g.Ko = 1; g.Ki = rr(0);
-            g.a_m = rr(0); g.a_ki = 1; g.b_ki = lt[1]; g.b_n = 1; g.c_m = lt[1]; g.c_n = 1; g.alpha = 1.0;
-            CK(done = small_try_batch(g, d - 1, A, B, C, stream, st));
+            CK(done = small_try_batch(gemm_desc(s[1], lt[1], rr(0), rr(0), 1, lt[1], 1), d - 1, A, B, C, stream, st));
         }
         if (!done)
             for (int mu = 0; mu < d - 1; ++mu)
-                CK(gemm2(s[mu + 1], lt[mu + 1], rr(mu), A[mu], rr(mu), 1, B[mu], lt[mu + 1], 1, C[mu], stream));
+                CK(gemm_plain(s[mu + 1], lt[mu + 1], rr(mu), A[mu], rr(mu), 1, B[mu], lt[mu + 1], 1, C[mu], stream));
     } else {
         for (int mu = 0; mu < d - 1; ++mu) W[mu] = ch.Rc[d - 2 - mu];
     }
@@ -136,7 +119,7 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
     // with it the rows (b, i) of the next unfolding, which changes neither that unfolding's R nor Q~ beyond the same row
     // flips -- and the sign reconstruction of every mode (an n-step elimination in one workgroup) runs on the helper
     // stream beside the next mode's products.  One pass over the cores at the end applies S_{mu-1} (rows) and S_mu (columns).
-    bool beside = kmax <= QR_CHOL_MAX_N;
+    bool beside = kmax <= CHOL_MAX_N;
     for (int mu = 1; mu < d - 1; ++mu) beside = beside && kk(mu - 1) * n[mu] >= 2 * kk(mu);   // (the one-workgroup Householder QR of a nearly square unfolding signs its Q itself: only mode 0 may take it)
     const int aux = (stream + 1) % TTSK_NUM_STREAMS;
     TTSK_STREAM(st_aux, aux);
@@ -160,7 +143,7 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
         } else {
             // T[q, i, p'] = sum_p Lc[p, q] X[p, i, p']
             double *dst = mu == d - 1 ? cores_out[mu] : T;
-            CK(gemm2(kp, nn * sp, sn, Lc, 1, kp, X[mu], nn * sp, 1, dst, stream));
+            CK(gemm_plain(kp, nn * sp, sn, Lc, 1, kp, X[mu], nn * sp, 1, dst, stream));
             Tm = dst;
         }
         if (mu == d - 1) {
@@ -169,7 +152,7 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
         }
         const int64_t k = kk(mu);
         double *Q = cores_out[mu];
-        CK(gemm2(m, k, sp, Tm, sp, 1, W[mu], k, 1, Q, stream));                     // M = T W
+        CK(gemm_plain(m, k, sp, Tm, sp, 1, W[mu], k, 1, Q, stream));                     // M = T W
         rc = qr_cholesky(Q, m, k, stream, st, qws, sticky, beside);
         if (rc < 0) return rc;
         if (rc == 0) { set_error("ttsk_tt_orth_sketch: QR outside the fast path"); return TTSK_ERR_UNSUPPORTED; }
@@ -181,7 +164,7 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
             Sg[mu] = Sm;
         }
         // next chain matrix Ln[p', q'] = sum_{(q,i)} T[(q,i), p'] Q[(q,i), q']
-        CK(gemm2(sp, k, m, Tm, 1, sp, Q, k, 1, Ln, stream));
+        CK(gemm_plain(sp, k, m, Tm, 1, sp, Q, k, 1, Ln, stream));
         std::swap(Lc, Ln);
         if (beside) CK(fix_core(mu));                     // the chain has read Q~ for the last time
     }
@@ -214,14 +197,14 @@ __global__ void orth_spread_flag_kernel(int *sticky, int *dst, int count)
 // (qr_cholesky_batch), the sign reconstruction (qr_signs_batch, helper stream) and the next chain matrix, each one launch with
 // `count` problems.  ~90 launches per batch instead of per tensor, on operands count times larger.  The fast factorisations'
 // verdict is one flag for the whole batch (a rejection repeats every tensor of it on its own).
-// 1 = done, 0 = shapes outside this path (nothing written that the caller may not overwrite), < 0 = error.
+// 1 = done, 0 = shapes outside this path (decided before anything is queued), < 0 = error.
 static int orth_batch_fused(int count, int d, const int64_t *n, const int64_t *s, const int64_t *lt, const int64_t *rt,
                             const double *const *X, const double *const *DL, const double *const *DR, double *const *cores_out,
                             double *const *omega_out, int *dev_status, int stream)
 {
     TTSK_STREAM(st, stream);
     const bool orth = DL != nullptr;
-    if (count < 2 || count > 16 || d < 2 || d - 1 > SK_MAXB) return 0;
+    if (count < 2 || count > QR_BATCH_MAX || d < 2 || d - 1 > SK_MAXB) return 0;
     int *sticky = deferred_flag(stream);
     if (!sticky) return 0;
     auto rr = [&](int mu) { return rt[d - 1 - mu]; };
@@ -234,14 +217,22 @@ static int orth_batch_fused(int count, int d, const int64_t *n, const int64_t *s
         smax = std::max(smax, s[mu + 1]);
         if (mu == d - 1) break;
         // every unfolding at least twice as tall as wide (CholeskyQR2 + signs beside the chain), factors within one workgroup's LDS
-        if (kk(mu) > 128 || m < 2 * kk(mu)) return 0;
-        if (orth && (std::min(lt[mu + 1], rr(mu)) > 128 || lt[mu + 1] != lt[1] || rr(mu) != rr(0) || s[mu + 1] != s[1])) return 0;
+        if (!qr_cholesky_batch_covers(count, m, (int)kk(mu)) || !qr_signs_batch_covers(count, (int)kk(mu))) return 0;
+        if (orth && (lt[mu + 1] != lt[1] || rr(mu) != rr(0) || s[mu + 1] != s[1])) return 0;
         mmax = std::max(mmax, m);
         kmax = std::max(kmax, kk(mu));
         if (orth) { pmax = std::max(pmax, (size_t)rr(mu) * lt[mu + 1]); lmax = std::max(lmax, lt[mu + 1]); }
     }
+    // the pseudo-inverses of all (tensor, mode) pairs: ttsk_pinv_batch_deferred over SK_MAXB of them at a time
+    const int pairs = count * (d - 1), full = std::min(pairs, SK_MAXB), rest = pairs % SK_MAXB;
+    if (orth && (!pinv_batch_covers(full, lt[1], rr(0), true) || (rest && !pinv_batch_covers(rest, lt[1], rr(0), true)))) return 0;
     int rc;
 #define CK(x) do { rc = (x); if (rc < 0) return rc; } while (0)
+    // from here on a decline of a callee contradicts the predicates above: an error, never a fallback (work is queued)
+    auto declined = [](const char *what) {
+        set_error("ttsk_tt_orth_sketch_batch: internal error: %s declined a shape its predicate covers", what);
+        return TTSK_ERR_HIP;
+    };
     // ---- 1. chains (and Omega) of all tensors
     TTChains ch{};
     ch.want_left = orth ? 1 : 0;
@@ -261,23 +252,6 @@ static int orth_batch_fused(int count, int d, const int64_t *n, const int64_t *s
     auto Pv = [&](int b, int mu) { return P0 + ((size_t)b * (d - 1) + mu) * szP; };
     auto Wv = [&](int b, int mu) { return W0 + ((size_t)b * (d - 1) + mu) * szW; };
     auto Sv = [&](int b, int mu) { return Sb + ((size_t)b * (d - 1) + mu) * szS; };
-    auto desc = [](int64_t M, int64_t N, int64_t K, int64_t a_m, int64_t a_k, int64_t b_k, int64_t b_n) {
-        ttsk_gemm_desc g{};
-        g.batch = 1; g.M = M; g.N = N; g.Ko = 1; g.Ki = K;
-        g.a_m = a_m; g.a_ki = a_k; g.b_ki = b_k; g.b_n = b_n; g.c_m = N; g.c_n = 1; g.alpha = 1.0;
-        return g;
-    };
-    // one product for every tensor: a batched launch where the shape has one, tensor by tensor otherwise
-    auto prod = [&](const ttsk_gemm_desc &g, const double *const *A, const double *const *B, double *const *C) -> int {
-        int r = skinny_try_batch(g, count, A, B, C, stream, st);
-        if (r == 0) r = small_try_batch(g, count, A, B, C, stream, st);
-        if (r != 0) return r < 0 ? r : TTSK_OK;
-        for (int b = 0; b < count; ++b) {
-            r = gemm2(g.M, g.N, g.Ki, A[b], g.a_m, g.a_ki, B[b], g.b_ki, g.b_n, C[b], stream);
-            if (r < 0) return r;
-        }
-        return TTSK_OK;
-    };
     // ---- 2. W_b,mu = R_b,mu Omega_b,mu^+
     std::vector<const double *> W((size_t)count * (d - 1));
     if (orth) {
@@ -290,12 +264,13 @@ static int orth_batch_fused(int count, int d, const int64_t *n, const int64_t *s
                 A[cnt] = Rc(b, d - 2 - mu); B[cnt] = pv[cnt]; C[cnt] = Wv(b, mu);
                 W[(size_t)b * (d - 1) + mu] = C[cnt];
                 if (++cnt == SK_MAXB || (b == count - 1 && mu == d - 2)) {
-                    CK(ttsk_pinv_batch_deferred(cnt, om, lt[1], rr(0), pv, stream));
-                    ttsk_gemm_desc g = desc(s[1], lt[1], rr(0), rr(0), 1, lt[1], 1);
-                    int done = small_try_batch(g, cnt, A, B, C, stream, st);
+                    rc = ttsk_pinv_batch_deferred(cnt, om, lt[1], rr(0), pv, stream);
+                    if (rc == TTSK_ERR_UNSUPPORTED) return declined("ttsk_pinv_batch_deferred");
+                    CK(rc);
+                    int done = small_try_batch(gemm_desc(s[1], lt[1], rr(0), rr(0), 1, lt[1], 1), cnt, A, B, C, stream, st);
                     if (done < 0) return done;
                     if (!done)
-                        for (int q = 0; q < cnt; ++q) CK(gemm2(s[1], lt[1], rr(0), A[q], rr(0), 1, B[q], lt[1], 1, C[q], stream));
+                        for (int q = 0; q < cnt; ++q) CK(gemm_plain(s[1], lt[1], rr(0), A[q], rr(0), 1, B[q], lt[1], 1, C[q], stream));
                     cnt = 0;
                 }
             }
@@ -308,9 +283,9 @@ static int orth_batch_fused(int count, int d, const int64_t *n, const int64_t *s
     TTSK_STREAM(st_aux, aux);
     std::vector<const double *> Sg((size_t)count * d, nullptr);
     auto fix_cores = [&](int mu) -> int {
-        double *c[16];
-        const double *spv[16], *snv[16];
-        int k0[16], nv[16], k1[16];
+        double *c[QR_BATCH_MAX];
+        const double *spv[QR_BATCH_MAX], *snv[QR_BATCH_MAX];
+        int k0[QR_BATCH_MAX], nv[QR_BATCH_MAX], k1[QR_BATCH_MAX];
         bool any = false;
         for (int b = 0; b < count; ++b) {
             spv[b] = mu > 0 ? Sg[(size_t)b * d + mu - 1] : nullptr;
@@ -324,56 +299,65 @@ static int orth_batch_fused(int count, int d, const int64_t *n, const int64_t *s
         if (r < 0) return r;
         return apply_signs(count, c, spv, snv, k0, nv, k1, st_aux);
     };
-    const double *Tm[16], *Lc[16], *Xm[16], *Wm[16];
-    double *Ln[16], *Q[16], *Td[16];
-    int flip = 0;
-    for (int mu = 0; mu < d; ++mu) {
-        const int64_t kp = kk(mu - 1), nn = n[mu], sn = s[mu], sp = s[mu + 1], m = kp * nn;
-        for (int b = 0; b < count; ++b) {
-            Xm[b] = X[(size_t)b * d + mu];
-            Lc[b] = Lb + ((size_t)b * 2 + flip) * szL;
-            Ln[b] = Lb + ((size_t)b * 2 + (flip ^ 1)) * szL;
-        }
-        if (mu == 0) {
-            for (int b = 0; b < count; ++b) Tm[b] = Xm[b];
-        } else {
-            for (int b = 0; b < count; ++b) { Td[b] = mu == d - 1 ? cores_out[(size_t)b * d + mu] : Tb + (size_t)b * szT; Tm[b] = Td[b]; }
-            CK(prod(desc(kp, nn * sp, sn, 1, kp, nn * sp, 1), Lc, Xm, Td));                 // T[q, i, p'] = sum_p Lc[p, q] X[p, i, p']
-        }
-        if (mu == d - 1) {
-            if (mu == 0)
-                for (int b = 0; b < count; ++b)
-                    TTSK_HIP(hipMemcpyAsync(cores_out[(size_t)b * d], Xm[b], (size_t)nn * 8, hipMemcpyDeviceToDevice, st));
-            break;
-        }
-        const int64_t k = kk(mu);
-        for (int b = 0; b < count; ++b) { Q[b] = cores_out[(size_t)b * d + mu]; Wm[b] = W[(size_t)b * (d - 1) + mu]; }
-        CK(prod(desc(m, k, sp, sp, 1, k, 1), Tm, Wm, Q));                                     // M = T W
-        rc = qr_cholesky_batch(count, Q, m, (int)k, stream, st, qws, sticky);
-        if (rc < 0) return rc;
-        if (rc == 0) { set_error("ttsk_tt_orth_sketch_batch: batched QR outside its cover at mode %d", mu); return TTSK_ERR_UNSUPPORTED; }
-        {
-            const double *cq[16], *sprev[16];
-            double *sout[16];
+    const double *Tm[QR_BATCH_MAX], *Lc[QR_BATCH_MAX], *Xm[QR_BATCH_MAX], *Wm[QR_BATCH_MAX];
+    double *Ln[QR_BATCH_MAX], *Q[QR_BATCH_MAX], *Td[QR_BATCH_MAX];
+    auto modes = [&]() -> int {
+        int flip = 0;
+        for (int mu = 0; mu < d; ++mu) {
+            const int64_t kp = kk(mu - 1), nn = n[mu], sn = s[mu], sp = s[mu + 1], m = kp * nn;
             for (int b = 0; b < count; ++b) {
-                cq[b] = Q[b]; sprev[b] = mu > 0 ? Sg[(size_t)b * d + mu - 1] : nullptr; sout[b] = Sv(b, mu);
-                Sg[(size_t)b * d + mu] = sout[b];
+                Xm[b] = X[(size_t)b * d + mu];
+                Lc[b] = Lb + ((size_t)b * 2 + flip) * szL;
+                Ln[b] = Lb + ((size_t)b * 2 + (flip ^ 1)) * szL;
             }
-            CK(ttsk_stream_wait(aux, stream));                                               // the unsigned factors are there
-            rc = qr_signs_batch(count, cq, (int)k, m == k ? 1 : 0, mu > 0 ? sprev : nullptr, (int)nn, sout, st_aux);
+            if (mu == 0) {
+                for (int b = 0; b < count; ++b) Tm[b] = Xm[b];
+            } else {
+                for (int b = 0; b < count; ++b) { Td[b] = mu == d - 1 ? cores_out[(size_t)b * d + mu] : Tb + (size_t)b * szT; Tm[b] = Td[b]; }
+                // T[q, i, p'] = sum_p Lc[p, q] X[p, i, p']
+                CK(gemm_each(gemm_desc(kp, nn * sp, sn, 1, kp, nn * sp, 1), count, Lc, Xm, Td, stream, st));
+            }
+            if (mu == d - 1) {
+                if (mu == 0)
+                    for (int b = 0; b < count; ++b)
+                        TTSK_HIP(hipMemcpyAsync(cores_out[(size_t)b * d], Xm[b], (size_t)nn * 8, hipMemcpyDeviceToDevice, st));
+                break;
+            }
+            const int64_t k = kk(mu);
+            for (int b = 0; b < count; ++b) { Q[b] = cores_out[(size_t)b * d + mu]; Wm[b] = W[(size_t)b * (d - 1) + mu]; }
+            // M = T W
+            CK(gemm_each(gemm_desc(m, k, sp, sp, 1, k, 1), count, Tm, Wm, Q, stream, st));
+            rc = qr_cholesky_batch(count, Q, m, (int)k, stream, st, qws, sticky);
             if (rc < 0) return rc;
-            if (rc == 0) { set_error("ttsk_tt_orth_sketch_batch: batched sign reconstruction outside its cover"); return TTSK_ERR_UNSUPPORTED; }
+            if (rc == 0) return declined("qr_cholesky_batch");
+            {
+                const double *cq[QR_BATCH_MAX], *sprev[QR_BATCH_MAX];
+                double *sout[QR_BATCH_MAX];
+                for (int b = 0; b < count; ++b) {
+                    cq[b] = Q[b]; sprev[b] = mu > 0 ? Sg[(size_t)b * d + mu - 1] : nullptr; sout[b] = Sv(b, mu);
+                    Sg[(size_t)b * d + mu] = sout[b];
+                }
+                CK(ttsk_stream_wait(aux, stream));                                               // the unsigned factors are there
+                rc = qr_signs_batch(count, cq, (int)k, m == k ? 1 : 0, mu > 0 ? sprev : nullptr, (int)nn, sout, st_aux);
+                if (rc < 0) return rc;
+                if (rc == 0) return declined("qr_signs_batch");
+            }
+            {
+                const double *cq[QR_BATCH_MAX];
+                for (int b = 0; b < count; ++b) cq[b] = Q[b];
+                // next chain matrix Ln = T^T Q
+                CK(gemm_each(gemm_desc(sp, k, m, 1, sp, k, 1), count, Tm, cq, Ln, stream, st));
+            }
+            flip ^= 1;
+            CK(fix_cores(mu));                                                                     // the chain has read Q for the last time
         }
-        {
-            const double *cq[16];
-            for (int b = 0; b < count; ++b) cq[b] = Q[b];
-            CK(prod(desc(sp, k, m, 1, sp, k, 1), Tm, cq, Ln));                                // next chain matrix Ln = T^T Q
-        }
-        flip ^= 1;
-        CK(fix_cores(mu));                                                                     // the chain has read Q for the last time
-    }
-    CK(fix_cores(d - 1));
-    CK(ttsk_stream_wait(stream, aux));
+        CK(fix_cores(d - 1));
+        return TTSK_OK;
+    };
+    rc = modes();
+    const int joined = ttsk_stream_wait(stream, aux);            // aux (forked by the modes) joined on every exit, errors included
+    if (rc < 0) return rc;
+    CK(joined);
     if ((rc = launch(orth_spread_flag_kernel, dim3(1), dim3(64), 0, st, sticky, dev_status, count))) return rc;
 #undef CK
     return 1;
@@ -394,7 +378,7 @@ int ttsk_tt_orth_sketch_batch(int count, int d, const int64_t *n, const int64_t 
     TTSK_ARG(!DL || omega_out, "ttsk_tt_orth_sketch_batch: the orthogonal method needs omega_out");
     int rc = orth_batch_fused(count, d, n, s, lt, rt, X, DL, DR, cores_out, omega_out, dev_status, stream);
     if (rc == 1) return TTSK_OK;
-    if (rc < 0 && rc != TTSK_ERR_UNSUPPORTED) return rc;
+    if (rc < 0) return rc;
     // (outside the fused batch's cover: the tensors as concurrent chains, below)
     bool used[TTSK_NUM_STREAMS] = {};
     const int lanes = TTSK_NUM_STREAMS / 2;
@@ -487,12 +471,8 @@ int ttsk_tt_assemble(int d, const int64_t *n, const int64_t *lr, const int64_t *
                 A[b] = psi[G[b]]; B[b] = work[G[b]]; C[b] = cores_out[G[b]]; Om[b] = omega[G[b]];
                 R[b] = Rall + (size_t)b * m * r; Rc[b] = R[b];
             }
-            auto desc = [](int64_t M, int64_t N, int64_t K, double alpha, int acc) {
-                ttsk_gemm_desc g{};
-                g.batch = 1; g.M = M; g.N = N; g.Ko = 1; g.Ki = K;
-                g.a_m = K; g.a_ki = 1; g.b_ki = N; g.b_n = 1; g.c_m = N; g.c_n = 1; g.alpha = alpha; g.accumulate = acc;
-                return g;
-            };
+            // row-major operands: A (M x K), B (K x N)
+            auto desc = [](int64_t M, int64_t N, int64_t K, double alpha, int acc) { return gemm_desc(M, N, K, K, 1, N, 1, alpha, acc); };
             rc = skinny_try_batch(desc(m, l, r, 1.0, 0), nb, A, B, C, stream, st);                       // C = Psi P
             if (rc < 0) return rc;
             if (rc == 1) {
@@ -511,11 +491,11 @@ int ttsk_tt_assemble(int d, const int64_t *n, const int64_t *lr, const int64_t *
                 rc = skinny_try_batch(desc(m, r, l, -1.0, 1), nb, Cc, Om, R, stream, st);           // R = Psi - C Omega
                 if (rc < 0) return rc;
                 if (rc == 0)
-                    for (int b = 0; b < nb; ++b) CK(gemm2(m, r, l, C[b], l, 1, Om[b], r, 1, R[b], stream, -1.0, 1));
+                    for (int b = 0; b < nb; ++b) CK(gemm_plain(m, r, l, C[b], l, 1, Om[b], r, 1, R[b], stream, -1.0, 1));
                 rc = skinny_try_batch(desc(m, l, r, 1.0, 1), nb, Rc, B, C, stream, st);              // C += R P
                 if (rc < 0) return rc;
                 if (rc == 0)
-                    for (int b = 0; b < nb; ++b) CK(gemm2(m, l, r, R[b], r, 1, B[b], l, 1, C[b], stream, 1.0, 1));
+                    for (int b = 0; b < nb; ++b) CK(gemm_plain(m, l, r, R[b], r, 1, B[b], l, 1, C[b], stream, 1.0, 1));
             }
         }
     }
@@ -541,22 +521,22 @@ int ttsk_tt_assemble(int d, const int64_t *n, const int64_t *lr, const int64_t *
             // C_k[(a, i), b] = sum_c Psi_k[(a, i), c] P_k[c, b]
             const int64_t m = (k ? lr[k - 1] : 1) * n[k];
             TTSK_ARG(psi[k] && cores_out[k], "ttsk_tt_assemble: NULL core %d", k);
-            CK(gemm2(m, lr[k], rr[k], psi[k], rr[k], 1, work[k], lr[k], 1, cores_out[k], q));
+            CK(gemm_plain(m, lr[k], rr[k], psi[k], rr[k], 1, work[k], lr[k], 1, cores_out[k], q));
             double *R = (double *)scratch(q, SCRATCH_DRIVER, (size_t)m * rr[k] * 8);
             if (!R) return TTSK_ERR_HIP;
             TTSK_HIP(hipMemcpyAsync(R, psi[k], (size_t)m * rr[k] * 8, hipMemcpyDeviceToDevice, stream_of(q)));
-            CK(gemm2(m, rr[k], lr[k], cores_out[k], lr[k], 1, omega[k], rr[k], 1, R, q, -1.0, 1));       // R = Psi - C Omega
-            CK(gemm2(m, lr[k], rr[k], R, rr[k], 1, work[k], lr[k], 1, cores_out[k], q, 1.0, 1));         // C += R P
+            CK(gemm_plain(m, rr[k], lr[k], cores_out[k], lr[k], 1, omega[k], rr[k], 1, R, q, -1.0, 1));       // R = Psi - C Omega
+            CK(gemm_plain(m, lr[k], rr[k], R, rr[k], 1, work[k], lr[k], 1, cores_out[k], q, 1.0, 1));         // C += R P
         } else {
             // C_{k+1}[c, (i, b)] = sum_a P_k[c, a] Psi_{k+1}[a, (i, b)]
             const int64_t cols = n[k + 1] * (k + 1 < d - 1 ? rr[k + 1] : 1);
             TTSK_ARG(psi[k + 1] && cores_out[k + 1], "ttsk_tt_assemble: NULL core %d", k + 1);
-            CK(gemm2(rr[k], cols, lr[k], work[k], lr[k], 1, psi[k + 1], cols, 1, cores_out[k + 1], q));
+            CK(gemm_plain(rr[k], cols, lr[k], work[k], lr[k], 1, psi[k + 1], cols, 1, cores_out[k + 1], q));
             double *R = (double *)scratch(q, SCRATCH_DRIVER, (size_t)lr[k] * cols * 8);
             if (!R) return TTSK_ERR_HIP;
             TTSK_HIP(hipMemcpyAsync(R, psi[k + 1], (size_t)lr[k] * cols * 8, hipMemcpyDeviceToDevice, stream_of(q)));
-            CK(gemm2(lr[k], cols, rr[k], omega[k], rr[k], 1, cores_out[k + 1], cols, 1, R, q, -1.0, 1)); // R = Psi - Omega C
-            CK(gemm2(rr[k], cols, lr[k], work[k], lr[k], 1, R, cols, 1, cores_out[k + 1], q, 1.0, 1));   // C += P R
+            CK(gemm_plain(lr[k], cols, rr[k], omega[k], rr[k], 1, cores_out[k + 1], cols, 1, R, q, -1.0, 1)); // R = Psi - Omega C
+            CK(gemm_plain(rr[k], cols, lr[k], work[k], lr[k], 1, R, cols, 1, cores_out[k + 1], q, 1.0, 1));   // C += P R
         }
     }
     const int e = direction == 0 ? d - 1 : 0;                                   // the core that is copied
