@@ -4,19 +4,19 @@
 
 namespace ttsk {
 
-int launch_chain_step_a(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, size_t lds, int grid, hipStream_t st);
-int launch_chain_step_b(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, size_t lds, int grid, hipStream_t st);
-int launch_chain_step_c(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, size_t lds, int grid, hipStream_t st);
-int launch_chain_step_d(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, size_t lds, int grid, hipStream_t st);
-int launch_chain_step_e(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, size_t lds, int grid, hipStream_t st);
+int launch_chain_step_a(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, int waves, size_t lds, int grid, hipStream_t st);
+int launch_chain_step_b(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, int waves, size_t lds, int grid, hipStream_t st);
+int launch_chain_step_c(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, int waves, size_t lds, int grid, hipStream_t st);
+int launch_chain_step_d(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, int waves, size_t lds, int grid, hipStream_t st);
+int launch_chain_step_e(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, int waves, size_t lds, int grid, hipStream_t st);
 
-static int launch_chain_step(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, size_t lds, int grid, hipStream_t st)
+static int launch_chain_step(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, int waves, size_t lds, int grid, hipStream_t st)
 {
-    if (nf <= 2) return launch_chain_step_a(a, nf, str, wt, ebuf, unr, lds, grid, st);
-    if (nf <= 4) return launch_chain_step_b(a, nf, str, wt, ebuf, unr, lds, grid, st);
-    if (nf == 5) return launch_chain_step_c(a, nf, str, wt, ebuf, unr, lds, grid, st);
-    if (nf == 6) return launch_chain_step_d(a, nf, str, wt, ebuf, unr, lds, grid, st);
-    return launch_chain_step_e(a, nf, str, wt, ebuf, unr, lds, grid, st);
+    if (nf <= 2) return launch_chain_step_a(a, nf, str, wt, ebuf, unr, waves, lds, grid, st);
+    if (nf <= 4) return launch_chain_step_b(a, nf, str, wt, ebuf, unr, waves, lds, grid, st);
+    if (nf == 5) return launch_chain_step_c(a, nf, str, wt, ebuf, unr, waves, lds, grid, st);
+    if (nf == 6) return launch_chain_step_d(a, nf, str, wt, ebuf, unr, waves, lds, grid, st);
+    return launch_chain_step_e(a, nf, str, wt, ebuf, unr, waves, lds, grid, st);
 }
 
 static int cf_num_cu()
@@ -92,6 +92,21 @@ int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool for
     if (wpp > c.n) wpp = c.n;
     // (one slice per workgroup -- a single tensor -- still beats the two-launch form: 313 vs 355 us per C3 sketch)
     a.wpp = wpp;
+    // the deal of (row tile, range of DRM-rank tiles) pieces over the waves (chain_deal.h): up to 4 row tiles one
+    // wave per row tile, beyond that 12 waves that read their piece from the table.  A levelled workgroup pays for the
+    // pairing of its cut row tiles (a barrier and a round trip through the slab) once, about 4 us per launch measured on
+    // single sketches, and gains about 3 us per slice at rank 100: it is dealt from two slices per workgroup on.
+    const ChainDeal deal = chain_deal(c.J, c.A, c.A2, nq, sq, nn, sn, KB1, c.n >= 2 * wpp);
+    if (deal.waves == CD_WAVES) {
+        bool taken[CD_WAVES] = {};
+        for (int i = 0; i < deal.npieces; ++i) taken[deal.piece[i].slot] = true;
+        for (int s = 0; s < CD_WAVES; ++s)                               // the last wave and every other one without a piece
+            if (!taken[s]) a.piece[s] = (unsigned)a.nload++ << 8 | (unsigned)CD_NONE << 16;
+        for (int i = 0; i < deal.npieces; ++i) {
+            const ChainPiece &p = deal.piece[i];
+            a.piece[p.slot] = (unsigned)p.tile | (unsigned)p.q0 << 8 | (unsigned)p.kind << 16;
+        }
+    }
     a.xcd_map = (wpp % 8 == 0 && wpp >= 8) ? 1 : 0;
     for (int b = 0; b < c.nb; ++b) {
         if ((uintptr_t)c.X[b] & 7) return 0;
@@ -113,22 +128,22 @@ int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool for
 #endif
     long long *stamps_dev = nullptr;
     if (stamps_on) {
-        if (hipMalloc(&stamps_dev, 8 * 8 * 8 * 8) != hipSuccess) return TTSK_ERR_HIP;
-        (void)hipMemset(stamps_dev, 0, 8 * 8 * 8 * 8);
+        if (hipMalloc(&stamps_dev, 8 * CD_WAVES * 8 * 8) != hipSuccess) return TTSK_ERR_HIP;
+        (void)hipMemset(stamps_dev, 0, 8 * CD_WAVES * 8 * 8);
         a.stamps = stamps_dev;
     }
-    int rc = launch_chain_step(a, nq, sq, wt, ebuf, unr, lds, (int)nslab, st);
+    int rc = launch_chain_step(a, nq, sq, wt, ebuf, unr, deal.waves, lds, (int)nslab, st);
     if (stamps_on) {
-        long long h[8 * 8 * 8];
+        long long h[8 * CD_WAVES * 8];
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(h, stamps_dev, sizeof(h), hipMemcpyDeviceToHost);
         (void)hipFree(stamps_dev);
         long long t0 = 0;
-        for (int i = 0; i < 8 * 8 * 8; ++i) if (h[i] && (!t0 || h[i] < t0)) t0 = h[i];
+        for (int i = 0; i < 8 * CD_WAVES * 8; ++i) if (h[i] && (!t0 || h[i] < t0)) t0 = h[i];
         fprintf(stderr, "[cf stamps] workgroup 0: cycles since its first stamp; per slice, wave: start | endA | afterB1 | endB | afterB2\n");
         for (int sl = 0; sl < 4; ++sl)
-            for (int w = 0; w < 8; ++w) {
-                const long long *r = h + (sl * 8 + w) * 8;
+            for (int w = 0; w < CD_WAVES; ++w) {
+                const long long *r = h + (sl * CD_WAVES + w) * 8;
                 if (!r[1] && !r[4]) continue;
                 fprintf(stderr, "  slice %d wave %d: %8lld %8lld %8lld %8lld %8lld\n", sl, w, r[0] ? r[0] - t0 : -1, r[1] - t0, r[2] - t0,
                         r[3] - t0, r[4] - t0);

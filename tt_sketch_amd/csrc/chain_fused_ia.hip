@@ -4,7 +4,7 @@
 
 namespace ttsk {
 
-int launch_chain_step_a(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, size_t lds, int grid, hipStream_t st)
+int launch_chain_step_a(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, int waves, size_t lds, int grid, hipStream_t st)
 {
     TTSK_CF_CASE(1, 0, 2)
     TTSK_CF_CASE(1, 1, 2)

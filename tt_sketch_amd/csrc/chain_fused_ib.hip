@@ -4,7 +4,7 @@
 
 namespace ttsk {
 
-int launch_chain_step_b(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, size_t lds, int grid, hipStream_t st)
+int launch_chain_step_b(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, int waves, size_t lds, int grid, hipStream_t st)
 {
     TTSK_CF_CASE(3, 0, 2)
     TTSK_CF_CASE(3, 1, 2)

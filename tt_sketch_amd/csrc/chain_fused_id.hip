@@ -4,7 +4,7 @@
 
 namespace ttsk {
 
-int launch_chain_step_d(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, size_t lds, int grid, hipStream_t st)
+int launch_chain_step_d(const ChainStep &a, int nf, int str, bool wt, int ebuf, int unr, int waves, size_t lds, int grid, hipStream_t st)
 {
     TTSK_CF_CASE(6, 0, 1)
     TTSK_CF_CASE(6, 1, 1)
