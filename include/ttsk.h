@@ -257,6 +257,30 @@ int ttsk_sparse_psi(const double *dev_val, const int64_t *dev_idx_row, const int
                     const double *dev_Lv, int64_t l, const double *dev_Rv, int64_t r,
                     int64_t n, double *dev_psi, int stream);
 
+/* ---- evaluation at index lists (csrc/tt_gather.hip) --------------------------
+ * TensorTrain.gather (tensor.py:414-440): per index tuple e the chain
+ *   t_e = G_0[0, i_0(e), :] G_1[:, i_1(e), :] ... G_{d-1}[:, i_{d-1}(e), 0]
+ * with all d modes in one launch and the running vector kept on chip (no (N x rank) panel in HBM).
+ *   dev_cores[k]  (ranks[k], shape[k], ranks[k + 1]) contiguous, ranks[0] = ranks[d] = 1
+ *   dev_idx       int64 index matrix: mode k of tuple e at dev_idx[row_order[k] * row_stride + e] (row_order NULL:
+ *                 identity), the addressing of ttsk_sparse_densedrm_gather -- a SparseTensor and its .T are read in place
+ *   dev_val       (N,) entries, or NULL
+ *   dev_out       (N,) receives t in input order, or NULL
+ *   dev_stats     3 doubles, or NULL: sum_e x_e t_e (SparseTensor.dot, tensor.py:250-255), sum_e t_e^2 and
+ *                 sum_e (t_e - x_e)^2 (the sampled error of scripts/frostt.py:112-116 over all of the list); needs dev_val.
+ *                 Summed in a fixed order (per-workgroup partial sums, then one workgroup): the same bits on every
+ *                 call, with or without dev_out.
+ * TTSK_ERR_ARG: NULL cores / indices, d < 1, ranks[0] or ranks[d] != 1, dev_out and dev_stats both NULL, dev_stats
+ * without dev_val.  TTSK_ERR_UNSUPPORTED before anything is launched: d > 32, a rank beyond 256, a mode of 2^31 or more. */
+int ttsk_tt_gather(const double *const *dev_cores, const int64_t *ranks /* d + 1 */, const int64_t *shape, int d,
+                   const int64_t *dev_idx, int64_t row_stride, const int *row_order, size_t N,
+                   const double *dev_val, double *dev_out, double *dev_stats /* 3 doubles */, int stream);
+/* CPTensor.gather (tensor.py:726-732): t_e = sum_rho prod_k A_k[i_k(e), rho], dev_factors[k] (shape[k], rank) contiguous;
+ * indices, outputs, statistics and errors as above (any rank >= 1 is covered). */
+int ttsk_cp_gather(const double *const *dev_factors, int64_t rank, const int64_t *shape, int d,
+                   const int64_t *dev_idx, int64_t row_stride, const int *row_order, size_t N,
+                   const double *dev_val, double *dev_out, double *dev_stats, int stream);
+
 /* ---- SparseTensor x SparseGaussianDRM without (nnz x rank) panels (csrc/sparse_fused.hip) ----
  * sparse_gaussian_drm.py:29-44 + sparse_sketch.py:8-69 as one pass per mode over a resident, mode-ordered stream. */
 /* multipliers of the Fortran-order flat index of fast_lazy_gaussian.pyx:60-71 incl. its 32-bit running product (host) */

@@ -319,6 +319,12 @@ class SketchedTensorTrain(Tensor):
     def dot(self, other: Tensor, reverse=False) -> float:
         return self.to_tt().dot(other, reverse)
 
+    def gather(self, idx):
+        return self.to_tt().gather(idx)
+
+    def support_error(self, sparse, relative: bool = False) -> float:
+        return self.to_tt().support_error(sparse, relative)
+
 
 def _blocked_stream_sketch_components(tensor, left_drm, right_drm, left_rank_slices,
                                       right_rank_slices, excluded_entries=None) -> BlockedSketch:

@@ -9,7 +9,9 @@ strided views, so a right sketch (drm_base.py:122-145 in the reference transpose
 the tensor on every call) costs no copy and no PCIe traffic.
 
 The arithmetic helpers (``error``, ``norm``, ``dot``, ``round``, ...) are off the hot
-path and stay plain NumPy on the host.
+path and stay plain NumPy on the host; the steps that follow
+``to_tt()`` have device forms beside them (``round_dev``, ``orthogonalize_dev``, resident ``dot`` /
+``norm``, and the evaluation at index lists: ``gather_dev``, ``support_error``, ``SparseTensor.dot``).
 
 Residency contract: payload arrays are treated as immutable once a tensor has been
 sketched; replace a core (``tt[i] = new``) rather than writing into it, or call
@@ -36,6 +38,107 @@ def _same_objects(key, items) -> bool:
     """The cached device copies belong to exactly these payload objects (identity, not id(): the id of
     a collected array can be handed to a new one)."""
     return key is not None and len(key) == len(items) and all(a is b for a, b in zip(key, items))
+
+
+# ------------------------------------------------------------------ evaluation at index lists (csrc/tt_gather.hip)
+_GATHER_PANEL_BYTES = 256 << 20      # composed fallback: the two (chunk x rank) panels of a step stay below this
+
+
+def _gather_indices(idx, shape):
+    """The index argument of ``gather_dev`` as (device index matrix, row stride, row order, N, device entries or None).
+    A ``SparseTensor`` is read in place (``.T`` views through their row order); host arrays are checked against
+    ``shape`` here, before anything is uploaded."""
+    d = len(shape)
+    if isinstance(idx, SparseTensor):
+        if tuple(idx.shape) != tuple(shape):
+            raise ValueError(f"gather: index tensor of shape {idx.shape}, tensor of shape {tuple(shape)}")
+        return idx.dev_indices(), idx.nnz, tuple(idx.dev_row_order), idx.nnz, idx.dev_entries()
+    arr = np.stack(idx) if isinstance(idx, (tuple, list)) else np.asarray(idx)
+    if arr.ndim != 2 or arr.shape[0] != d:
+        raise ValueError(f"gather: {d} index rows expected, got an array of shape {arr.shape}")
+    arr = np.ascontiguousarray(arr, dtype=np.int64)
+    if arr.size and (arr.min() < 0 or (arr.max(axis=1) >= np.asarray(shape, dtype=np.int64)).any()):
+        raise IndexError(f"gather: an index lies outside the shape {tuple(shape)}")
+    return DevArray.from_host(arr, dtype=np.int64), arr.shape[1], tuple(range(d)), arr.shape[1], None
+
+
+def _tt_gather_composed(cores, dev_idx, stride, order, N, val, want_out, want_stats):
+    """The chain from ``ttsk_sparse_ttdrm_step``, mode by mode, for ranks beyond the fused kernel's cover: chunks of the
+    list small enough for the panel budget, the statistics from device products summed over the chunks in order."""
+    import ctypes
+    from . import _native as nat
+    widest = max(max(c.shape[0], c.shape[2]) for c in cores)
+    chunk = max(1, _GATHER_PANEL_BYTES // (16 * widest))
+    out = DevArray.empty((N,)) if want_out else None
+    stats = np.zeros(3) if want_stats else None
+    for lo in range(0, N, chunk):
+        m = min(chunk, N - lo)
+        v = None
+        for k, c in enumerate(cores):
+            rho, n, rhop = c.shape
+            nxt = DevArray.empty((m, rhop))
+            nat.call("ttsk_sparse_ttdrm_step", None if v is None else ctypes.c_void_p(v.ptr), rho, ctypes.c_void_p(c.ptr),
+                     n, rhop, ctypes.c_void_p(dev_idx.ptr + (order[k] * stride + lo) * 8), ctypes.c_size_t(m),
+                     ctypes.c_void_p(nxt.ptr), 0)
+            v = nxt
+        if want_out:
+            copy_into(out[lo:lo + m], v.reshape(m))
+        if want_stats:
+            x = val[lo:lo + m].reshape(m, 1)
+            res = v.copy()
+            axpby(res, x, -1.0, 1.0)                                   # t - x
+            for j, (a, b) in enumerate(((x, v), (v, v), (res, res))):
+                stats[j] += float(contract("ka,kb->ab", a, b).get()[0, 0])
+    return out, stats
+
+
+def _gather_device(tensor, idx, want_out: bool, want_stats: bool):
+    """One pass of ``ttsk_tt_gather`` / ``ttsk_cp_gather`` over an index list: (DevArray (N,) or None, the three sums
+    (x . t, t . t, |t - x|^2) as a host array or None).  Nothing of the tensor or the list is downloaded."""
+    import ctypes
+    from . import _native as nat
+    dev_idx, stride, order, N, val = _gather_indices(idx, tensor.shape)
+    if want_stats and val is None:
+        raise ValueError("gather: the sums need the entries of a SparseTensor")
+    d = tensor.ndim
+    cores = [c.contiguous() for c in tensor.dev_cores()]
+    out = DevArray.empty((N,)) if want_out else None
+    stats = DevArray.empty((3,)) if want_stats else None
+    ptr = lambda a: None if a is None else ctypes.c_void_p(a.ptr)
+    tail = (ptr(dev_idx), stride, (ctypes.c_int * d)(*order), ctypes.c_size_t(N), ptr(val) if want_stats else None,
+            ptr(out), ptr(stats), 0)
+    cptr = (ctypes.c_void_p * d)(*[c.ptr for c in cores])
+    shape = (ctypes.c_int64 * d)(*tensor.shape)
+    if isinstance(tensor, TensorTrain):
+        ranks = (ctypes.c_int64 * (d + 1))(*([c.shape[0] for c in cores] + [cores[-1].shape[2]]))
+        try:
+            nat.call("ttsk_tt_gather", cptr, ranks, shape, d, *tail)
+        except nat.TtskUnsupported:
+            return _tt_gather_composed(cores, dev_idx, stride, order, N, val, want_out, want_stats)
+    else:
+        nat.call("ttsk_cp_gather", cptr, tensor.rank, shape, d, *tail)
+    return out, (stats.get() if want_stats else None)
+
+
+class _GatherOnDevice:
+    """``gather_dev`` / ``support_error`` of the formats with a gather kernel (TensorTrain, CPTensor)."""
+
+    def gather_dev(self, idx) -> DevArray:
+        """Entries at the given multi-indices as a device array (N,): ``idx`` is a ``SparseTensor`` of this shape (its
+        resident index matrix is used in place), a ``(d, N)`` array or a tuple of ``d`` arrays."""
+        return _gather_device(self, idx, True, False)[0]
+
+    def support_error(self, sparse: "SparseTensor", relative: bool = False) -> float:
+        """``|| self[indices] - entries ||`` over ALL nonzeros of ``sparse`` in one device pass (the figure the
+        reference's scripts/frostt.py:112-116 forms on a sample of 10^4); exact where ``error(fast=True)`` has lost
+        everything below 1e-8.  ``relative``: divided by ``||entries||``."""
+        err = float(np.sqrt(_gather_device(self, sparse, False, True)[1][2]))
+        if relative:
+            ref = sparse.norm()
+            if ref == 0:
+                return np.inf
+            err /= ref
+        return err
 
 
 class Tensor(abc.ABC):
@@ -267,6 +370,8 @@ class SparseTensor(Tensor):
         return float(np.linalg.norm(self.entries))
 
     def dot(self, other, reverse=False) -> float:
+        if isinstance(other, _GatherOnDevice) and (other.resident() or self._dev is not None):
+            return float(_gather_device(other, self, False, True)[1][0])      # one pass, no (N,) vector
         if hasattr(other, "gather"):
             return float(np.dot(other.gather(self.indices), self.entries))
         return super().dot(other, reverse=reverse)
@@ -296,7 +401,7 @@ class SparseTensor(Tensor):
 
 
 # --------------------------------------------------------------------------- TT
-class TensorTrain(Tensor):
+class TensorTrain(_GatherOnDevice, Tensor):
     """Tensor train with cores ``(r_{k-1}, n_k, r_k)`` (reference tensor.py:294-609)."""
 
     def __init__(self, cores: ArrayList, _dev=None) -> None:
@@ -387,7 +492,10 @@ class TensorTrain(Tensor):
         self.invalidate_device()
 
     def gather(self, idx) -> npt.NDArray:
-        """Entries at the given multi-indices (rows of ``idx`` are modes)."""
+        """Entries at the given multi-indices (rows of ``idx`` are modes).  On the device (``gather_dev``) for a
+        resident train or a ``SparseTensor`` of indices; host NumPy otherwise."""
+        if self.resident() or isinstance(idx, SparseTensor):
+            return self.gather_dev(idx).get()
         idx = np.stack(idx) if not isinstance(idx, np.ndarray) else idx
         cs = [_host(c) for c in self.cores]
         acc = cs[0][0][idx[0]]                       # (N, r1)
@@ -680,7 +788,7 @@ class TensorSum(Tensor):
 
 
 # --------------------------------------------------------------------------- CP
-class CPTensor(Tensor):
+class CPTensor(_GatherOnDevice, Tensor):
     """CP format, factor matrices ``(n_k, R)`` (reference tensor.py:674-743)."""
 
     def __init__(self, cores: ArrayList, _dev=None) -> None:
@@ -728,7 +836,15 @@ class CPTensor(Tensor):
         self.cores[k] = data
         self.invalidate_device()
 
+    def resident(self) -> bool:
+        """True if the factor matrices live in HBM only."""
+        return all(isinstance(c, DevArray) for c in self.cores)
+
     def gather(self, idx) -> npt.NDArray:
+        """Entries at the given multi-indices; on the device (``gather_dev``) for device factors or a ``SparseTensor``
+        of indices, host NumPy otherwise."""
+        if self.resident() or isinstance(idx, SparseTensor):
+            return self.gather_dev(idx).get()
         acc = 1.0
         for C, rows in zip(self.cores, idx):
             acc = acc * _host(C)[rows]
