@@ -281,6 +281,25 @@ int ttsk_cp_gather(const double *const *dev_factors, int64_t rank, const int64_t
                    const int64_t *dev_idx, int64_t row_stride, const int *row_order, size_t N,
                    const double *dev_val, double *dev_out, double *dev_stats, int stream);
 
+/* ---- a tensor train against a dense tensor (csrc/tt_dense_stats.hip) ----------
+ * Tensor.error / dot / norm for a DenseTensor argument (tensor.py:53-88) and TensorTrain.dense in one pass over the
+ * tensor.  The train is cut at a bond: T^{<k>} = L R, dev_L (M x rho) and dev_R (rho x N) row-major and contiguous.
+ *   dev_x      (M x N) row-major, or NULL (read as zeros)
+ *   dev_out    (M x N) row-major, receives T, or NULL: the reconstruction is then never stored
+ *   dev_stats  4 doubles, or NULL: sum x t, sum t^2, sum (t - x)^2, sum x^2.  Per-workgroup partial sums, then one
+ *              workgroup, in an order that depends on M and N alone: the same bits on every call, with or without dev_out.
+ * Any M, N, rho >= 1.  TTSK_ERR_ARG: a non-positive extent, a NULL factor, a row stride below N.  TTSK_ERR_UNSUPPORTED:
+ * dev_out and dev_stats both NULL. */
+int ttsk_tt_dense_stats(const double *dev_L, int64_t M, const double *dev_R, int64_t N, int64_t rho,
+                        const double *dev_x, double *dev_out, double *dev_stats /* 4 doubles */, int stream);
+/* the same on a block of columns of a wider array: rows of dev_x / dev_out are ld_x / ld_out numbers apart (the slab of
+ * one range of a mode's values), and with accumulate != 0 the four sums are added to what dev_stats holds */
+int ttsk_tt_dense_stats_ld(const double *dev_L, int64_t M, const double *dev_R, int64_t N, int64_t rho,
+                           const double *dev_x, int64_t ld_x, double *dev_out, int64_t ld_out, double *dev_stats,
+                           int accumulate, int stream);
+/* dev_out[0] = sum_i x_i^2 (DenseTensor.norm of a device tensor), the same two-stage, atomic-free form; n = 0 gives 0 */
+int ttsk_sumsq(const double *dev_x, size_t n, double *dev_out, int stream);
+
 /* ---- SparseTensor x SparseGaussianDRM without (nnz x rank) panels (csrc/sparse_fused.hip) ----
  * sparse_gaussian_drm.py:29-44 + sparse_sketch.py:8-69 as one pass per mode over a resident, mode-ordered stream. */
 /* multipliers of the Fortran-order flat index of fast_lazy_gaussian.pyx:60-71 incl. its 32-bit running product (host) */

@@ -84,6 +84,9 @@ def _bind(lib):
         "ttsk_sparse_psi": [P, P, P, S, P, c_int64, P, c_int64, c_int64, P, I],
         "ttsk_tt_gather": [POINTER(P), POINTER(c_int64), POINTER(c_int64), I, P, c_int64, POINTER(I), S, P, P, P, I],
         "ttsk_cp_gather": [POINTER(P), c_int64, POINTER(c_int64), I, P, c_int64, POINTER(I), S, P, P, P, I],
+        "ttsk_tt_dense_stats": [P, c_int64, P, c_int64, c_int64, P, P, P, I],
+        "ttsk_tt_dense_stats_ld": [P, c_int64, P, c_int64, c_int64, P, c_int64, P, c_int64, P, I, I],
+        "ttsk_sumsq": [P, S, P, I],
         "ttsk_sparse_normal_table": [POINTER(c_uint64), I, I, I, c_uint64, P, I],
         "ttsk_sparse_sign_table": [POINTER(c_uint64), I, I, I, I, I, c_uint64, P, I],
         "ttsk_sparse_flat_mult": [POINTER(c_uint64), I, POINTER(c_uint64)],
@@ -166,6 +169,7 @@ _STREAM_LAST = frozenset((
     "ttsk_memset", "ttsk_d2d", "ttsk_gemm", "ttsk_copy_strided", "ttsk_axpby", "ttsk_sum_slices",
     "ttsk_tt_sketch", "ttsk_tt_sketch_batch", "ttsk_tt_sketch_sum", "ttsk_chain_step", "ttsk_chain_step_wide", "ttsk_sparse_normal_dev", "ttsk_sparse_sign_dev",
     "ttsk_fill_normal", "ttsk_fill_normal_many", "ttsk_sparse_ttdrm_step", "ttsk_sparse_densedrm_gather", "ttsk_sparse_psi", "ttsk_tt_gather", "ttsk_cp_gather",
+    "ttsk_tt_dense_stats", "ttsk_tt_dense_stats_ld", "ttsk_sumsq",
     "ttsk_sparse_sort_mode", "ttsk_sparse_normal_table", "ttsk_sparse_sign_table", "ttsk_sparse_mode_order", "ttsk_sparse_mode_stream", "ttsk_sparse_mode_stream_u32", "ttsk_sparse_gauss_pass", "ttsk_sparse_gauss_pass_u32", "ttsk_pinv", "ttsk_pinv_begin", "ttsk_pinv_end", "ttsk_triu", "ttsk_svd_small",
     "ttsk_qr_thin", "ttsk_orth_step", "ttsk_orth_step_pinv", "ttsk_pinv_batch_deferred", "ttsk_pinv_batch", "ttsk_dense_first_pass", "ttsk_tt_orth_sketch", "ttsk_tt_orth_sketch_batch", "ttsk_tt_assemble", "ttsk_tt_assemble_batch", "ttsk_comm_allreduce_sum", "ttsk_comm_reduce_sum", "ttsk_comm_allgather", "ttsk_comm_allreduce_max", "ttsk_graph_launch", "ttsk_timer_start"))
 _BLOCKING = frozenset(("ttsk_h2d", "ttsk_d2h"))          # return only after their stream has drained

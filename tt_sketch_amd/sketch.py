@@ -22,7 +22,7 @@ from .sketch_container import SketchContainer
 from .sketch_dispatch import SketchMethod, general_sketch
 from .sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchSparse,
                                                  CansketchTT)
-from .tensor import Tensor, TensorTrain
+from .tensor import DenseTensor, Tensor, TensorTrain
 from .utils import ArrayList, TTRank, pinv_dev_many, process_tt_rank, refine_left, refine_right
 
 DEFAULT_DRM = {
@@ -318,6 +318,12 @@ class SketchedTensorTrain(Tensor):
 
     def dot(self, other: Tensor, reverse=False) -> float:
         return self.to_tt().dot(other, reverse)
+
+    def error(self, other, relative: bool = False, rmse: bool = False, fast: bool = False) -> float:
+        """Against a dense tensor: the assembled (device-resident) train's one-pass error; anything else as before."""
+        if isinstance(other, (DenseTensor, np.ndarray)):
+            return self.to_tt().error(other, relative=relative, rmse=rmse, fast=fast)
+        return super().error(other, relative=relative, rmse=rmse, fast=fast)
 
     def gather(self, idx):
         return self.to_tt().gather(idx)

@@ -11,7 +11,8 @@ the tensor on every call) costs no copy and no PCIe traffic.
 The arithmetic helpers (``error``, ``norm``, ``dot``, ``round``, ...) are off the hot
 path and stay plain NumPy on the host; the steps that follow
 ``to_tt()`` have device forms beside them (``round_dev``, ``orthogonalize_dev``, resident ``dot`` /
-``norm``, and the evaluation at index lists: ``gather_dev``, ``support_error``, ``SparseTensor.dot``).
+``norm``, the evaluation at index lists: ``gather_dev``, ``support_error``, ``SparseTensor.dot``, and the pass over a
+dense tensor: ``dense_stats``, ``to_dense_dev`` and with them ``error`` / ``dot`` against a ``DenseTensor``).
 
 Residency contract: payload arrays are treated as immutable once a tensor has been
 sketched; replace a core (``tt[i] = new``) rather than writing into it, or call
@@ -117,6 +118,115 @@ def _gather_device(tensor, idx, want_out: bool, want_stats: bool):
             return _tt_gather_composed(cores, dev_idx, stride, order, N, val, want_out, want_stats)
     else:
         nat.call("ttsk_cp_gather", cptr, tensor.rank, shape, d, *tail)
+    return out, (stats.get() if want_stats else None)
+
+
+# ------------------------------------------------------------------ a train against a dense tensor (csrc/tt_dense_stats.hip)
+def _dense_split(shape, ranks, budget_bytes: int = _GATHER_PANEL_BYTES) -> dict:
+    """Where to cut a train of the given ``shape`` and bond ``ranks`` (d - 1 of them) for the pass over a dense tensor:
+    ``T^{<k>} = L R`` with L (M x rho) the modes before bond ``k`` and R (rho x N) the rest, ``k`` minimising
+    ``(M + N) rho`` (the numbers that must exist beside the tensor; the first such bond on a tie).  If the two panels
+    exceed ``budget_bytes`` the right group is cut into slabs of its leading mode k: for the values ``[j0, j1)`` of that
+    mode ``R_J = G_k[:, j0:j1, :] R'`` with ``R' = G_{k+1} ... G_{d-1}``, and the plan keeps
+    ``8 (M rho + (j1 - j0) N' rho + rho' N')`` under the budget (``N' = N / n_k``).  Pure arithmetic, no device call.
+    Returns ``dict(k, M, N, rho, slabs)``, ``slabs`` the list of ``(j0, j1)`` (one entry covering the mode: no slabbing)."""
+    shape = tuple(int(n) for n in shape)
+    d = len(shape)
+    rk = (1,) + tuple(int(r) for r in ranks) + (1,)
+    if d < 1 or len(rk) != d + 1 or min(shape) < 1 or min(rk) < 1:
+        raise ValueError(f"_dense_split: shape {shape} with bond ranks {tuple(ranks)}")
+    best = None
+    for k in (range(1, d) if d > 1 else (0,)):
+        M, N = _prod(shape[:k]), _prod(shape[k:])
+        cost = (M + N) * rk[k]
+        if best is None or cost < best[0]:
+            best = (cost, k, M, N)
+    cost, k, M, N = best
+    rho, n_k = rk[k], shape[k]
+    plan = dict(k=k, M=M, N=N, rho=rho, slabs=[(0, n_k)])
+    if 8 * cost <= budget_bytes:
+        return plan
+    Np = N // n_k
+    fixed, per = 8 * (M * rho + rk[k + 1] * Np), 8 * Np * rho
+    width = (budget_bytes - fixed) // per if budget_bytes > fixed else 0
+    if width < 1:
+        raise ValueError(f"_dense_split: a train of shape {shape} and ranks {rk[1:-1]} cut at bond {k} needs "
+                         f"{fixed + per} bytes of panels (L {M} x {rho}, one slice of R {rho} x {Np}, R' {rk[k + 1]} x {Np}) "
+                         f"for a single value of mode {k}: above the budget of {budget_bytes} bytes")
+    width = min(width, n_k)
+    plan["slabs"] = [(j, min(j + width, n_k)) for j in range(0, n_k, width)]
+    return plan
+
+
+def _prod(xs) -> int:
+    out = 1
+    for x in xs:
+        out *= int(x)
+    return out
+
+
+def _dense_current(dense: "DenseTensor") -> bool:
+    """The dense tensor lives on the device, or has an upload that is still current."""
+    return isinstance(dense.data, DevArray) or (dense._dev is not None and dense._dev_src is dense.data)
+
+
+def _dense_operand(X, shape):
+    """The dense argument of ``dense_stats`` as (C-contiguous DevArray, transposed): checked against ``shape`` before
+    anything touches the device.  A ``.T`` view of a contiguous buffer is returned as that buffer with ``transposed``
+    set (the caller runs its own ``.T`` against it: no copy); any other layout is copied once."""
+    if isinstance(X, np.ndarray):
+        X = DenseTensor(X)
+    if not isinstance(X, DenseTensor):
+        raise TypeError(f"dense_stats: a DenseTensor or an ndarray expected, got {type(X).__name__}")
+    if tuple(X.shape) != tuple(shape):
+        raise ValueError(f"dense_stats: dense tensor of shape {tuple(X.shape)}, tensor train of shape {tuple(shape)}")
+    if np.dtype(X.data.dtype) != np.float64:
+        raise TypeError(f"dense_stats: float64 data expected, got {X.data.dtype}")
+    arr = X.dev_data()
+    if arr.is_contiguous():
+        return arr, False
+    if arr.T.is_contiguous():
+        return arr.T, True
+    return arr.contiguous(), False
+
+
+def _core_chain(cores, from_right: bool) -> DevArray:
+    """The product of consecutive cores as one (r_first, n ... n, r_last) array, built from the cheap end."""
+    if from_right:
+        acc = cores[-1]
+        for c in cores[-2::-1]:
+            acc = contract("ajb,bm->ajm", c, acc.reshape(acc.shape[0], -1)).reshape(c.shape[0], -1, acc.shape[2])
+        return acc
+    acc = cores[0]
+    for c in cores[1:]:
+        acc = contract("mb,bjc->mjc", acc.reshape(-1, acc.shape[2]), c).reshape(acc.shape[0], -1, c.shape[2])
+    return acc
+
+
+def _tt_dense_pass(tt: "TensorTrain", X: Optional[DevArray], want_out: bool, want_stats: bool):
+    """``ttsk_tt_dense_stats`` over the whole tensor: (DevArray of ``tt.shape`` or None, the four sums ``x . t``,
+    ``t . t``, ``|t - x|^2``, ``x . x`` as a host array or None).  ``X``: C-contiguous device array of ``tt.shape``, or
+    None.  Slabs (``_dense_split``) are passed in order and their sums added on the device."""
+    import ctypes
+    from . import _native as nat
+    plan = _dense_split(tt.shape, tt.rank, _GATHER_PANEL_BYTES)
+    k, M, N, rho, slabs = plan["k"], plan["M"], plan["N"], plan["rho"], plan["slabs"]
+    cores = [c.contiguous() for c in tt.dev_cores()]                # a .T train holds transposed views
+    one = lambda: DevArray.from_host(np.ones((1, 1)))
+    L = _core_chain(cores[:k], False).contiguous().reshape(M, rho) if k else one()
+    out = DevArray.empty(tt.shape) if want_out else None
+    stats = DevArray.empty((4,)) if want_stats else None
+    ptr = lambda a, off=0: None if a is None else ctypes.c_void_p(a.ptr + 8 * off)
+    if len(slabs) == 1:
+        R = _core_chain(cores[k:], True).contiguous().reshape(rho, N)
+        nat.call("ttsk_tt_dense_stats", ptr(L), M, ptr(R), N, rho, ptr(X), ptr(out), ptr(stats), 0)
+    else:
+        Np = N // tt.shape[k]
+        Rp = _core_chain(cores[k + 1:], True).contiguous().reshape(-1, Np) if k + 1 < tt.ndim else one()
+        for i, (j0, j1) in enumerate(slabs):
+            RJ = contract("ajb,bn->ajn", cores[k][:, j0:j1, :], Rp)
+            nat.call("ttsk_tt_dense_stats_ld", ptr(L), M, ptr(RJ), (j1 - j0) * Np, rho, ptr(X, j0 * Np), N,
+                     ptr(out, j0 * Np), N, ptr(stats), 1 if i else 0, 0)
     return out, (stats.get() if want_stats else None)
 
 
@@ -262,6 +372,25 @@ class DenseTensor(Tensor):
 
     def to_numpy(self):
         return _host(self.data)
+
+    def norm(self) -> float:
+        """``||X||``: on the device (``ttsk_sumsq``, fixed summation order) for a device tensor or one with a current
+        upload, host NumPy otherwise."""
+        if not _dense_current(self):
+            return super().norm()
+        import ctypes
+        from . import _native as nat
+        arr = self.dev_data()
+        if not (arr.is_contiguous() or arr.T.is_contiguous()):      # a sum over all entries: their order is free
+            arr = arr.contiguous()
+        out = DevArray.empty((1,))
+        nat.call("ttsk_sumsq", ctypes.c_void_p(arr.ptr), ctypes.c_size_t(arr.size), ctypes.c_void_p(out.ptr), 0)
+        return float(np.sqrt(out.get()[0]))
+
+    def dot(self, other, reverse=False) -> float:
+        if isinstance(other, TensorTrain) and (other.resident() or _dense_current(self)):
+            return float(other.dense_stats(self)[0])                  # one pass over the tensor, nothing downloaded
+        return super().dot(other, reverse=reverse)
 
     def to_sparse(self) -> "SparseTensor":
         X = self.to_numpy()
@@ -504,6 +633,20 @@ class TensorTrain(_GatherOnDevice, Tensor):
             acc = np.einsum("nr,rns->ns", acc, sl)
         return acc.reshape(-1)
 
+    def dense_stats(self, X) -> npt.NDArray[np.float64]:
+        """``[sum x t, sum t^2, sum (t - x)^2, sum x^2]`` over all entries of the dense tensor ``X`` (a ``DenseTensor`` or
+        an ndarray of this shape) in one device pass that reconstructs the train tile by tile and stores nothing
+        (``ttsk_tt_dense_stats``).  The same bits on every call."""
+        arr, transposed = _dense_operand(X, self.shape)
+        return _tt_dense_pass(self.T if transposed else self, arr, False, True)[1]
+
+    def to_dense_dev(self) -> "DenseTensor":
+        """The full tensor as a ``DenseTensor`` whose data stay on the device (the same kernel, storing its tiles)."""
+        return DenseTensor(_tt_dense_pass(self, None, True, False)[0])
+
+    def dense(self) -> "DenseTensor":
+        return self.to_dense_dev() if self.resident() else super().dense()
+
     def orthogonalize(self) -> "TensorTrain":
         """Left-orthogonalising QR sweep (reference tensor.py:559-572)."""
         out, carry = [], None
@@ -709,11 +852,33 @@ class TensorTrain(_GatherOnDevice, Tensor):
             for a, b in zip(self.cores, other.cores):
                 acc = np.einsum("ij,ika,jkb->ab", acc, _host(a), _host(b), optimize=True)
             return float(acc.sum())
+        if isinstance(other, DenseTensor) and (self.resident() or _dense_current(other)):
+            return float(self.dense_stats(other)[0])
         return super().dot(other, reverse=reverse)
 
     def error(self, other, relative: bool = False, rmse: bool = False, fast: bool = False) -> float:
+        """``||self - other||`` (reference tensor.py:53-88).  Against a dense tensor with either side on the device all
+        of it comes from the four sums of one pass (``dense_stats``): the residual is ``sqrt(sum (t - x)^2)``, the
+        reference norm ``sqrt(sum x^2)``, and ``fast`` puts ``sum x t``, ``sum t^2`` and ``sum x^2`` into the reference's
+        formula.  A host train with a host array keeps the NumPy path."""
         if hasattr(other, "to_tt"):
             other = other.to_tt()
+        dense = DenseTensor(other) if isinstance(other, np.ndarray) else other
+        if isinstance(dense, DenseTensor) and (self.resident() or _dense_current(dense)):
+            s = self.dense_stats(dense)
+            ref_norm = float(np.sqrt(s[3]))
+            if fast:
+                tot = s[1] + s[3]
+                err = np.sqrt(tot) * np.sqrt(abs(1 - 2 * s[0] / tot))
+            else:
+                err = np.sqrt(s[2])
+            if relative:
+                if ref_norm == 0:
+                    return np.inf
+                err /= ref_norm
+            if rmse:
+                err /= np.sqrt(np.prod(self.shape))
+            return float(err)
         if isinstance(other, TensorTrain):
             err = self.add(-other).norm()
             if relative:
