@@ -568,6 +568,33 @@ def test_sum_slices(tsa):
         assert rel(got[:n2], want2) < 1e-15 and np.array_equal(got[n2:], dst0[n2:])
 
 
+def test_dev_array_is_a_ctypes_argument(tsa):
+    """A DevArray passed as it is reaches the library as its device address, a view's offset included: the same bits
+    as the explicit ``c_void_p(x.ptr)``.  None is still NULL (checked on entry points that test for it: ttsk_axpby
+    itself does not, its kernel would dereference the pointer)."""
+    import ctypes
+    from tt_sketch_amd import _native as nat
+    from tt_sketch_amd.device import DevArray
+    rng = np.random.default_rng(11)
+    # multiples of 1/8 below 2^7: every product and sum is exact, so NumPy's two roundings and a fused multiply-add on the
+    # device give the same bits
+    x, y0 = rng.integers(-1000, 1000, 8) / 8.0, rng.integers(-1000, 1000, 8) / 8.0
+    a, b, n = 1.75, -0.5, 5
+    want = y0.copy()
+    want[:n] = a * x[3:] + b * y0[:n]
+    xd = DevArray.from_host(x)
+    view = xd[3:]
+    assert view.ptr == xd.ptr + 24 and view._as_parameter_.value == view.ptr
+    raw, wrapped = DevArray.from_host(y0), DevArray.from_host(y0)
+    nat.call("ttsk_axpby", raw, view, a, b, n, 0)
+    nat.call("ttsk_axpby", ctypes.c_void_p(wrapped.ptr), ctypes.c_void_p(view.ptr), a, b, ctypes.c_size_t(n), 0)
+    assert np.array_equal(raw.get(), wrapped.get()) and np.array_equal(raw.get(), want)
+    with pytest.raises(ValueError):
+        nat.call("ttsk_triu", None, 4, 4, 0)
+    with pytest.raises(ValueError):          # None beside raw arrays
+        nat.call("ttsk_svd_small", DevArray.from_host(np.eye(4)), 4, 4, None, DevArray.empty((4,)), DevArray.empty((4, 4)), 0)
+
+
 def test_batched_one_call_path(tsa):
     """ttsk_tt_sketch_batch: nb tensors of one signature in one pass give, tensor by tensor, the
     sketch of the single-tensor call and of the oracle (rank slices included; nb > 32 is sliced)."""

@@ -1,6 +1,7 @@
 """CPU tests: host-side logic of tt_sketch_amd and the C-ABI surface (no compute calls)."""
 import ctypes
 import os
+import re
 
 import numpy as np
 import pytest
@@ -167,6 +168,101 @@ def test_helper_stream_of_a_one_call_sketch_is_drained_with_its_caller():
         tag = nat.dirty_snapshot()
         nat._drained(0)
         assert nat._dirty == {1} and not nat.drained_since(1, tag[1])
+    finally:
+        nat._dirty.clear(); nat._dirty.update(saved[0])
+        nat._stream_gen[:] = saved[1]
+        nat._joined_into.clear(); nat._joined_into.update(saved[2])
+
+
+# ------------------------------------------------------------------ _native.ENTRY_POINTS against include/ttsk.h
+_C_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64,
+              "double": ctypes.c_double, "float": ctypes.c_float}
+_C_RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char *": ctypes.c_char_p}
+# entry points that end in `int stream` and neither queue work on it nor drain it
+_STREAM_LAST_WITHOUT_ROLE = {
+    "ttsk_graph_begin": "opens a capture: nothing runs on the stream until ttsk_graph_launch, which is marked",
+}
+
+
+def _header_text():
+    with open(nat.HEADER_PATH) as f:
+        text = f.read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    return re.sub(r"//[^\n]*", " ", text)
+
+
+def _header_declarations():
+    """{name: (return type, [(type, name, is pointer), ...])} of every function include/ttsk.h declares."""
+    out = {}
+    for ret, name, params in re.findall(r"^[ \t]*((?:const\s+)?\w+\s*\*?)\s*(ttsk_\w+)\s*\(([^()]*)\)\s*;", _header_text(), flags=re.M):
+        plist = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            words = p.replace("*", " * ").split()
+            pname = words.pop()
+            plist.append((" ".join(w for w in words if w != "const"), pname, "*" in words))
+        out[name] = (" ".join(ret.replace("*", " *").split()), plist)
+    return out
+
+
+def _is_pointer_type(t) -> bool:
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer)
+
+
+def _ends_in_stream(params) -> bool:
+    return bool(params) and params[-1][:2] == ("int", "stream")
+
+
+def _roles_missing(has_role) -> list:
+    """Functions of the header that end in `int stream` for which ``has_role(name)`` is false, the stated exceptions aside."""
+    return sorted(name for name, (_, params) in _header_declarations().items()
+                  if _ends_in_stream(params) and not has_role(name) and name not in _STREAM_LAST_WITHOUT_ROLE)
+
+
+def test_entry_point_table_matches_the_header_types():
+    decls = _header_declarations()
+    assert sorted(decls) == nat.declared_symbols() == sorted(nat.ENTRY_POINTS)
+    for name, (ret, params) in decls.items():
+        e = nat.ENTRY_POINTS[name]
+        assert e.restype is _C_RETURNS[ret], name
+        assert len(e.argtypes) == len(params), name
+        for i, ((ctype, pname, is_ptr), t) in enumerate(zip(params, e.argtypes)):
+            assert _is_pointer_type(t) == is_ptr, (name, i, pname)
+            if not is_ptr:
+                assert t is _C_SCALARS[ctype], (name, i, pname)
+
+
+def test_entry_point_table_matches_the_header_constants():
+    text = _header_text()
+    assert nat.NUM_STREAMS == int(re.search(r"#define\s+TTSK_NUM_STREAMS\s+(\d+)", text).group(1))
+    status = {k: int(v) for k, v in re.findall(r"\b(TTSK_ERR_\w+)\s*=\s*(-?\d+)", text)}
+    mine = {k: v for k, v in vars(nat).items() if k.startswith("TTSK_ERR_")}
+    assert mine and all(status[k] == v for k, v in mine.items())
+
+
+def test_every_stream_argument_has_a_role():
+    """A queued entry point that is not marked leaves its stream out of the tag of a released buffer: the pool of
+    device.py would hand the buffer to another stream while the kernel still reads it."""
+    decls = _header_declarations()
+    queueing = (nat.QUEUE, nat.FORK_NEXT, nat.FORK_ALL)
+    assert _roles_missing(lambda name: nat.ENTRY_POINTS[name].role is not None) == []
+    assert set(_STREAM_LAST_WITHOUT_ROLE) <= set(decls)
+    for name, e in nat.ENTRY_POINTS.items():
+        params = decls[name][1]
+        assert e.role in queueing + (nat.DRAIN_FIRST, nat.DRAIN_LAST, None), name
+        if e.role in queueing or e.role == nat.DRAIN_LAST:
+            assert _ends_in_stream(params), name
+        if e.role == nat.DRAIN_FIRST:
+            assert params[0][:2] == ("int", "stream"), name
+
+
+def test_mark_records_the_streams_of_every_queueing_entry_point():
+    saved = (set(nat._dirty), list(nat._stream_gen), dict(nat._joined_into))
+    try:
+        for name, e in nat.ENTRY_POINTS.items():
+            nat._dirty.clear(); nat._joined_into.clear()
+            nat._mark(name, (None,) * (len(e.argtypes) - 1) + (3,))
+            want = {nat.QUEUE: {3}, nat.FORK_NEXT: {3, 4}, nat.FORK_ALL: set(range(nat.NUM_STREAMS))}.get(e.role, set())
+            assert nat._dirty == want, name
     finally:
         nat._dirty.clear(); nat._dirty.update(saved[0])
         nat._stream_gen[:] = saved[1]

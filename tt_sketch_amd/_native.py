@@ -6,8 +6,8 @@ device is present every compute entry point raises.
 import ctypes
 import os
 import re
-from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int16, c_int64,
-                    c_size_t, c_uint64, c_void_p)
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
+from typing import NamedTuple, Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TTSK_LIB") or os.path.join(_HERE, "libttsk.so")      # TTSK_LIB: another build of the library (A/B runs)
@@ -43,94 +43,133 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(ttsk_[a-z0-9_]+)\s*\(", text)))
 
 
+# Stream role of an entry point: what a call does to the library streams, which is what the buffer pool of device.py
+# needs to know to hand a released buffer out again (dirty_snapshot / drained_since below).
+QUEUE = "queue"              # queues work on the library stream given as the LAST argument
+FORK_NEXT = "queue, +1"      # the same, and forks a helper on stream + 1 that is joined back before the call returns
+FORK_ALL = "queue, all"      # the same, and forks every other library stream, all joined back
+DRAIN_FIRST = "drain first"  # returns only after the stream given as the FIRST argument has drained (negative: all of them)
+DRAIN_LAST = "drain last"    # the same for the stream given as the last argument
+_QUEUEING = (QUEUE, FORK_NEXT, FORK_ALL)
+
+
+class Entry(NamedTuple):
+    argtypes: list
+    role: Optional[str] = None     # None: queues no work
+    restype: type = c_int          # a ttsk_status unless stated
+
+
+P, I, S, I64, U64 = c_void_p, c_int, c_size_t, c_int64, c_uint64
+_CHAIN = [I, I, I, I, I, I, POINTER(P), I64, POINTER(P), I64, I64, I64, I64, P]       # ttsk_chain_step*: up to E
+_MODE_STREAM = [P, I64, P, S, POINTER(I), POINTER(U64), I, POINTER(I), POINTER(U64), I, I, P, P, P, P, P, I]
+_GAUSS_PASS = [P, P, P, P, S, I64, P, P, P, I, P, P, I]
+# Every function of include/ttsk.h, one line each: argument types, stream role, return type.  This is the only place an
+# entry point is described; tests/test_host_logic.py holds it against the header.
+ENTRY_POINTS = {
+    "ttsk_init": Entry([I]),
+    "ttsk_shutdown": Entry([]),
+    "ttsk_last_error": Entry([], restype=c_char_p),
+    "ttsk_device_info": Entry([c_char_p, S, POINTER(I), POINTER(S)]),
+    "ttsk_malloc": Entry([POINTER(P), S]),
+    "ttsk_free": Entry([P]),
+    "ttsk_memset": Entry([P, I, S, I], QUEUE),
+    "ttsk_h2d": Entry([P, P, S, I], DRAIN_LAST),
+    "ttsk_d2h": Entry([P, P, S, I], DRAIN_LAST),
+    "ttsk_d2d": Entry([P, P, S, I], QUEUE),
+    "ttsk_sync": Entry([I], DRAIN_FIRST),
+    "ttsk_stream_wait": Entry([I, I]),
+    "ttsk_timer_start": Entry([I], QUEUE),
+    "ttsk_timer_stop": Entry([I, POINTER(c_float)]),
+    "ttsk_graph_begin": Entry([I]),
+    "ttsk_graph_end": Entry([I, POINTER(P)]),
+    "ttsk_graph_launch": Entry([P, I], QUEUE),
+    "ttsk_graph_free": Entry([P]),
+    "ttsk_gemm": Entry([POINTER(GemmDesc), P, P, P, P, I], QUEUE),
+    "ttsk_copy_strided": Entry([P, P, I, POINTER(I64), POINTER(I64), POINTER(I64), I], QUEUE),
+    "ttsk_axpby": Entry([P, P, c_double, c_double, S, I], QUEUE),
+    "ttsk_sum_slices": Entry([P, P, I, S, S, I, I], QUEUE),
+    "ttsk_tt_sketch": Entry([I] + [POINTER(I64)] * 8 + [POINTER(P)] * 3 + [P, I, I], FORK_NEXT),
+    "ttsk_tt_sketch_batch": Entry([I, I] + [POINTER(I64)] * 8 + [POINTER(P)] * 3 + [P, I64, I, I], FORK_NEXT),
+    "ttsk_tt_sketch_sum": Entry([I, I] + [POINTER(I64)] * 8 + [POINTER(P)] * 3 + [P, I, I], FORK_NEXT),
+    "ttsk_chain_step": Entry(_CHAIN + [POINTER(P), POINTER(P), I], QUEUE),
+    "ttsk_chain_step_wide": Entry(_CHAIN + [POINTER(P), POINTER(P), I], QUEUE),
+    "ttsk_chain_step_sum": Entry(_CHAIN + [P, I64, I64, I64, POINTER(P), I], QUEUE),
+    "ttsk_dense_left_pass": Entry([P, I64, I64, I64, I64, I64, I, P, P, P, P, P, P, P, P, I], QUEUE),
+    "ttsk_tt_sketch_size": Entry([I] + [POINTER(I64)] * 5, restype=I64),
+    "ttsk_prof_enable": Entry([I]),
+    "ttsk_mfma_f64_peak_probe": Entry([POINTER(c_double)]),
+    "ttsk_ndtri_rate_probe": Entry([POINTER(c_double)]),
+    "ttsk_prof_read": Entry([I, POINTER(I64), POINTER(c_double), POINTER(c_double)]),
+    "ttsk_prof_kernel_name": Entry([I, c_char_p, S]),
+    "ttsk_hash_u64": Entry([P, S]),
+    "ttsk_inds_to_rand_double": Entry([P, P, I, S, I, I, U64, P]),
+    "ttsk_inds_to_normal": Entry([P, P, I, S, I, I, U64, P]),
+    "ttsk_inds_to_sparse_sign": Entry([P, P, I, S, I, I, I, I, U64, P]),
+    "ttsk_sparse_normal_dev": Entry([P, I64, POINTER(I), POINTER(U64), I, S, I, I, U64, P, I], QUEUE),
+    "ttsk_sparse_normal_table": Entry([POINTER(U64), I, I, I, U64, P, I], QUEUE),
+    "ttsk_sparse_sign_dev": Entry([P, I64, POINTER(I), POINTER(U64), I, S, I, I, I, I, U64, P, I], QUEUE),
+    "ttsk_sparse_sign_table": Entry([POINTER(U64), I, I, I, I, I, U64, P, I], QUEUE),
+    "ttsk_fill_normal": Entry([P, S, U64, c_double, I], QUEUE),
+    "ttsk_fill_normal_many": Entry([I, POINTER(P), POINTER(S), POINTER(U64), POINTER(c_double), I], QUEUE),
+    "ttsk_sparse_ttdrm_step": Entry([P, I64, P, I64, I64, P, S, P, I], QUEUE),
+    "ttsk_sparse_densedrm_gather": Entry([P, I64, I64, P, I64, POINTER(I), POINTER(I64), I, S, P, I], QUEUE),
+    "ttsk_sparse_psi": Entry([P, P, P, S, P, I64, P, I64, I64, P, I], QUEUE),
+    "ttsk_tt_gather": Entry([POINTER(P), POINTER(I64), POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
+    "ttsk_cp_gather": Entry([POINTER(P), I64, POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
+    "ttsk_tt_dense_stats": Entry([P, I64, P, I64, I64, P, P, P, I], QUEUE),
+    "ttsk_tt_dense_stats_ld": Entry([P, I64, P, I64, I64, P, I64, P, I64, P, I, I], QUEUE),
+    "ttsk_sumsq": Entry([P, S, P, I], QUEUE),
+    "ttsk_sparse_flat_mult": Entry([POINTER(U64), I, POINTER(U64)]),
+    "ttsk_sparse_mode_order": Entry([P, I64, S, POINTER(I), POINTER(U64), I, I, I64, P, I], QUEUE),
+    "ttsk_sparse_mode_stream": Entry(_MODE_STREAM, QUEUE),
+    "ttsk_sparse_mode_stream_u32": Entry(_MODE_STREAM, QUEUE),
+    "ttsk_sparse_gauss_pass": Entry(_GAUSS_PASS, QUEUE),
+    "ttsk_sparse_gauss_pass_u32": Entry(_GAUSS_PASS, QUEUE),
+    "ttsk_sparse_sort_mode": Entry([P, S, I64, P, I], QUEUE),
+    "ttsk_pinv": Entry([P, I64, I64, c_double, P, POINTER(I), I], QUEUE),
+    "ttsk_pinv_begin": Entry([P, I64, I64, c_double, P, I], QUEUE),
+    "ttsk_pinv_end": Entry([P, I64, I64, c_double, P, POINTER(I), I], QUEUE),
+    "ttsk_svd_small": Entry([P, I64, I64, P, P, P, I], QUEUE),
+    "ttsk_triu": Entry([P, I64, I64, I], QUEUE),
+    "ttsk_qr_thin": Entry([P, I64, I64, I], QUEUE),
+    "ttsk_orth_step": Entry([P, I64, I64, P, I64, P, I], QUEUE),
+    "ttsk_pinv_batch_deferred": Entry([I, POINTER(P), I64, I64, POINTER(P), I], QUEUE),
+    "ttsk_orth_step_pinv": Entry([P, I64, I64, P, I64, P, I], QUEUE),
+    "ttsk_deferred_status": Entry([I, POINTER(I)], DRAIN_FIRST),
+    "ttsk_tt_orth_sketch": Entry([I] + [POINTER(I64)] * 4 + [POINTER(P)] * 5 + [I], FORK_NEXT),
+    "ttsk_tt_orth_sketch_batch": Entry([I, I] + [POINTER(I64)] * 4 + [POINTER(P)] * 5 + [P, I], FORK_ALL),
+    "ttsk_dense_first_pass": Entry([P, I64, I64, I64, P, I64, P, I64, P, P, I], QUEUE),
+    "ttsk_pinv_batch": Entry([I, POINTER(P), I64, I64, POINTER(P), I], QUEUE),
+    "ttsk_tt_assemble": Entry([I] + [POINTER(I64)] * 3 + [POINTER(P)] * 4 + [I, I], FORK_ALL),
+    "ttsk_tt_assemble_batch": Entry([I, I] + [POINTER(I64)] * 3 + [POINTER(P)] * 4 + [I, I], QUEUE),
+    "ttsk_comm_unique_id": Entry([P]),
+    "ttsk_comm_init": Entry([P, I, I]),
+    "ttsk_comm_allreduce_sum": Entry([P, S, I], QUEUE),
+    "ttsk_comm_reduce_sum": Entry([P, S, I, I], QUEUE),
+    "ttsk_comm_allgather": Entry([P, P, S, I], QUEUE),
+    "ttsk_comm_allreduce_max": Entry([P, S, I], QUEUE),
+    "ttsk_comm_destroy": Entry([]),
+}
+del P, I, S, I64, U64
+
+
+def ptr_array(arrays):
+    """Host array of the device addresses of ``arrays`` (the `const double *const *` arguments)."""
+    return (c_void_p * len(arrays))(*[a.ptr for a in arrays])
+
+
+def i64_array(values):
+    return (c_int64 * len(values))(*[int(v) for v in values])
+
+
 def _bind(lib):
-    P, I, S = c_void_p, c_int, c_size_t
-    sig = {
-        "ttsk_init": [I], "ttsk_shutdown": [], "ttsk_device_info": [c_char_p, S, POINTER(I), POINTER(S)],
-        "ttsk_malloc": [POINTER(P), S], "ttsk_free": [P], "ttsk_memset": [P, I, S, I],
-        "ttsk_h2d": [P, P, S, I], "ttsk_d2h": [P, P, S, I], "ttsk_d2d": [P, P, S, I],
-        "ttsk_sync": [I], "ttsk_stream_wait": [I, I],
-        "ttsk_timer_start": [I], "ttsk_timer_stop": [I, POINTER(c_float)],
-        "ttsk_graph_begin": [I], "ttsk_graph_end": [I, POINTER(P)], "ttsk_graph_launch": [P, I],
-        "ttsk_graph_free": [P],
-        "ttsk_gemm": [POINTER(GemmDesc), P, P, P, P, I],
-        "ttsk_copy_strided": [P, P, I, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), I],
-        "ttsk_axpby": [P, P, c_double, c_double, S, I],
-        "ttsk_sum_slices": [P, P, I, S, S, I, I],
-        "ttsk_tt_sketch": [I] + [POINTER(c_int64)] * 8 + [POINTER(P)] * 3 + [P, I, I],
-        "ttsk_tt_sketch_batch": [I, I] + [POINTER(c_int64)] * 8 + [POINTER(P)] * 3 + [P, c_int64, I, I],
-        "ttsk_tt_sketch_sum": [I, I] + [POINTER(c_int64)] * 8 + [POINTER(P)] * 3 + [P, I, I],
-        "ttsk_chain_step": [I, I, I, I, I, I, POINTER(P), c_int64, POINTER(P), c_int64, c_int64, c_int64, c_int64, P,
-                            POINTER(P), POINTER(P), I],
-        "ttsk_chain_step_wide": [I, I, I, I, I, I, POINTER(P), c_int64, POINTER(P), c_int64, c_int64, c_int64, c_int64, P,
-                                 POINTER(P), POINTER(P), I],
-        "ttsk_chain_step_sum": [I, I, I, I, I, I, POINTER(P), c_int64, POINTER(P), c_int64, c_int64, c_int64, c_int64, P,
-                                P, c_int64, c_int64, c_int64, POINTER(P), I],
-        "ttsk_prof_enable": [I],
-        "ttsk_mfma_f64_peak_probe": [POINTER(c_double)],
-        "ttsk_ndtri_rate_probe": [POINTER(c_double)],
-        "ttsk_prof_read": [I, POINTER(c_int64), POINTER(c_double), POINTER(c_double)],
-        "ttsk_prof_kernel_name": [I, c_char_p, S],
-        "ttsk_hash_u64": [P, S],
-        "ttsk_inds_to_rand_double": [P, P, I, S, I, I, c_uint64, P],
-        "ttsk_inds_to_normal": [P, P, I, S, I, I, c_uint64, P],
-        "ttsk_inds_to_sparse_sign": [P, P, I, S, I, I, I, I, c_uint64, P],
-        "ttsk_sparse_normal_dev": [P, c_int64, POINTER(I), POINTER(c_uint64), I, S, I, I, c_uint64, P, I],
-        "ttsk_sparse_sign_dev": [P, c_int64, POINTER(I), POINTER(c_uint64), I, S, I, I, I, I, c_uint64, P, I],
-        "ttsk_fill_normal": [P, S, c_uint64, c_double, I],
-        "ttsk_fill_normal_many": [I, POINTER(P), POINTER(S), POINTER(c_uint64), POINTER(c_double), I],
-        "ttsk_sparse_ttdrm_step": [P, c_int64, P, c_int64, c_int64, P, S, P, I],
-        "ttsk_sparse_densedrm_gather": [P, c_int64, c_int64, P, c_int64, POINTER(I), POINTER(c_int64), I, S, P, I],
-        "ttsk_sparse_psi": [P, P, P, S, P, c_int64, P, c_int64, c_int64, P, I],
-        "ttsk_tt_gather": [POINTER(P), POINTER(c_int64), POINTER(c_int64), I, P, c_int64, POINTER(I), S, P, P, P, I],
-        "ttsk_cp_gather": [POINTER(P), c_int64, POINTER(c_int64), I, P, c_int64, POINTER(I), S, P, P, P, I],
-        "ttsk_tt_dense_stats": [P, c_int64, P, c_int64, c_int64, P, P, P, I],
-        "ttsk_tt_dense_stats_ld": [P, c_int64, P, c_int64, c_int64, P, c_int64, P, c_int64, P, I, I],
-        "ttsk_sumsq": [P, S, P, I],
-        "ttsk_sparse_normal_table": [POINTER(c_uint64), I, I, I, c_uint64, P, I],
-        "ttsk_sparse_sign_table": [POINTER(c_uint64), I, I, I, I, I, c_uint64, P, I],
-        "ttsk_sparse_flat_mult": [POINTER(c_uint64), I, POINTER(c_uint64)],
-        "ttsk_sparse_mode_order": [P, c_int64, S, POINTER(I), POINTER(c_uint64), I, I, c_int64, P, I],
-        "ttsk_sparse_mode_stream": [P, c_int64, P, S, POINTER(I), POINTER(c_uint64), I, POINTER(I), POINTER(c_uint64), I, I,
-                                    P, P, P, P, P, I],
-        "ttsk_sparse_mode_stream_u32": [P, c_int64, P, S, POINTER(I), POINTER(c_uint64), I, POINTER(I), POINTER(c_uint64), I, I,
-                                    P, P, P, P, P, I],
-        "ttsk_sparse_gauss_pass": [P, P, P, P, S, c_int64, P, P, P, I, P, P, I],
-        "ttsk_sparse_gauss_pass_u32": [P, P, P, P, S, c_int64, P, P, P, I, P, P, I],
-        "ttsk_sparse_sort_mode": [P, S, c_int64, P, I],
-        "ttsk_pinv": [P, c_int64, c_int64, c_double, P, POINTER(I), I],
-        "ttsk_pinv_begin": [P, c_int64, c_int64, c_double, P, I],
-        "ttsk_pinv_end": [P, c_int64, c_int64, c_double, P, POINTER(I), I],
-        "ttsk_triu": [P, c_int64, c_int64, I],
-        "ttsk_svd_small": [P, c_int64, c_int64, P, P, P, I],
-        "ttsk_qr_thin": [P, c_int64, c_int64, I],
-        "ttsk_orth_step": [P, c_int64, c_int64, P, c_int64, P, I],
-        "ttsk_deferred_status": [I, POINTER(I)],
-        "ttsk_pinv_batch_deferred": [I, POINTER(P), c_int64, c_int64, POINTER(P), I],
-        "ttsk_pinv_batch": [I, POINTER(P), c_int64, c_int64, POINTER(P), I],
-        "ttsk_dense_first_pass": [P, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P, P, I],
-        "ttsk_dense_left_pass": [P, c_int64, c_int64, c_int64, c_int64, c_int64, I, P, P, P, P, P, P, P, P, I],
-        "ttsk_orth_step_pinv": [P, c_int64, c_int64, P, c_int64, P, I],
-        "ttsk_tt_orth_sketch": [I] + [POINTER(c_int64)] * 4 + [POINTER(P)] * 5 + [I],
-        "ttsk_tt_orth_sketch_batch": [I, I] + [POINTER(c_int64)] * 4 + [POINTER(P)] * 5 + [P, I],
-        "ttsk_tt_assemble": [I] + [POINTER(c_int64)] * 3 + [POINTER(P)] * 4 + [I, I],
-        "ttsk_tt_assemble_batch": [I, I] + [POINTER(c_int64)] * 3 + [POINTER(P)] * 4 + [I, I],
-        "ttsk_comm_unique_id": [P], "ttsk_comm_init": [P, I, I],
-        "ttsk_comm_allreduce_sum": [P, S, I], "ttsk_comm_reduce_sum": [P, S, I, I],
-        "ttsk_comm_allgather": [P, P, S, I], "ttsk_comm_allreduce_max": [P, S, I],
-        "ttsk_comm_destroy": [],
-    }
     missing = [s for s in declared_symbols() if not hasattr(lib, s)]
     if missing:
         raise TtskError(f"{LIB_PATH} does not export {missing}")
-    for name, args in sig.items():
+    for name, e in ENTRY_POINTS.items():
         fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = c_int
-    lib.ttsk_last_error.restype = c_char_p
-    lib.ttsk_last_error.argtypes = []
-    lib.ttsk_tt_sketch_size.restype = c_int64
-    lib.ttsk_tt_sketch_size.argtypes = [I] + [POINTER(c_int64)] * 5
+        fn.argtypes = e.argtypes
+        fn.restype = e.restype
 
 
 def lib():
@@ -164,17 +203,6 @@ _sync_epoch = 0
 # user on the same stream, or after the streams that may still be touching it have been synchronised.
 _stream_gen = [0] * NUM_STREAMS
 _dirty = set()
-# entry points whose LAST argument is the library stream their work is queued on
-_STREAM_LAST = frozenset((
-    "ttsk_memset", "ttsk_d2d", "ttsk_gemm", "ttsk_copy_strided", "ttsk_axpby", "ttsk_sum_slices",
-    "ttsk_tt_sketch", "ttsk_tt_sketch_batch", "ttsk_tt_sketch_sum", "ttsk_chain_step", "ttsk_chain_step_wide", "ttsk_sparse_normal_dev", "ttsk_sparse_sign_dev",
-    "ttsk_fill_normal", "ttsk_fill_normal_many", "ttsk_sparse_ttdrm_step", "ttsk_sparse_densedrm_gather", "ttsk_sparse_psi", "ttsk_tt_gather", "ttsk_cp_gather",
-    "ttsk_tt_dense_stats", "ttsk_tt_dense_stats_ld", "ttsk_sumsq",
-    "ttsk_sparse_sort_mode", "ttsk_sparse_normal_table", "ttsk_sparse_sign_table", "ttsk_sparse_mode_order", "ttsk_sparse_mode_stream", "ttsk_sparse_mode_stream_u32", "ttsk_sparse_gauss_pass", "ttsk_sparse_gauss_pass_u32", "ttsk_pinv", "ttsk_pinv_begin", "ttsk_pinv_end", "ttsk_triu", "ttsk_svd_small",
-    "ttsk_qr_thin", "ttsk_orth_step", "ttsk_orth_step_pinv", "ttsk_pinv_batch_deferred", "ttsk_pinv_batch", "ttsk_dense_first_pass", "ttsk_tt_orth_sketch", "ttsk_tt_orth_sketch_batch", "ttsk_tt_assemble", "ttsk_tt_assemble_batch", "ttsk_comm_allreduce_sum", "ttsk_comm_reduce_sum", "ttsk_comm_allgather", "ttsk_comm_allreduce_max", "ttsk_graph_launch", "ttsk_timer_start"))
-_BLOCKING = frozenset(("ttsk_h2d", "ttsk_d2h"))          # return only after their stream has drained
-_TWO_STREAMS = frozenset(("ttsk_tt_sketch", "ttsk_tt_sketch_batch", "ttsk_tt_sketch_sum", "ttsk_tt_orth_sketch"))   # fork a helper on stream + 1, joined back
-_ALL_STREAMS = frozenset(("ttsk_tt_assemble", "ttsk_tt_orth_sketch_batch"))           # fork every other library stream, all joined back
 
 
 def sync_epoch() -> int:
@@ -205,13 +233,14 @@ _joined_into = {}
 
 
 def _mark(name, args):
-    if name in _STREAM_LAST:
+    e = ENTRY_POINTS.get(name)
+    if e is not None and e.role in _QUEUEING:
         s = int(args[-1])
         if 0 <= s < NUM_STREAMS:
             _dirty.add(s)
             _joined_into.pop(s, None)          # direct work on s: it is no longer merely a joined helper
-            helpers = ((s + 1) % NUM_STREAMS,) if name in _TWO_STREAMS else \
-                (tuple(h for h in range(NUM_STREAMS) if h != s) if name in _ALL_STREAMS else ())
+            helpers = ((s + 1) % NUM_STREAMS,) if e.role == FORK_NEXT else \
+                (tuple(h for h in range(NUM_STREAMS) if h != s) if e.role == FORK_ALL else ())
             for h in helpers:
                 if h not in _dirty or _joined_into.get(h) == s:
                     _joined_into[h] = s
@@ -233,21 +262,14 @@ def call(name, *args):
     global _sync_epoch
     _mark(name, args)                      # before the call: a failing call may have queued part of its work
     check(getattr(lib(), name)(*args))
-    if name == "ttsk_sync" and args:
-        s = int(args[0])
-        if s < 0:
+    role = ENTRY_POINTS[name].role
+    if role in (DRAIN_FIRST, DRAIN_LAST):
+        s = int(args[0 if role == DRAIN_FIRST else -1])
+        if s < 0:                          # ttsk_sync(-1): every stream
             _sync_epoch += 1
             for i in range(NUM_STREAMS):
                 _stream_gen[i] += 1
             _dirty.clear()
             _joined_into.clear()
         elif s < NUM_STREAMS:
-            _drained(s)
-    elif name in _BLOCKING:
-        s = int(args[-1])
-        if 0 <= s < NUM_STREAMS:
-            _drained(s)
-    elif name == "ttsk_deferred_status":   # waits for its stream
-        s = int(args[0])
-        if 0 <= s < NUM_STREAMS:
             _drained(s)

@@ -35,6 +35,7 @@ _F64 = np.dtype(np.float64)
 # work queued later on the same stream is ordered behind the old owner's.  So the single-stream paths
 # recycle at once, and whatever is released inside a multi-stream region (assemble_sketched_tt,
 # pinv_dev_many, contract(..., stream=k) temporaries) waits for that region's closing sync().
+# Which streams a call makes busy or drains is the stream role of its entry in ``_native.ENTRY_POINTS``.
 _POOL_MIN = 8 << 20          # bytes; from here on sizes are rounded to 2 MB instead of powers of two
 _POOL_CAP = 48 << 30         # bytes kept at most (large classes)
 _SMALL_CAP = 2 << 30         # bytes kept at most (small classes)
@@ -81,7 +82,7 @@ def _pool_give(size: int, ptr: int) -> None:
     big = size >= _POOL_MIN
     cap = _POOL_CAP if big else _SMALL_CAP
     if not big and _pool_bytes[False] + size > cap:
-        nat.lib().ttsk_free(ctypes.c_void_p(ptr))          # hipFree waits for the device itself
+        nat.lib().ttsk_free(ptr)          # hipFree waits for the device itself
         return
     _pool.setdefault(size, []).append((nat.dirty_snapshot(), ptr))
     _pool_bytes[big] += size
@@ -91,7 +92,7 @@ def _pool_give(size: int, ptr: int) -> None:
             break
         _, old = _pool[top].pop(0)
         _pool_bytes[True] -= top
-        nat.lib().ttsk_free(ctypes.c_void_p(old))
+        nat.lib().ttsk_free(old)
 
 
 def release_cached(min_bytes: int = _POOL_MIN) -> int:
@@ -103,7 +104,7 @@ def release_cached(min_bytes: int = _POOL_MIN) -> int:
     freed = 0
     for size in [k for k in _pool if k >= min_bytes]:
         for _, ptr in _pool.pop(size):
-            nat.lib().ttsk_free(ctypes.c_void_p(ptr))
+            nat.lib().ttsk_free(ptr)
             _pool_bytes[size >= _POOL_MIN] -= size
             freed += size
     return freed
@@ -121,7 +122,7 @@ class _Buffer:
             self.ptr = got
             return
         p = ctypes.c_void_p()
-        nat.call("ttsk_malloc", ctypes.byref(p), ctypes.c_size_t(self._pooled))
+        nat.call("ttsk_malloc", ctypes.byref(p), self._pooled)
         self.ptr = p.value
 
     def __del__(self):
@@ -165,7 +166,7 @@ class DevArray:
     def zeros(cls, shape, dtype=_F64, stream=0) -> "DevArray":
         a = cls.empty(shape, dtype, stream)
         if a.size:
-            nat.call("ttsk_memset", ctypes.c_void_p(a.ptr), 0, ctypes.c_size_t(a.size * a.dtype.itemsize), stream)
+            nat.call("ttsk_memset", a, 0, a.size * a.dtype.itemsize, stream)
         return a
 
     @classmethod
@@ -175,14 +176,18 @@ class DevArray:
             arr = arr.astype(np.float64)
         a = cls.empty(arr.shape, arr.dtype, stream)
         if arr.size:
-            nat.call("ttsk_h2d", ctypes.c_void_p(a.ptr), ctypes.c_void_p(arr.ctypes.data),
-                     ctypes.c_size_t(arr.nbytes), stream)
+            nat.call("ttsk_h2d", a, arr.ctypes.data, arr.nbytes, stream)
         return a
 
     # ---- basic properties
     @property
     def ptr(self) -> int:
         return self.buf.ptr + self.offset * self.dtype.itemsize
+
+    @property
+    def _as_parameter_(self):
+        """What ctypes passes for this array: its device address (a view's offset included)."""
+        return ctypes.c_void_p(self.ptr)
 
     @property
     def ndim(self):
@@ -282,8 +287,7 @@ class DevArray:
         out = DevArray.empty(self.shape, self.dtype, stream)
         if self.size:
             if self.is_contiguous():
-                nat.call("ttsk_d2d", ctypes.c_void_p(out.ptr), ctypes.c_void_p(self.ptr),
-                         ctypes.c_size_t(self.size * self.dtype.itemsize), stream)
+                nat.call("ttsk_d2d", out, self, self.size * self.dtype.itemsize, stream)
             else:
                 copy_into(out, self, stream)
         return out
@@ -292,8 +296,7 @@ class DevArray:
         src = self.contiguous(stream)
         out = np.empty(self.shape, dtype=self.dtype)
         if out.size:
-            nat.call("ttsk_d2h", ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(src.ptr),
-                     ctypes.c_size_t(out.nbytes), stream)
+            nat.call("ttsk_d2h", out.ctypes.data, src, out.nbytes, stream)
         return out
 
     def __array__(self, dtype=None, copy=None):
@@ -304,8 +307,7 @@ class DevArray:
         if not self.is_contiguous():
             raise ValueError("fill_zero needs a contiguous array")
         if self.size:
-            nat.call("ttsk_memset", ctypes.c_void_p(self.ptr), 0,
-                     ctypes.c_size_t(self.size * self.dtype.itemsize), stream)
+            nat.call("ttsk_memset", self, 0, self.size * self.dtype.itemsize, stream)
         return self
 
 
@@ -372,9 +374,8 @@ def copy_into(dst: DevArray, src: DevArray, stream=0):
     if len(merged) > 5:
         raise ValueError("copy_into supports at most 5 non-mergeable dimensions")
     nd = len(merged)
-    A = (ctypes.c_int64 * max(nd, 1))
-    nat.call("ttsk_copy_strided", ctypes.c_void_p(dst.ptr), ctypes.c_void_p(src.ptr), nd,
-             A(*[m[0] for m in merged]), A(*[m[1] for m in merged]), A(*[m[2] for m in merged]), stream)
+    shape, dst_strides, src_strides = (nat.i64_array([m[k] for m in merged]) for k in range(3))
+    nat.call("ttsk_copy_strided", dst, src, nd, shape, dst_strides, src_strides, stream)
 
 
 def as_dev(x, stream=0) -> DevArray:
@@ -496,13 +497,9 @@ def contract(spec: str, A: DevArray, B: DevArray, out: Optional[DevArray] = None
     d.alpha = float(alpha)
     d.accumulate = 1 if accumulate else 0
     d.split_k = int(split_k)
-    ks = None
-    if k_scale is not None:
-        if not k_scale.is_contiguous() or k_scale.size != d.Ko * d.Ki:
-            raise ValueError("k_scale must be a contiguous vector over the contracted index")
-        ks = ctypes.c_void_p(k_scale.ptr)
-    nat.call("ttsk_gemm", ctypes.byref(d), ctypes.c_void_p(A.ptr), ctypes.c_void_p(B.ptr),
-             ctypes.c_void_p(out.ptr), ks, stream)
+    if k_scale is not None and (not k_scale.is_contiguous() or k_scale.size != d.Ko * d.Ki):
+        raise ValueError("k_scale must be a contiguous vector over the contracted index")
+    nat.call("ttsk_gemm", ctypes.byref(d), A, B, out, k_scale, stream)
     return out
 
 
@@ -514,6 +511,5 @@ def axpby(y: DevArray, x: DevArray, a: float = 1.0, b: float = 1.0, stream=0):
     if not y.is_contiguous():
         raise ValueError("axpby: destination must be contiguous")
     if y.size:
-        nat.call("ttsk_axpby", ctypes.c_void_p(y.ptr), ctypes.c_void_p(x.ptr), float(a), float(b),
-                 ctypes.c_size_t(y.size), stream)
+        nat.call("ttsk_axpby", y, x, float(a), float(b), y.size, stream)
     return y

@@ -156,11 +156,11 @@ class RcclComm:
     def allreduce_sum(self, buf: DevArray, stream: int = 0) -> DevArray:
         if not buf.is_contiguous():
             raise ValueError("allreduce needs the packed (contiguous) sketch buffer")
-        nat.call("ttsk_comm_allreduce_sum", ctypes.c_void_p(buf.ptr), ctypes.c_size_t(buf.size), stream)
+        nat.call("ttsk_comm_allreduce_sum", buf, buf.size, stream)
         return buf
 
     def reduce_sum(self, buf: DevArray, root: int = 0, stream: int = 0) -> DevArray:
-        nat.call("ttsk_comm_reduce_sum", ctypes.c_void_p(buf.ptr), ctypes.c_size_t(buf.size), root, stream)
+        nat.call("ttsk_comm_reduce_sum", buf, buf.size, root, stream)
         return buf
 
     def allgather(self, send: DevArray, stream: int = 0) -> DevArray:
@@ -168,8 +168,7 @@ class RcclComm:
         if not send.is_contiguous():
             raise ValueError("allgather needs a contiguous buffer")
         recv = DevArray.empty((self.world, send.size), stream=stream)
-        nat.call("ttsk_comm_allgather", ctypes.c_void_p(send.ptr), ctypes.c_void_p(recv.ptr),
-                 ctypes.c_size_t(send.size), stream)
+        nat.call("ttsk_comm_allgather", send, recv, send.size, stream)
         return recv
 
     def max_over_ranks(self, value: float, stream: int = 0) -> float:
@@ -177,9 +176,9 @@ class RcclComm:
         if self._scalar is None:
             self._scalar = DevArray.empty((2,), stream=stream)
         host = np.array([float(value), 0.0])
-        nat.call("ttsk_h2d", ctypes.c_void_p(self._scalar.ptr), ctypes.c_void_p(host.ctypes.data), ctypes.c_size_t(16), stream)
-        nat.call("ttsk_comm_allreduce_max", ctypes.c_void_p(self._scalar.ptr), ctypes.c_size_t(2), stream)
-        nat.call("ttsk_d2h", ctypes.c_void_p(host.ctypes.data), ctypes.c_void_p(self._scalar.ptr), ctypes.c_size_t(16), stream)
+        nat.call("ttsk_h2d", self._scalar, host.ctypes.data, 16, stream)
+        nat.call("ttsk_comm_allreduce_max", self._scalar, 2, stream)
+        nat.call("ttsk_d2h", host.ctypes.data, self._scalar, 16, stream)
         return float(host[0])
 
     def barrier(self, stream: int = 0) -> None:

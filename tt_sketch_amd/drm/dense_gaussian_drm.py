@@ -67,8 +67,6 @@ class DenseGaussianDRM(CansketchTT, CansketchSparse, CansketchDense, CanIncrease
             rank, cols = mat.shape
             out = DevArray.empty((N, rank))
             m = mu + 1
-            nat.call("ttsk_sparse_densedrm_gather", ctypes.c_void_p(mat.ptr), rank, cols,
-                     ctypes.c_void_p(idx.ptr), N, (ctypes.c_int * m)(*order[:m]),
-                     (ctypes.c_int64 * m)(*tensor.shape[:m]), m, ctypes.c_size_t(N),
-                     ctypes.c_void_p(out.ptr), 0)
+            nat.call("ttsk_sparse_densedrm_gather", mat, rank, cols, idx, N, (ctypes.c_int * m)(*order[:m]),
+                     nat.i64_array(tensor.shape[:m]), m, N, out, 0)
             yield out.T

@@ -1,7 +1,6 @@
 """Drop-in for the reference's Cython module ``tt_sketch/drm/fast_lazy_gaussian.pyx``: the
 same four callables (``hash_int_c``, ``_inds_to_rand_double``, ``inds_to_normal``,
 ``inds_to_sparse_sign``; pyx:14,53,156,183), host arrays in and out, computed on the GPU."""
-import ctypes
 
 import numpy as np
 
@@ -13,7 +12,7 @@ def hash_int_c(vals) -> None:
     arr = np.asarray(vals)
     if arr.dtype != np.uint64 or not arr.flags.c_contiguous:
         raise TypeError("hash_int_c needs a C-contiguous uint64 array")
-    nat.call("ttsk_hash_u64", ctypes.c_void_p(arr.ctypes.data), ctypes.c_size_t(arr.size))
+    nat.call("ttsk_hash_u64", arr.ctypes.data, arr.size)
 
 
 def _prep(indices, shape):
@@ -29,9 +28,8 @@ def _inds_to_rand_double(indices, shape, rank_min, rank_max, seed):
     idx, shp = _prep(indices, shape)
     N = idx.shape[1]
     out = np.empty(N * (int(rank_max) - int(rank_min)))
-    nat.call("ttsk_inds_to_rand_double", ctypes.c_void_p(idx.ctypes.data),
-             ctypes.c_void_p(shp.ctypes.data), idx.shape[0], ctypes.c_size_t(N), int(rank_min),
-             int(rank_max), ctypes.c_uint64(int(seed) % 2**64), ctypes.c_void_p(out.ctypes.data))
+    nat.call("ttsk_inds_to_rand_double", idx.ctypes.data, shp.ctypes.data, idx.shape[0], N, int(rank_min),
+             int(rank_max), int(seed) % 2**64, out.ctypes.data)
     return out
 
 
@@ -40,9 +38,8 @@ def inds_to_normal(indices, shape, rank_min, rank_max, seed):
     idx, shp = _prep(indices, shape)
     N = idx.shape[1]
     out = np.empty((N, int(rank_max) - int(rank_min)))
-    nat.call("ttsk_inds_to_normal", ctypes.c_void_p(idx.ctypes.data), ctypes.c_void_p(shp.ctypes.data),
-             idx.shape[0], ctypes.c_size_t(N), int(rank_min), int(rank_max),
-             ctypes.c_uint64(int(seed) % 2**63), ctypes.c_void_p(out.ctypes.data))
+    nat.call("ttsk_inds_to_normal", idx.ctypes.data, shp.ctypes.data, idx.shape[0], N, int(rank_min), int(rank_max),
+             int(seed) % 2**63, out.ctypes.data)
     return out
 
 
@@ -51,8 +48,6 @@ def inds_to_sparse_sign(indices, shape, rank, rank_min, rank_max, non_zero_per_r
     idx, shp = _prep(indices, shape)
     N = idx.shape[1]
     out = np.zeros((N, int(rank_max) - int(rank_min)), dtype=np.int16)
-    nat.call("ttsk_inds_to_sparse_sign", ctypes.c_void_p(idx.ctypes.data),
-             ctypes.c_void_p(shp.ctypes.data), idx.shape[0], ctypes.c_size_t(N), int(rank), int(rank_min),
-             int(rank_max), int(non_zero_per_row), ctypes.c_uint64(int(seed) % 2**63),
-             ctypes.c_void_p(out.ctypes.data))
+    nat.call("ttsk_inds_to_sparse_sign", idx.ctypes.data, shp.ctypes.data, idx.shape[0], N, int(rank), int(rank_min),
+             int(rank_max), int(non_zero_per_row), int(seed) % 2**63, out.ctypes.data)
     return out

@@ -31,8 +31,6 @@ class SparseGaussianDRM(CansketchSparse, CanIncreaseRank):
             m = mu + 1
             lo, hi = self.rank_min[mu], self.rank_max[mu]
             out = DevArray.empty((N, hi - lo))
-            nat.call("ttsk_sparse_normal_dev", ctypes.c_void_p(idx.ptr), N,
-                     (ctypes.c_int * m)(*order[:m]), (ctypes.c_uint64 * m)(*tensor.shape[:m]), m,
-                     ctypes.c_size_t(N), lo, hi, ctypes.c_uint64((mu + int(self.seed)) % 2**63),
-                     ctypes.c_void_p(out.ptr), 0)
+            nat.call("ttsk_sparse_normal_dev", idx, N, (ctypes.c_int * m)(*order[:m]), (ctypes.c_uint64 * m)(*tensor.shape[:m]),
+                     m, N, lo, hi, (mu + int(self.seed)) % 2**63, out, 0)
             yield out.T

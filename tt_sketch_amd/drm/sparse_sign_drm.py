@@ -31,8 +31,6 @@ class SparseSignDRM(CansketchSparse, CanSlice):
             m = mu + 1
             lo, hi = self.rank_min[mu], self.rank_max[mu]
             out = DevArray.empty((N, hi - lo))
-            nat.call("ttsk_sparse_sign_dev", ctypes.c_void_p(idx.ptr), N,
-                     (ctypes.c_int * m)(*order[:m]), (ctypes.c_uint64 * m)(*tensor.shape[:m]), m,
-                     ctypes.c_size_t(N), int(self.true_rank[mu]), lo, hi, int(self.nnz[mu]),
-                     ctypes.c_uint64((mu + int(self.seed)) % 2**63), ctypes.c_void_p(out.ptr), 0)
+            nat.call("ttsk_sparse_sign_dev", idx, N, (ctypes.c_int * m)(*order[:m]), (ctypes.c_uint64 * m)(*tensor.shape[:m]),
+                     m, N, int(self.true_rank[mu]), lo, hi, int(self.nnz[mu]), (mu + int(self.seed)) % 2**63, out, 0)
             yield out.T

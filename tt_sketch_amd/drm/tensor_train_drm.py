@@ -8,7 +8,6 @@ last core never materialised) and every chain step is an MFMA contraction in HBM
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional, Tuple, Union
 
 import numpy as np
@@ -104,10 +103,7 @@ class TensorTrainDRM(CansketchSparse, CansketchTT, CansketchCP, CanSlice, Canske
             D = self._core(mu).contiguous()
             rho, n, rhop = D.shape
             out = DevArray.empty((N, rhop))
-            row_ptr = idx.ptr + order[mu] * N * 8
-            nat.call("ttsk_sparse_ttdrm_step", None if v is None else ctypes.c_void_p(v.ptr), rho,
-                     ctypes.c_void_p(D.ptr), n, rhop, ctypes.c_void_p(row_ptr), ctypes.c_size_t(N),
-                     ctypes.c_void_p(out.ptr), 0)
+            nat.call("ttsk_sparse_ttdrm_step", v, rho, D, n, rhop, idx[order[mu]], N, out, 0)
             v = out
             yield self._cut(mu, v).T
 

@@ -15,6 +15,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Type
 import numpy as np
 import numpy.typing as npt
 
+from . import _native as nat
 from .device import DevArray, as_dev, contract, sync, to_host
 from .drm import ALL_DRM, DenseGaussianDRM, SparseGaussianDRM, TensorTrainDRM
 from .drm_base import DRM, CanIncreaseRank, CanSlice
@@ -140,18 +141,13 @@ def stream_sketch_batch(tensors: Sequence[Tensor], left_rank: TTRank, right_rank
                and all(tuple(t.shape) == tuple(tensors[0].shape) and tuple(t.rank) == tuple(tensors[0].rank) for t in tensors))
     out = []
     if batched:
-        import ctypes
         if tuple(left_drm.shape) != tuple(tensors[0].shape) or tuple(right_drm.shape) != tuple(tensors[0].shape):
             raise ValueError(f"Shape {left_drm.shape} of DRM doesn't match tensor's shape {tensors[0].shape}")
         plan = tt_fused.TTSketchPlan(tensors[0].shape, tensors[0].rank, left_drm, right_drm)
         stride = plan.size + (plan.size & 1)
         buf = DevArray.empty((len(tensors) * stride,))
-        keep, flat = [], []
-        for t in tensors:
-            ptrs, k = plan.core_pointers(t)
-            keep.append(k)
-            flat += [ptrs[i] for i in range(plan.d)]
-        plan.run_batch((ctypes.c_void_p * len(flat))(*flat), len(tensors), buf, stride)
+        cores = [c for t in tensors for c in plan.core_pointers(t)[1]]
+        plan.run_batch(nat.ptr_array(cores), len(tensors), buf, stride)
         for b in range(len(tensors)):
             Psi, Om = plan.views(buf[b * stride:b * stride + plan.size])
             out.append(SketchedTensorTrain(SketchContainer(Psi, Om), left_drm, right_drm))
@@ -346,16 +342,9 @@ def _blocked_stream_sketch_components(tensor, left_drm, right_drm, left_rank_sli
     return out
 
 
-def nat_streams() -> int:
-    from . import _native
-    return _native.NUM_STREAMS
-
-
 def _assemble_one_call(Psi, Om, direction):
     """The d - 1 (pseudo-inverse, product) pairs through ``ttsk_tt_assemble``: one library call that deals them over the
     library's streams and joins them, instead of 3 (d - 1) calls from here.  None if an operand is not a plain array."""
-    import ctypes
-    from . import _native as nat
     d = len(Psi)
     if d < 2 or len(Om) != d - 1 or not all(isinstance(a, DevArray) for a in list(Psi) + list(Om)):
         return None
@@ -381,10 +370,8 @@ def _assemble_one_call(Psi, Om, direction):
     arrs = _carve(shapes + [(rr[k], lr[k]) for k in range(d - 1)])
     cores = arrs[:d - 1] + [Psi[-1]] if direction == "right" else [Psi[0]] + arrs[:d - 1]
     work = arrs[d - 1:]
-    I64, P = ctypes.c_int64, ctypes.c_void_p
-    nat.call("ttsk_tt_assemble", d, (I64 * d)(*n), (I64 * (d - 1))(*lr), (I64 * (d - 1))(*rr), (P * d)(*[p.ptr for p in Psi]),
-             (P * (d - 1))(*[o.ptr for o in Om]), (P * d)(*[c.ptr for c in cores]), (P * (d - 1))(*[w.ptr for w in work]),
-             0 if direction == "right" else 1, 0)
+    nat.call("ttsk_tt_assemble", d, nat.i64_array(n), nat.i64_array(lr), nat.i64_array(rr), nat.ptr_array(Psi),
+             nat.ptr_array(Om), nat.ptr_array(cores), nat.ptr_array(work), 0 if direction == "right" else 1, 0)
     nat.call("ttsk_sync", 0)                      # operands and the pseudo-inverses are released after this
     return cores
 
@@ -403,7 +390,7 @@ def assemble_sketched_tt(sketch: SketchContainer, direction="auto", device: bool
     one = _assemble_one_call(Psi, Om, direction)
     if one is not None:
         return one if device else [np.asarray(to_host(C)) for C in one]
-    nstreams = max(1, min(len(Om), nat_streams()))
+    nstreams = max(1, min(len(Om), nat.NUM_STREAMS))
     sync()
     pending, keep = [], []          # `keep`: operands stay allocated until the streams have drained
     pinvs = pinv_dev_many(Om, streams=range(nstreams))      # pinv k on stream k % nstreams, verdicts read afterwards
@@ -448,8 +435,6 @@ def _auto_direction(sketch: SketchContainer) -> str:
 def _assemble_batch_call(group, direction):
     """One ``ttsk_tt_assemble_batch`` call over sketches of one signature whose operands are device arrays; returns the
     cores per sketch (device-resident).  Cores of one mode are equally spaced in one allocation."""
-    import ctypes
-    from . import _native as nat
     from .tt_fused import _carve
     arrs = [s.device_arrays() for s in group]
     Psi0, Om0 = arrs[0]
@@ -464,20 +449,18 @@ def _assemble_batch_call(group, direction):
         shapes = [(rr[mu - 1], n[mu], 1 if mu == d - 1 else rr[mu]) for mu in range(1, d)]
     per = shapes + [(rr[k], lr[k]) for k in range(d - 1)]
     out = _carve(per * len(group))
-    psi_p, om_p, core_p, work_p, cores = [], [], [], [], []
+    psi, om, work, cores = [], [], [], []
     for b, (Psi, Om) in enumerate(arrs):
         Psi = [p.contiguous() for p in Psi]
         Om = [o.contiguous() for o in Om]
         mine = out[b * len(per):(b + 1) * len(per)]
         cs = mine[:d - 1] + [Psi[-1]] if direction == "right" else [Psi[0]] + mine[:d - 1]
         cores.append(cs)
-        psi_p += [p.ptr for p in Psi]
-        om_p += [o.ptr for o in Om]
-        core_p += [c.ptr for c in cs]
-        work_p += [w.ptr for w in mine[d - 1:]]
-    I64, P = ctypes.c_int64, ctypes.c_void_p
-    nat.call("ttsk_tt_assemble_batch", len(group), d, (I64 * d)(*n), (I64 * (d - 1))(*lr), (I64 * (d - 1))(*rr),
-             (P * len(psi_p))(*psi_p), (P * len(om_p))(*om_p), (P * len(core_p))(*core_p), (P * len(work_p))(*work_p),
+        psi += Psi
+        om += Om
+        work += mine[d - 1:]
+    nat.call("ttsk_tt_assemble_batch", len(group), d, nat.i64_array(n), nat.i64_array(lr), nat.i64_array(rr),
+             nat.ptr_array(psi), nat.ptr_array(om), nat.ptr_array([c for cs in cores for c in cs]), nat.ptr_array(work),
              0 if direction == "right" else 1, 0)
     return cores
 

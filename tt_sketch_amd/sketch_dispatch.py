@@ -118,10 +118,8 @@ def _pinvs_up_front(Omega_mats) -> dict:
         if len(items) < 2 or min(l, r) > 128 or len(items) > 32:
             continue
         Ps = [DevArray.empty((r, l)) for _ in items]
-        P = ctypes.c_void_p
         try:
-            nat.call("ttsk_pinv_batch_deferred", len(items), (P * len(items))(*[O.ptr for _, O in items]), l, r,
-                     (P * len(items))(*[p.ptr for p in Ps]), 0)
+            nat.call("ttsk_pinv_batch_deferred", len(items), nat.ptr_array([O for _, O in items]), l, r, nat.ptr_array(Ps), 0)
         except nat.TtskUnsupported:
             continue
         for (mu, O), p in zip(items, Ps):
@@ -142,20 +140,19 @@ def orth_step(Psi, Omega=None, deferred: bool = False, pinv=None) -> DevArray:
         raise ValueError(f"cannot orthogonalise a {r1 * n} x {k} unfolding: trim the sketch ranks")
     if deferred and pinv is not None:
         Q = DevArray.empty((r1 * n, k))
-        nat.call("ttsk_orth_step_pinv", ctypes.c_void_p(M.ptr), r1 * n, r2, ctypes.c_void_p(pinv[0].ptr), k, ctypes.c_void_p(Q.ptr), 0)
+        nat.call("ttsk_orth_step_pinv", M, r1 * n, r2, pinv[0], k, Q, 0)
         return Q.reshape(r1, n, k)
     if deferred:
         Om = None if Omega is None else as_dev(Omega).contiguous()
         Q = DevArray.empty((r1 * n, k))
-        nat.call("ttsk_orth_step", ctypes.c_void_p(M.ptr), r1 * n, r2, None if Om is None else ctypes.c_void_p(Om.ptr),
-                 k, ctypes.c_void_p(Q.ptr), 0)
+        nat.call("ttsk_orth_step", M, r1 * n, r2, Om, k, Q, 0)
         return Q.reshape(r1, n, k)
     if Omega is not None:
         M = contract("ij,jk->ik", M, pinv_dev(Omega))
     elif M is P or M.buf is P.buf:
         M = M.copy()                       # QR works in place; keep the caller's Psi intact
     m, k = M.shape
-    nat.call("ttsk_qr_thin", ctypes.c_void_p(M.ptr), m, k, 0)
+    nat.call("ttsk_qr_thin", M, m, k, 0)
     return M.reshape(r1, n, k)
 
 

@@ -86,7 +86,6 @@ def prepare_left(tensor, left_contractions) -> bool:
     """DRM MATRICES on the left (DenseGaussianDRM, plug-ins), order >= 5: the first four left products Z_mu = A_mu X^{<mu+1>}
     from ONE read of the tensor (``ttsk_dense_left_pass``) instead of one pass each; they land in ``_shared`` under the
     keys ``_left_product`` looks them up by.  Called by ``general_sketch`` before the Omega loop."""
-    import ctypes
     from .. import _native as nat
     if os.environ.get("TTSK_DENSE_LEFT_PASS", "1") == "0":
         return False
@@ -116,10 +115,8 @@ def prepare_left(tensor, left_contractions) -> bool:
     A3 = hit[1]
     Z0, Z1 = DevArray.empty((l, n1 * n2 * C)), DevArray.empty((l, n2 * C))
     Z2, E3 = DevArray.empty((l, C)), DevArray.empty((l, C))
-    V = ctypes.c_void_p
     try:
-        nat.call("ttsk_dense_left_pass", V(X.ptr), n0, n1, n2, C, n4, l, V(A0.ptr), V(A1t.ptr), V(A2t.ptr), V(A3.ptr), V(Z0.ptr),
-                 V(Z1.ptr), V(Z2.ptr), V(E3.ptr), 0)
+        nat.call("ttsk_dense_left_pass", X, n0, n1, n2, C, n4, l, A0, A1t, A2t, A3, Z0, Z1, Z2, E3, 0)
     except nat.TtskUnsupported:
         return False
     Z3 = contract("aij,i->aj", E3.reshape(l, n3, n4), DevArray.from_host(np.ones(n3)))
@@ -181,7 +178,6 @@ def _first_pass(A, B, X, mu: int = 0) -> bool:
     """Z_mu and Psi_mu -- the two products that read the tensor (mu = 0) or the previous left product Z_{mu-1} (mu > 0) --
     from ONE read of it (``ttsk_dense_first_pass``, csrc/dense_pass.hip) when both DRMs are tensor trains and the shape is in
     the kernel's cover.  Both land in ``_shared`` under the keys ``_left_product`` / ``_psi_chained`` look them up by."""
-    import ctypes
     from .. import _native as nat
     if not (isinstance(A, ChainedUnfolding) and A.depth == mu and isinstance(B, ChainedUnfolding) and B.prev is not None):
         return False
@@ -212,9 +208,8 @@ def _first_pass(A, B, X, mu: int = 0) -> bool:
         return False
     C = A.core.reshape(rows, ll).contiguous()
     Z, U = DevArray.empty((ll, Q * T)), DevArray.empty((rows, rho, T))
-    V = ctypes.c_void_p
     try:
-        nat.call("ttsk_dense_first_pass", V(S.ptr), rows, Q, T, V(C.ptr), ll, V(P.ptr), rho, V(Z.ptr), V(U.ptr), 0)
+        nat.call("ttsk_dense_first_pass", S, rows, Q, T, C, ll, P, rho, Z, U, 0)
     except nat.TtskUnsupported:
         return False
     _shared[("left", _ident(A), id(X.buf), X.offset, mu)] = (A, X, Z)

@@ -82,10 +82,10 @@ class _Side:
             out = DevArray.empty((self.prefixes(k) + 1, self.width(k)))
             if self.sign:
                 nat.call("ttsk_sparse_sign_table", _u64(self.shape[:k + 1]), k + 1, int(drm.true_rank[k]), int(drm.rank_min[k]),
-                         int(drm.rank_max[k]), int(drm.nnz[k]), ctypes.c_uint64(self.seed(k)), ctypes.c_void_p(out.ptr), 0)
+                         int(drm.rank_max[k]), int(drm.nnz[k]), self.seed(k), out, 0)
             else:
                 nat.call("ttsk_sparse_normal_table", _u64(self.shape[:k + 1]), k + 1, int(drm.rank_min[k]),
-                         int(drm.rank_max[k]), ctypes.c_uint64(self.seed(k)), ctypes.c_void_p(out.ptr), 0)
+                         int(drm.rank_max[k]), self.seed(k), out, 0)
             self.cache[key] = out
         return self.cache[key]
 
@@ -123,19 +123,17 @@ def _mode_stream(tensor: SparseTensor, mu: int):
         # mode order with the suffix as the secondary key (not the plain mode sort of dev_mode_perm): inside a slice the
         # rows of the right-hand DRM tables are then visited in ascending order
         perm = DevArray.empty((N,), dtype=np.int64)
-        nat.call("ttsk_sparse_mode_order", ctypes.c_void_p(idx.ptr), N, ctypes.c_size_t(N), ints(r_rows), _u64(r_shape or [1]),
-                 len(r_rows), int(order[mu]), int(tensor.shape[mu]), ctypes.c_void_p(perm.ptr), 0)
+        nat.call("ttsk_sparse_mode_order", idx, N, N, ints(r_rows), _u64(r_shape or [1]),
+                 len(r_rows), int(order[mu]), int(tensor.shape[mu]), perm, 0)
         # 32-bit flat indices where every prefix / suffix extent stays below 2^31 (20 instead of 28 bytes per record and pass)
         small = int(np.prod(l_shape or [1], dtype=object)) < 2**31 and int(np.prod(r_shape or [1], dtype=object)) < 2**31
         words = (N + 1) // 2 if small else N
         fl, fr = DevArray.empty((words,), dtype=np.int64), DevArray.empty((words,), dtype=np.int64)
         jj = DevArray.empty(((N + 1) // 2,), dtype=np.int64)          # int32 records
         vv = DevArray.empty((N,))
-        nat.call("ttsk_sparse_mode_stream_u32" if small else "ttsk_sparse_mode_stream", ctypes.c_void_p(idx.ptr), N,
-                 ctypes.c_void_p(perm.ptr), ctypes.c_size_t(N),
+        nat.call("ttsk_sparse_mode_stream_u32" if small else "ttsk_sparse_mode_stream", idx, N, perm, N,
                  ints(l_rows), _u64(l_shape or [1]), len(l_rows), ints(r_rows), _u64(r_shape or [1]), len(r_rows), int(order[mu]),
-                 ctypes.c_void_p(val.ptr), ctypes.c_void_p(fl.ptr), ctypes.c_void_p(fr.ptr), ctypes.c_void_p(jj.ptr),
-                 ctypes.c_void_p(vv.ptr), 0)
+                 val, fl, fr, jj, vv, 0)
         cache[key] = (fl, fr, jj, vv, small)
     return cache[key]
 
@@ -216,11 +214,9 @@ def try_sparse_gauss_sketch(tensor, left_drm, right_drm, method):
         for f in (A, B, C):
             if f is not None and f.kind >= 2:
                 sampled += f.w
-        P = ctypes.c_void_p
         ref = lambda f: None if f is None else ctypes.byref(f)
-        nat.call("ttsk_sparse_gauss_pass_u32" if small else "ttsk_sparse_gauss_pass", P(fl.ptr), P(fr.ptr), P(jj.ptr), P(vv.ptr),
-                 ctypes.c_size_t(N), int(shape[mu]),
-                 ref(A), ref(B), ref(C), c_left, P(psi.ptr), None if om is None else P(om.ptr), 0)
+        nat.call("ttsk_sparse_gauss_pass_u32" if small else "ttsk_sparse_gauss_pass", fl, fr, jj, vv, N, int(shape[mu]),
+                 ref(A), ref(B), ref(C), c_left, psi, om, 0)
         Psi.append(psi)
     last_plan.clear()
     last_plan.update(sampled_columns_per_nonzero=sampled, passes=d, stream_bytes_per_nonzero_and_pass=20 if small else 28,

@@ -66,7 +66,6 @@ def _gather_indices(idx, shape):
 def _tt_gather_composed(cores, dev_idx, stride, order, N, val, want_out, want_stats):
     """The chain from ``ttsk_sparse_ttdrm_step``, mode by mode, for ranks beyond the fused kernel's cover: chunks of the
     list small enough for the panel budget, the statistics from device products summed over the chunks in order."""
-    import ctypes
     from . import _native as nat
     widest = max(max(c.shape[0], c.shape[2]) for c in cores)
     chunk = max(1, _GATHER_PANEL_BYTES // (16 * widest))
@@ -78,9 +77,7 @@ def _tt_gather_composed(cores, dev_idx, stride, order, N, val, want_out, want_st
         for k, c in enumerate(cores):
             rho, n, rhop = c.shape
             nxt = DevArray.empty((m, rhop))
-            nat.call("ttsk_sparse_ttdrm_step", None if v is None else ctypes.c_void_p(v.ptr), rho, ctypes.c_void_p(c.ptr),
-                     n, rhop, ctypes.c_void_p(dev_idx.ptr + (order[k] * stride + lo) * 8), ctypes.c_size_t(m),
-                     ctypes.c_void_p(nxt.ptr), 0)
+            nat.call("ttsk_sparse_ttdrm_step", v, rho, c, n, rhop, dev_idx[order[k], lo:lo + m], m, nxt, 0)
             v = nxt
         if want_out:
             copy_into(out[lo:lo + m], v.reshape(m))
@@ -105,13 +102,11 @@ def _gather_device(tensor, idx, want_out: bool, want_stats: bool):
     cores = [c.contiguous() for c in tensor.dev_cores()]
     out = DevArray.empty((N,)) if want_out else None
     stats = DevArray.empty((3,)) if want_stats else None
-    ptr = lambda a: None if a is None else ctypes.c_void_p(a.ptr)
-    tail = (ptr(dev_idx), stride, (ctypes.c_int * d)(*order), ctypes.c_size_t(N), ptr(val) if want_stats else None,
-            ptr(out), ptr(stats), 0)
-    cptr = (ctypes.c_void_p * d)(*[c.ptr for c in cores])
-    shape = (ctypes.c_int64 * d)(*tensor.shape)
+    tail = (dev_idx, stride, (ctypes.c_int * d)(*order), N, val if want_stats else None, out, stats, 0)
+    cptr = nat.ptr_array(cores)
+    shape = nat.i64_array(tensor.shape)
     if isinstance(tensor, TensorTrain):
-        ranks = (ctypes.c_int64 * (d + 1))(*([c.shape[0] for c in cores] + [cores[-1].shape[2]]))
+        ranks = nat.i64_array([c.shape[0] for c in cores] + [cores[-1].shape[2]])
         try:
             nat.call("ttsk_tt_gather", cptr, ranks, shape, d, *tail)
         except nat.TtskUnsupported:
@@ -207,7 +202,6 @@ def _tt_dense_pass(tt: "TensorTrain", X: Optional[DevArray], want_out: bool, wan
     """``ttsk_tt_dense_stats`` over the whole tensor: (DevArray of ``tt.shape`` or None, the four sums ``x . t``,
     ``t . t``, ``|t - x|^2``, ``x . x`` as a host array or None).  ``X``: C-contiguous device array of ``tt.shape``, or
     None.  Slabs (``_dense_split``) are passed in order and their sums added on the device."""
-    import ctypes
     from . import _native as nat
     plan = _dense_split(tt.shape, tt.rank, _GATHER_PANEL_BYTES)
     k, M, N, rho, slabs = plan["k"], plan["M"], plan["N"], plan["rho"], plan["slabs"]
@@ -216,17 +210,17 @@ def _tt_dense_pass(tt: "TensorTrain", X: Optional[DevArray], want_out: bool, wan
     L = _core_chain(cores[:k], False).contiguous().reshape(M, rho) if k else one()
     out = DevArray.empty(tt.shape) if want_out else None
     stats = DevArray.empty((4,)) if want_stats else None
-    ptr = lambda a, off=0: None if a is None else ctypes.c_void_p(a.ptr + 8 * off)
     if len(slabs) == 1:
         R = _core_chain(cores[k:], True).contiguous().reshape(rho, N)
-        nat.call("ttsk_tt_dense_stats", ptr(L), M, ptr(R), N, rho, ptr(X), ptr(out), ptr(stats), 0)
+        nat.call("ttsk_tt_dense_stats", L, M, R, N, rho, X, out, stats, 0)
     else:
         Np = N // tt.shape[k]
         Rp = _core_chain(cores[k + 1:], True).contiguous().reshape(-1, Np) if k + 1 < tt.ndim else one()
+        slab = lambda a: None if a is None else a.reshape(M, N)[:, j0 * Np:j1 * Np]       # its columns, rows N apart
         for i, (j0, j1) in enumerate(slabs):
             RJ = contract("ajb,bn->ajn", cores[k][:, j0:j1, :], Rp)
-            nat.call("ttsk_tt_dense_stats_ld", ptr(L), M, ptr(RJ), (j1 - j0) * Np, rho, ptr(X, j0 * Np), N,
-                     ptr(out, j0 * Np), N, ptr(stats), 1 if i else 0, 0)
+            nat.call("ttsk_tt_dense_stats_ld", L, M, RJ, (j1 - j0) * Np, rho, slab(X), N, slab(out), N, stats,
+                     1 if i else 0, 0)
     return out, (stats.get() if want_stats else None)
 
 
@@ -378,13 +372,12 @@ class DenseTensor(Tensor):
         upload, host NumPy otherwise."""
         if not _dense_current(self):
             return super().norm()
-        import ctypes
         from . import _native as nat
         arr = self.dev_data()
         if not (arr.is_contiguous() or arr.T.is_contiguous()):      # a sum over all entries: their order is free
             arr = arr.contiguous()
         out = DevArray.empty((1,))
-        nat.call("ttsk_sumsq", ctypes.c_void_p(arr.ptr), ctypes.c_size_t(arr.size), ctypes.c_void_p(out.ptr), 0)
+        nat.call("ttsk_sumsq", arr, arr.size, out, 0)
         return float(np.sqrt(out.get()[0]))
 
     def dot(self, other, reverse=False) -> float:
@@ -450,15 +443,13 @@ class SparseTensor(Tensor):
     def dev_mode_perm(self, mu: int) -> DevArray:
         """Permutation that visits the nonzeros in order of their (logical) mode-``mu`` index; sorted
         once per tensor and mode on the device and shared with ``.T`` views."""
-        import ctypes
         from . import _native as nat
         idx = self._upload()[0]
         phys = self._order[mu]
         cache = self._dev[2]
         if phys not in cache:
             perm = DevArray.empty((self.nnz,), dtype=np.int64)
-            nat.call("ttsk_sparse_sort_mode", ctypes.c_void_p(idx.ptr + phys * self.nnz * 8),
-                     ctypes.c_size_t(self.nnz), int(self.shape[mu]), ctypes.c_void_p(perm.ptr), 0)
+            nat.call("ttsk_sparse_sort_mode", idx[phys], self.nnz, int(self.shape[mu]), perm, 0)
             cache[phys] = perm
         return cache[phys]
 
@@ -687,7 +678,6 @@ class TensorTrain(_GatherOnDevice, Tensor):
         """Left-orthogonalising QR sweep on the device: thin QR by ``ttsk_qr_thin`` (CholeskyQR2
         with LAPACK's signs, Householder fallback), R recovered as Q^T M by the long-K kernel.
         Same result as ``orthogonalize`` (reference tensor.py:559-572) up to rounding."""
-        import ctypes
         from . import _native as nat
         from .device import contract
         cores = self.dev_cores()
@@ -702,9 +692,9 @@ class TensorTrain(_GatherOnDevice, Tensor):
                 # wide unfolding (m < r2): Q (m x m) from the leading square block, R = Q^T M is m x r2
                 Q = M.copy() if m >= r2 else M[:, :m].contiguous()
                 q = min(m, r2)
-                nat.call("ttsk_qr_thin", ctypes.c_void_p(Q.ptr), m, q, 0)
+                nat.call("ttsk_qr_thin", Q, m, q, 0)
                 carry = contract("ai,aj->ij", Q, M)
-                nat.call("ttsk_triu", ctypes.c_void_p(carry.ptr), q, r2, 0)
+                nat.call("ttsk_triu", carry, q, r2, 0)
                 out.append(Q.reshape(r1, n, q))
             else:
                 out.append(C.contiguous())
@@ -716,7 +706,6 @@ class TensorTrain(_GatherOnDevice, Tensor):
         the SVD of each wide unfolding M (r x n r') goes through the thin QR of M^T and a Jacobi SVD
         of the r x r factor (``ttsk_svd_small``).  Cores stay on the device; they equal ``round``'s
         up to the sign gauge of the singular vectors (the represented tensor is the same)."""
-        import ctypes
         from . import _native as nat
         tt = self if orthogonalized else self.orthogonalize_dev()
         eps = 0 if eps is None else eps
@@ -743,15 +732,14 @@ class TensorTrain(_GatherOnDevice, Tensor):
             else:
                 Mt = C.reshape(r1, k2).T.contiguous()                # (n r2, r1), tall
                 Qc = Mt.copy()
-                nat.call("ttsk_qr_thin", ctypes.c_void_p(Qc.ptr), k2, r1, 0)
+                nat.call("ttsk_qr_thin", Qc, k2, r1, 0)
                 Rc = contract("ai,aj->ij", Qc, Mt)                   # (r1, r1) upper triangular
-                nat.call("ttsk_triu", ctypes.c_void_p(Rc.ptr), r1, r1, 0)
+                nat.call("ttsk_triu", Rc, r1, r1, 0)
                 A = Rc.T.contiguous()                                # M = Rc^T Qc^T
             if r1 > 1024:
                 raise ValueError(f"round_dev: TT rank {r1} > 1024 is beyond the one-workgroup SVD; use round()")
             US, S, Vt = DevArray.empty((r1, r1)), DevArray.empty((r1,)), DevArray.empty((r1, r1))
-            nat.call("ttsk_svd_small", ctypes.c_void_p(A.ptr), r1, r1, ctypes.c_void_p(US.ptr),
-                     ctypes.c_void_p(S.ptr), ctypes.c_void_p(Vt.ptr), 0)
+            nat.call("ttsk_svd_small", A, r1, r1, US, S, Vt, 0)
             sv = S.get()
             r = max(1, min(int(np.sum(sv > sv[0] * eps)), cap[k - 1], k2))
             if Qc is None:

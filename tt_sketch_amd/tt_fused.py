@@ -8,7 +8,6 @@ contractions as ``TensorTrainDRM.sketch_tt`` + ``sketch_omega_tt`` / ``sketch_ps
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -18,7 +17,6 @@ from .device import DevArray
 from .drm.tensor_train_drm import TensorTrainDRM
 from .tensor import TensorSum, TensorTrain
 
-_I64 = ctypes.c_int64
 MAX_BATCH = 32   # tensors per batched pass (SK_MAXB in csrc/skinny.h); the library slices larger batches itself
 
 
@@ -31,7 +29,7 @@ class TTSketchPlan:
         self.d = d
         self.shape = tuple(int(x) for x in shape)
         self.tt_rank = tuple(int(x) for x in tt_rank)
-        arr = lambda v: (_I64 * len(v))(*[int(x) for x in v])
+        arr = nat.i64_array
         self.n = arr(self.shape)
         self.s = arr((1,) + self.tt_rank + (1,))
         self.lt = arr((1,) + tuple(left_drm.true_rank))
@@ -47,9 +45,8 @@ class TTSketchPlan:
             want = (self.rt[k], self.shape[d - 1 - k], self.rt[k + 1])
             if tuple(c.shape) != want:
                 raise ValueError(f"right DRM core {k} has shape {c.shape}, expected {want}")
-        P = ctypes.c_void_p
-        self.DL = (P * (d - 1))(*[c.contiguous().ptr for c in self._keep[0]])
-        self.DR = (P * (d - 1))(*[c.contiguous().ptr for c in self._keep[1]])
+        self.DL = nat.ptr_array([c.contiguous() for c in self._keep[0]])
+        self.DR = nat.ptr_array([c.contiguous() for c in self._keep[1]])
         self.left_rank = tuple(left_drm.rank)
         self.right_rank = tuple(right_drm.rank[::-1])
         self.size = int(nat.lib().ttsk_tt_sketch_size(d, self.n, self.l_lo, self.l_hi, self.r_lo, self.r_hi))
@@ -63,26 +60,24 @@ class TTSketchPlan:
         if tuple(tt.shape) != self.shape or tuple(tt.rank) != self.tt_rank:
             raise ValueError(f"TT of shape {tt.shape} / rank {tt.rank} does not fit the plan")
         keep = [c.contiguous() for c in cores]
-        return (ctypes.c_void_p * self.d)(*[c.ptr for c in keep]), keep
+        return nat.ptr_array(keep), keep
 
     def run(self, X_ptrs, out: DevArray, accumulate: bool = False, stream: int = 0):
         nat.call("ttsk_tt_sketch", self.d, self.n, self.s, self.lt, self.l_lo, self.l_hi, self.rt,
-                 self.r_lo, self.r_hi, X_ptrs, self.DL, self.DR, ctypes.c_void_p(out.ptr),
-                 1 if accumulate else 0, stream)
+                 self.r_lo, self.r_hi, X_ptrs, self.DL, self.DR, out, 1 if accumulate else 0, stream)
 
     def run_batch(self, X_ptrs, nb: int, out: DevArray, out_stride: int, accumulate: bool = False, stream: int = 0):
         """``nb`` tensors of the plan's signature in one pass: ``X_ptrs`` holds nb * d core pointers
         (tensor-major), sketch ``b`` lands at ``out[b * out_stride:]``."""
         nat.call("ttsk_tt_sketch_batch", nb, self.d, self.n, self.s, self.lt, self.l_lo, self.l_hi, self.rt,
-                 self.r_lo, self.r_hi, X_ptrs, self.DL, self.DR, ctypes.c_void_p(out.ptr),
-                 _I64(out_stride), 1 if accumulate else 0, stream)
+                 self.r_lo, self.r_hi, X_ptrs, self.DL, self.DR, out, out_stride,
+                 1 if accumulate else 0, stream)
 
     def run_sum(self, X_ptrs, nb: int, out: DevArray, accumulate: bool = False, stream: int = 0):
         """The sketch of the SUM of ``nb`` tensors of the plan's signature as one packed sketch at ``out``
         (``ttsk_tt_sketch_sum``: chains per tensor, Psi / Omega contracted over (tensor, rank) at once)."""
         nat.call("ttsk_tt_sketch_sum", nb, self.d, self.n, self.s, self.lt, self.l_lo, self.l_hi, self.rt,
-                 self.r_lo, self.r_hi, X_ptrs, self.DL, self.DR, ctypes.c_void_p(out.ptr),
-                 1 if accumulate else 0, stream)
+                 self.r_lo, self.r_hi, X_ptrs, self.DL, self.DR, out, 1 if accumulate else 0, stream)
 
     def views(self, out: DevArray) -> Tuple[List[DevArray], List[DevArray]]:
         """Psi / Omega arrays as views into the packed (contiguous) buffer."""
@@ -135,12 +130,8 @@ def try_stream_sketch(tensor, left_drm, right_drm, method) -> Optional[Tuple[lis
         plan0 = plan0 or plan
         if out is None:
             out = DevArray.empty((plan.size,))
-        keep, flat = [], []
-        for tt in tts:
-            ptrs, k = plan.core_pointers(tt)
-            keep.append(k)
-            flat += [ptrs[i] for i in range(plan.d)]
-        plan.run_sum((ctypes.c_void_p * len(flat))(*flat), len(tts), out, accumulate=not first)
+        cores = [c for tt in tts for c in plan.core_pointers(tt)[1]]
+        plan.run_sum(nat.ptr_array(cores), len(tts), out, accumulate=not first)
         first = False
     return plan0.views(out)
 
@@ -181,18 +172,16 @@ def try_orth_sketch(tensor, left_drm, right_drm, method) -> Optional[Tuple[list,
         return None
     if any(tuple(m.rank_min) != (0,) * (d - 1) or tuple(m.rank_max) != tuple(m.true_rank) for m in drms):
         return None                                   # a rank slice of a blocked sketch: the general path
-    arr = lambda v: (_I64 * len(v))(*[int(x) for x in v])
-    P = ctypes.c_void_p
+    arr = nat.i64_array
     n, s = arr(tensor.shape), arr((1,) + tuple(tensor.rank) + (1,))
     rt = arr((1,) + tuple(right_drm.true_rank))
     keep = [[c.contiguous() for c in tensor.dev_cores()], [c.contiguous() for c in right_drm.dev_cores()]]
-    X = (P * d)(*[c.ptr for c in keep[0]])
-    DR = (P * (d - 1))(*[c.ptr for c in keep[1]])
+    X, DR = nat.ptr_array(keep[0]), nat.ptr_array(keep[1])
     right_rank = tuple(right_drm.rank[::-1])
     if orth:
         lt = arr((1,) + tuple(left_drm.true_rank))
         keep.append([c.contiguous() for c in left_drm.dev_cores()])
-        DL = (P * (d - 1))(*[c.ptr for c in keep[2]])
+        DL = nat.ptr_array(keep[2])
         out_rank = tuple(left_drm.rank)
         om_shapes = [(out_rank[mu], right_rank[mu]) for mu in range(d - 1)]
     else:
@@ -202,9 +191,9 @@ def try_orth_sketch(tensor, left_drm, right_drm, method) -> Optional[Tuple[list,
     # every output of the call in ONE allocation (a dozen pool round trips cost the host more than the device idles for)
     arrs = _carve([(kr[mu], tensor.shape[mu], kr[mu + 1]) for mu in range(d)] + om_shapes)
     cores, Omega = arrs[:d], arrs[d:]
-    om = (P * (d - 1))(*[o.ptr for o in Omega]) if orth else None
+    om = nat.ptr_array(Omega) if orth else None
     try:
-        nat.call("ttsk_tt_orth_sketch", d, n, s, lt, rt, X, DL, DR, (P * d)(*[c.ptr for c in cores]), om, 0)
+        nat.call("ttsk_tt_orth_sketch", d, n, s, lt, rt, X, DL, DR, nat.ptr_array(cores), om, 0)
     except nat.TtskUnsupported:
         return None
     return cores, Omega
@@ -234,18 +223,16 @@ def try_orth_sketch_batch(tensors, left_drm, right_drm, method):
     if any(tuple(m.rank_min) != (0,) * (d - 1) or tuple(m.rank_max) != tuple(m.true_rank) for m in drms):
         return None
     B = len(tensors)
-    arr = lambda v: (_I64 * len(v))(*[int(x) for x in v])
-    P = ctypes.c_void_p
+    arr = nat.i64_array
     n, s = arr(first.shape), arr((1,) + tuple(first.rank) + (1,))
     rt = arr((1,) + tuple(right_drm.true_rank))
     keep = [[c.contiguous() for t in tensors for c in t.dev_cores()], [c.contiguous() for c in right_drm.dev_cores()]]
-    X = (P * (B * d))(*[c.ptr for c in keep[0]])
-    DR = (P * (d - 1))(*[c.ptr for c in keep[1]])
+    X, DR = nat.ptr_array(keep[0]), nat.ptr_array(keep[1])
     right_rank = tuple(right_drm.rank[::-1])
     if orth:
         lt = arr((1,) + tuple(left_drm.true_rank))
         keep.append([c.contiguous() for c in left_drm.dev_cores()])
-        DL = (P * (d - 1))(*[c.ptr for c in keep[2]])
+        DL = nat.ptr_array(keep[2])
         out_rank = tuple(left_drm.rank)
         om_shapes = [(out_rank[mu], right_rank[mu]) for mu in range(d - 1)]
     else:
@@ -255,11 +242,11 @@ def try_orth_sketch_batch(tensors, left_drm, right_drm, method):
     per = [(kr[mu], first.shape[mu], kr[mu + 1]) for mu in range(d)] + om_shapes
     arrs = _carve(per * B)
     outs = [(arrs[b * len(per):b * len(per) + d], arrs[b * len(per) + d:(b + 1) * len(per)]) for b in range(B)]
-    cores = (P * (B * d))(*[c.ptr for o in outs for c in o[0]])
-    om = (P * (B * (d - 1)))(*[c.ptr for o in outs for c in o[1]]) if orth else None
+    cores = nat.ptr_array([c for o in outs for c in o[0]])
+    om = nat.ptr_array([c for o in outs for c in o[1]]) if orth else None
     status = DevArray.zeros(((B + 1) // 2,), dtype=np.int64)         # B int32 verdicts
     try:
-        nat.call("ttsk_tt_orth_sketch_batch", B, d, n, s, lt, rt, X, DL, DR, cores, om, P(status.ptr), 0)
+        nat.call("ttsk_tt_orth_sketch_batch", B, d, n, s, lt, rt, X, DL, DR, cores, om, status, 0)
     except nat.TtskUnsupported:
         return None
     return outs, status

@@ -17,7 +17,6 @@ the tests use as checker).  No CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional
 
 import numpy as np
@@ -41,19 +40,18 @@ def _inv_singular(sv: np.ndarray, m: int) -> np.ndarray:
 def _svd_wide(M: DevArray, cap: int):
     """(U_r (m, r), remainder (r, cols)) of M (m, cols) with r = max(min(min(m, cols), cap), 1)."""
     m, cols = M.shape
-    P = ctypes.c_void_p
     if cols >= m:
         if m > _SVD_MAX:
             raise ValueError(f"tt_svd: unfolding with {m} rows is beyond the Jacobi SVD (<= {_SVD_MAX}); "
                              "lower the rank cap of the previous mode")
         Q = DevArray.empty((cols, m))
         copy_into(Q, M.T)                                       # M^T, tall
-        nat.call("ttsk_qr_thin", P(Q.ptr), cols, m, 0)
+        nat.call("ttsk_qr_thin", Q, cols, m, 0)
         R = contract("ai,ja->ij", Q, M)                         # Q^T M^T = R (m, m), upper triangular
-        nat.call("ttsk_triu", P(R.ptr), m, m, 0)
+        nat.call("ttsk_triu", R, m, m, 0)
         A = R.T.contiguous()                                    # M = R^T Q^T
         US, S, Vt = DevArray.empty((m, m)), DevArray.empty((m,)), DevArray.empty((m, m))
-        nat.call("ttsk_svd_small", P(A.ptr), m, m, P(US.ptr), P(S.ptr), P(Vt.ptr), 0)
+        nat.call("ttsk_svd_small", A, m, m, US, S, Vt, 0)
         r = max(min(m, cap), 1)
         sv = S.get()[:r]
         inv = DevArray.from_host(_inv_singular(sv, m))
@@ -67,7 +65,7 @@ def _svd_wide(M: DevArray, cap: int):
         raise ValueError(f"tt_svd: tall unfolding with {cols} columns is beyond the Jacobi SVD (<= {_SVD_MAX})")
     A = M.contiguous()
     US, S, Vt = DevArray.empty((m, cols)), DevArray.empty((cols,)), DevArray.empty((cols, cols))
-    nat.call("ttsk_svd_small", P(A.ptr), m, cols, P(US.ptr), P(S.ptr), P(Vt.ptr), 0)
+    nat.call("ttsk_svd_small", A, m, cols, US, S, Vt, 0)
     r = max(min(cols, cap), 1)
     sv = S.get()[:r]
     inv = DevArray.from_host(_inv_singular(sv, m))

@@ -83,8 +83,7 @@ def pinv_dev(Omega, rcond=None, stream=0) -> DevArray:
     Om = as_dev(Omega, stream).contiguous(stream)
     l, r = Om.shape
     P = DevArray.empty((r, l), stream=stream)
-    nat.call("ttsk_pinv", ctypes.c_void_p(Om.ptr), l, r, -1.0 if rcond is None else float(rcond),
-             ctypes.c_void_p(P.ptr), None, stream)
+    nat.call("ttsk_pinv", Om, l, r, -1.0 if rcond is None else float(rcond), P, None, stream)
     return P
 
 
@@ -99,10 +98,10 @@ def pinv_dev_many(Omegas, rcond=None, streams=None):
         for k, st in zip(range(lo, min(lo + len(streams), len(Omegas))), streams):
             Om = as_dev(Omegas[k], st).contiguous(st)
             P = DevArray.empty((Om.shape[1], Om.shape[0]), stream=st)
-            nat.call("ttsk_pinv_begin", ctypes.c_void_p(Om.ptr), Om.shape[0], Om.shape[1], rc, ctypes.c_void_p(P.ptr), st)
+            nat.call("ttsk_pinv_begin", Om, Om.shape[0], Om.shape[1], rc, P, st)
             group.append((k, st, Om, P))
         for k, st, Om, P in group:
-            nat.call("ttsk_pinv_end", ctypes.c_void_p(Om.ptr), Om.shape[0], Om.shape[1], rc, ctypes.c_void_p(P.ptr), None, st)
+            nat.call("ttsk_pinv_end", Om, Om.shape[0], Om.shape[1], rc, P, None, st)
             out[k] = P
     return out
 
@@ -150,8 +149,7 @@ def random_normal_dev(shape, seed=None, scale: float = 1.0, stream=0) -> DevArra
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
     out = DevArray.empty(shape, stream=stream)
-    nat.call("ttsk_fill_normal", ctypes.c_void_p(out.ptr), ctypes.c_size_t(out.size),
-             ctypes.c_uint64(int(seed) % 2**64), float(scale), stream)
+    nat.call("ttsk_fill_normal", out, out.size, int(seed) % 2**64, float(scale), stream)
     return out
 
 
@@ -161,8 +159,8 @@ def random_normal_dev_many(shapes, seeds, scales, stream=0):
     outs = [DevArray.empty(tuple(sh), stream=stream) for sh in shapes]
     k = len(outs)
     if k:
-        nat.call("ttsk_fill_normal_many", k, (ctypes.c_void_p * k)(*[o.ptr for o in outs]),
-                 (ctypes.c_size_t * k)(*[o.size for o in outs]), (ctypes.c_uint64 * k)(*[int(s) % 2**64 for s in seeds]),
+        nat.call("ttsk_fill_normal_many", k, nat.ptr_array(outs), (ctypes.c_size_t * k)(*[o.size for o in outs]),
+                 (ctypes.c_uint64 * k)(*[int(s) % 2**64 for s in seeds]),
                  (ctypes.c_double * k)(*[float(c) for c in scales]), stream)
     return outs
 
