@@ -1,7 +1,7 @@
 """Every kernel family behind ttsk_gemm (gemm.hip), at its dispatch edges, element by element.
 
 Each case of CASES names the family it is meant to reach, as a regular expression matched at the start of the kernel
-name the profiling hooks record (tt_fused.hip prof_open / prof_open_named), and the number of bracketed launches.
+name the launcher's profiling bracket records (csrc/prof.h ProfBracket), and the number of bracketed launches.
 An untagged ttsk_gemm call files under the last profiling class, 11.  Branches the name does not show (the skinny_r
 operand variant, swap, rebase, nsub) are stated in the case's comment, with the line of skinny.hip try_r its shape
 takes, and in its coverage tags; test_family_table_covers_every_branch checks the union of the tags.
@@ -46,7 +46,7 @@ PAD = 1e300                         # operand elements outside the view
 # C guards and, with accumulate off, C itself before the call: finite and not a multiple of 1/2, so an unwritten
 # element fails the integer pass and a stray accumulating store changes it (NaN + x would give the NaN back)
 SENT = np.float64(-1.0 / 3.0).view(np.uint64)
-PROF_CLS = 11                       # untagged ttsk_gemm calls (tt_fused.hip NCLS - 1)
+PROF_CLS = 11                       # untagged ttsk_gemm calls (csrc/prof.h PROF_OTHER)
 DESC = "bmoi,boin->bmn"             # the descriptor form: A[b,m,ko,ki], B[b,ko,ki,n], C[b,m,n]
 
 

@@ -1,6 +1,7 @@
 // Host side of the fused chain step (chain_fused.h): shape tests, LDS plan, launch geometry.
 #include <cstdlib>
 #include "chain_fused.h"
+#include "prof.h"
 
 namespace ttsk {
 
@@ -117,10 +118,10 @@ int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool for
     const int64_t nslab = (int64_t)c.nb * wpp;
     a.slab = (double *)scratch(stream, SCRATCH_GEMM, (size_t)nslab * c.J * c.A2 * 8 + 64);
     if (!a.slab) return TTSK_ERR_HIP;
-    const bool prof = prof_on();
-    // flops of BOTH products of the step (the pair this kernel replaces), reduce launch inside the bracket
-    if (prof) prof_open(st, 2.0 * c.nb * (double)c.n * c.J * ((double)c.K1 * c.A + (double)c.A * c.A2), 6,
-                        nq * 100 + sq * 10 + (wt ? 1 : 0), unr == 25, false);
+    // flops of BOTH products of the step (the pair this kernel replaces), reduce launch inside the bracket; the name as
+    // profiles/*_traffic.json is keyed by it: the nine parameters from before the deal (no NWV), NN / SN given as NQ / SQ
+    ProfBracket prof(st, PROF_CURRENT, 2.0 * c.nb * (double)c.n * c.J * ((double)c.K1 * c.A + (double)c.A * c.A2),
+                     "chain_step_kernel<%d, %d, %d, %d, 5, %s, 1, %d, %d>", nq, sq, nq, sq, wt ? "true" : "false", ebuf, unr);
 #ifdef TTSK_LAB
     static int stamps_on = [] { const char *e = getenv("TTSK_CF_STAMPS"); return e ? atoi(e) : 0; }();
 #else
@@ -154,7 +155,6 @@ int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool for
         for (int b = 0; b < c.nb; ++b) ro.C[b] = c.Out[b];
         rc = launch_r_reduce(st, a.slab, wpp, c.J, c.A2, 1, (int64_t)c.J, ro, c.nb, (int64_t)c.A2, (int64_t)1, 1.0, 0);
     }
-    if (prof) prof_close(st);
     return rc == TTSK_OK ? 1 : (rc == 1 ? 0 : rc);
 }
 

@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 #include "chain_sum.h"
+#include "prof.h"
 
 namespace ttsk {
 
@@ -266,9 +267,8 @@ int chain_sum_try(const ChainSumArgs &cc, int stream, hipStream_t st, bool force
     const int64_t nslab = (int64_t)c.nb * nr;
     a.slab = (double *)scratch(stream, SCRATCH_GEMM, (size_t)nslab * c.J * c.A2 * 8 + 64);
     if (!a.slab) return TTSK_ERR_HIP;
-    const bool prof = prof_on();
-    if (prof) prof_open_named(st, -2, 2.0 * c.nb * (double)c.n * c.J * ((double)c.K1 * c.A + (double)c.A * c.A2),
-                              a.T ? "chain_sum_kernel<5, 5, NA, true>" : "chain_sum_kernel<5, 5, NA, false>");
+    ProfBracket prof(st, PROF_CURRENT, 2.0 * c.nb * (double)c.n * c.J * ((double)c.K1 * c.A + (double)c.A * c.A2),
+                     "chain_sum_kernel<5, 5, NA, %s>", a.T ? "true" : "false");
 #ifdef TTSK_LAB
     static int stamps_on = [] { const char *e = getenv("TTSK_CS_STAMPS"); return e ? atoi(e) : 0; }();
     long long *stamps_dev = nullptr;
@@ -311,7 +311,6 @@ int chain_sum_try(const ChainSumArgs &cc, int stream, hipStream_t st, bool force
         for (int b = 0; b < c.nb; ++b) ro.C[b] = c.Out[b];
         rc = launch_r_reduce(st, a.slab, nr, c.J, c.A2, 1, (int64_t)c.J, ro, c.nb, (int64_t)c.A2, (int64_t)1, 1.0, 0);
     }
-    if (prof) prof_close(st);
     return rc == TTSK_OK ? 1 : rc;
 }
 

@@ -2,6 +2,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "chain_wide.h"
+#include "prof.h"
 
 namespace ttsk {
 
@@ -173,20 +174,15 @@ int chain_wide_try(const ChainStepArgs &c, int stream, hipStream_t st, bool forc
     const int64_t nslab = (int64_t)c.nb * units;
     a.slab = (double *)scratch(stream, SCRATCH_GEMM, (size_t)nslab * c.J * c.A2 * 8 + 64);
     if (!a.slab) return TTSK_ERR_HIP;
-    const bool prof = prof_on();
-    if (prof) {
-        char name[96];
-        snprintf(name, sizeof(name), "chain_wide_kernel<%d, %d, %d, %d, %s, %d, %s>", CW_NQ[ci], CW_SQ[ci], nn, sn, wt ? "true" : "false", unr,
-                 (CW_NQ[ci] <= 3 && nn + (sn ? 1 : 0) <= 7) ? "true" : "false");
-        prof_open_named(st, -2, 2.0 * c.nb * (double)c.n * c.J * ((double)c.K1 * c.A + (double)c.A * c.A2), name);
-    }
+    ProfBracket prof(st, PROF_CURRENT, 2.0 * c.nb * (double)c.n * c.J * ((double)c.K1 * c.A + (double)c.A * c.A2),
+                     "chain_wide_kernel<%d, %d, %d, %d, %s, %d, %s>", CW_NQ[ci], CW_SQ[ci], nn, sn, wt ? "true" : "false", unr,
+                     (CW_NQ[ci] <= 3 && nn + (sn ? 1 : 0) <= 7) ? "true" : "false");
     int rc = launch_chain_wide(ci, a, nn, sn, wt, unr, lds, ng * units, st);
     if (rc == TTSK_OK) {
         ReduceOut ro{};
         for (int b = 0; b < c.nb; ++b) ro.C[b] = c.Out[b];
         rc = launch_r_reduce(st, a.slab, units, c.J, c.A2, 1, (int64_t)c.J, ro, c.nb, (int64_t)c.A2, (int64_t)1, 1.0, 0);
     }
-    if (prof) prof_close(st);
     return rc == TTSK_OK ? 1 : (rc == 1 ? 0 : rc);
 }
 

@@ -83,13 +83,6 @@ __device__ __forceinline__ v4d mfma16(double a, double b, v4d c)
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
-// per-launch device timing hooks (implemented in tt_fused.hip, used by ttsk_gemm)
-bool prof_on();
-void prof_open(hipStream_t st, double flops, int family, int tiles, bool ak, bool bk);
-void prof_close(hipStream_t st);
-enum { PROF_SAMPLER = 6, PROF_SPARSE = 7, PROF_SOLVE = 8 };
-void prof_open_named(hipStream_t st, int cls, double work, const char *name);   // work in the class's own unit
-
 // dense_right_pass.hip: C[m][n] (+)= alpha sum_k S[m][k] B[n][k], both rows contiguous along a long k, n <= 48: 1 = launched, 0 = not covered
 int rows_longk_try(const double *S, int64_t rows, int64_t s_row, const double *B, int N, int64_t b_row, int64_t K, double *C,
                    int64_t c_row, double alpha, int accumulate, int stream, hipStream_t st);

@@ -23,6 +23,7 @@
 // workgroups per CU in turn), bytes: X once + A_3 once + Z_0 written = 14 GB.
 #include <type_traits>
 #include "common.h"
+#include "prof.h"
 #include "skinny.h"
 
 namespace ttsk {
@@ -285,8 +286,7 @@ extern "C" int ttsk_dense_left_pass(const double *X, int64_t n0, int64_t n1, int
     a.slab3 = ws + slab;
     const size_t lds = ((size_t)4 * 4 * LP_XP + (size_t)4 * (((3 + a.ni3) * 80 + 127) / 128 * 128 + 128)) * 8;
     const unsigned grid = (unsigned)(n2 * a.nct);
-    const bool prof = prof_on();
-    if (prof) prof_open_named(st, -2, 8.0 * l * (double)n0 * n1 * n2 * C, "dense_left_pass_kernel");
+    ProfBracket prof(st, PROF_CURRENT, 8.0 * l * (double)n0 * n1 * n2 * C, "dense_left_pass_kernel");
     int rc = launch(l > 16 ? dense_left_pass_kernel<true> : dense_left_pass_kernel<false>, dim3(grid), dim3(512), lds, st, a);
     if (rc != TTSK_OK) return rc;
     // Z_2 = sum_{i2} slab2[i2], E_3 likewise: the slabs are [chunk = i2][M = l][N = C]
@@ -295,6 +295,5 @@ extern "C" int ttsk_dense_left_pass(const double *X, int64_t n0, int64_t n1, int
     r3.C[0] = E3;
     rc = launch_r_reduce(st, a.slab2, (int)n2, l, (int)C, 1, (int64_t)l, r2, 1, C, 1, 1.0, 0);
     if (rc == TTSK_OK) rc = launch_r_reduce(st, a.slab3, (int)n2, l, (int)C, 1, (int64_t)l, r3, 1, C, 1, 1.0, 0);
-    if (prof) prof_close(st);
     return rc;
 }

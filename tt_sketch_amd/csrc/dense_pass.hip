@@ -36,6 +36,7 @@
 // accumulator registers at 4 + 0) -- a first mode of 64 is then two blocks, their partial Z summed as for longer modes.  An odd
 // r reads a copy of P padded to r + 1 columns (16-byte units need an even row).
 #include "common.h"
+#include "prof.h"
 #include <type_traits>
 
 namespace ttsk {
@@ -441,7 +442,7 @@ extern "C" int ttsk_dense_first_pass(const double *X, int64_t n0, int64_t Q, int
     constexpr int dbg = 0;
 #endif
     DensePass a{X, Q * T, (int)Q, (int)T, C, (int)ll, P, (int)r, (int)pr, zout, slab, nt, (int)nqc, zblock, split ? 1 : 0, p_half, z_half, dbg};
-    if (prof_on()) prof_open_named(st, PROF_SOLVE, 0.0, "dense_pass");
+    ProfBracket prof(st, PROF_SOLVE, 0.0, "dense_pass");             // the whole sequence: pass, reduces, sum over the blocks
     int rc;
     if (one_kind) rc = dense_pass_launch<8, 2, 3, 1, 2>(a, grid, st);
     else if (split) {
@@ -463,6 +464,5 @@ extern "C" int ttsk_dense_first_pass(const double *X, int64_t n0, int64_t Q, int
         const int64_t pairs = zblock / 2;               // Q T is a multiple of 128
         if ((rc = launch(dense_pass_zsum, dim3((unsigned)cdiv(pairs, 256)), dim3(256), 0, st, (const double2 *)zout, nbb, pairs, (double2 *)Z))) return rc;
     }
-    if (prof_on()) prof_close(st);
     return TTSK_OK;
 }

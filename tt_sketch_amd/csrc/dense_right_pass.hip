@@ -16,6 +16,7 @@
 // Work per stage: 10 k cycles of the matrix pipes for 57 KB of operands: HBM-bound (the operands once).  Partial results per
 // (row block, K range) go to slabs, summed by skinny_r_reduce in range order (no atomics).
 #include "common.h"
+#include "prof.h"
 #include "skinny.h"
 
 namespace ttsk {
@@ -162,15 +163,13 @@ int rows_longk_try(const double *S, int64_t rows, int64_t s_row, const double *B
     a.nrb = (int)nrb; a.nkc = (int)nkc;
     a.slab = (double *)scratch(stream, SCRATCH_GEMM, (size_t)nrb * nkc * 64 * N * 8 + 64);
     if (!a.slab) return TTSK_ERR_HIP;
-    const bool prof = prof_on();
-    if (prof) prof_open_named(st, -2, 2.0 * rows * (double)N * K, "rows_longk_kernel");
+    ProfBracket prof(st, PROF_CURRENT, 2.0 * rows * (double)N * K, "rows_longk_kernel");
     int rc = launch(rows_longk_kernel, dim3((unsigned)(nrb * nkc)), dim3(512), (size_t)2 * (64 + RP_BROWS) * 64 * 8, st, a);
     if (rc == TTSK_OK) {
         ReduceOut ro{};
         ro.C[0] = C;
         rc = launch_r_reduce(st, a.slab, (int)nkc, 64, N, (int)nrb, rows, ro, 1, c_row, 1, alpha, accumulate);
     }
-    if (prof) prof_close(st);
     return rc == TTSK_OK ? 1 : rc;
 }
 

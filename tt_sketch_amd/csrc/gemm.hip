@@ -15,6 +15,7 @@
 // Split-K over (ko,ki) through gridDim.z with fp64 global atomics.
 #include <cstdlib>
 #include "gemm_kernel.h"
+#include "prof.h"
 #include "skinny.h"
 
 namespace ttsk {
@@ -331,13 +332,16 @@ int ttsk_gemm(const ttsk_gemm_desc *dp, const double *A, const double *B, double
     GemmLaunch g{d, A, B, k_scale, C, partial, p.family, p.tiles, splits, avec, bvec, fast_ok, kchunk, p.bm, p.bn,
                  a_extent, b_extent};
     int rc;
-    const bool prof = prof_on();
-    if (prof) prof_open(st, 2.0 * (double)d.batch * (double)d.M * (double)d.N * (double)K, p.family, p.tiles, ak, bk);
+    // the tile kernel alone, not the split-K reduce: <waves along m, n, tiles per wave along m, n, layouts>
+    const int wm = p.family == 0 ? 2 : (p.family == 1 ? 1 : 4), wn = p.family == 0 ? 2 : (p.family == 1 ? 4 : 1);
+    const int tm = p.family == 0 ? 2 : (p.family == 1 ? p.tiles : 1), tn = p.family == 0 ? 2 : (p.family == 1 ? 1 : p.tiles);
+    ProfBracket prof(st, PROF_CURRENT, 2.0 * (double)d.batch * (double)d.M * (double)d.N * (double)K,
+                     "gemm_f64_kernel<%d, %d, %d, %d, %s, %s>", wm, wn, tm, tn, ak ? "true" : "false", bk ? "true" : "false");
     if (ak && bk) rc = launch_gemm_layout<true, true>(g, st);
     else if (ak) rc = launch_gemm_layout<true, false>(g, st);
     else if (bk) rc = launch_gemm_layout<false, true>(g, st);
     else rc = launch_gemm_layout<false, false>(g, st);
-    if (prof) prof_close(st);
+    prof.close();
     if (rc || !partial) return rc;
     return launch_splitk_reduce(d, partial, C, splits, tiles_m, tiles_n, p.family == 2 ? 1 : 0, st);
 }

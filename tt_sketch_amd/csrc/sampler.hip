@@ -7,6 +7,7 @@
 #include <cmath>
 #include <vector>
 #include "common.h"
+#include "prof.h"
 #include "sampler_dev.h"
 
 namespace ttsk {
@@ -396,11 +397,7 @@ int ttsk_sparse_normal_dev(const int64_t *dev_idx, int64_t row_stride, const int
     // copied out -- 0.25 instead of 0.78 ms per mode at C4.  Only without the reference's 32-bit wrap of the
     // multipliers (fast_lazy_gaussian.pyx:60-71), i.e. when the flat index really is < prod(shape).
     const int w = rank_max - rank_min;
-    struct ProfScope {      // device time of the whole sampling pass (work unit: Gaussian samples delivered)
-        hipStream_t st; bool on;
-        ProfScope(hipStream_t s, double samples) : st(s), on(prof_on()) { if (on) prof_open_named(st, PROF_SAMPLER, samples, "sample_rows_kernel / expand_rows_kernel"); }
-        ~ProfScope() { if (on) prof_close(st); }
-    } prof_scope(st, (double)tot);
+    ProfBracket prof(st, PROF_SAMPLER, (double)tot, "sample_rows_kernel / expand_rows_kernel");   // the whole sampling pass
     double prod = 1.0;
     for (int i = 0; i < m; ++i) prod *= (double)shape[i];
     if (w <= 32 && prod * 4.0 <= (double)N && prod < 16777216.0) {
@@ -430,11 +427,8 @@ int ttsk_sparse_normal_table(const uint64_t *shape, int m, int rank_min, int ran
         set_error("ttsk_sparse_normal_table: %g prefixes: the reference's 32-bit running product wraps", prod);
         return TTSK_ERR_UNSUPPORTED;
     }
-    const bool prof = prof_on();
-    if (prof) prof_open_named(st, PROF_SAMPLER, prod * (rank_max - rank_min), "sample_rows_kernel (prefix table)");
-    rc = launch_sample<1>(nullptr, im, (size_t)prod, rank_min, rank_max - rank_min, seed, dev_out, st);
-    if (prof) prof_close(st);
-    return rc;
+    ProfBracket prof(st, PROF_SAMPLER, prod * (rank_max - rank_min), "sample_rows_kernel (prefix table)");
+    return launch_sample<1>(nullptr, im, (size_t)prod, rank_min, rank_max - rank_min, seed, dev_out, st);
 }
 
 int ttsk_sparse_sign_dev(const int64_t *dev_idx, int64_t row_stride, const int *row_order,

@@ -1,6 +1,7 @@
 // Host side of the barrier-free chain kernels (skinny.h): shape tests and launch geometry.
 #include <cstdlib>
 #include "skinny.h"
+#include "prof.h"
 
 namespace ttsk {
 
@@ -159,7 +160,7 @@ static int num_cu()
 }
 
 // C[m, j] = alpha sum_k W[k, m] S[j, k]
-static int run_s(SkinnyS a, hipStream_t st, int *prof, double flops)
+static int run_s(SkinnyS a, hipStream_t st, double flops)
 {
     const int npt = (int)cdiv(a.P, 16);
     const int kb = (a.K + 3) / 4;
@@ -188,7 +189,7 @@ static int run_s(SkinnyS a, hipStream_t st, int *prof, double flops)
     // partial last tile of W with <= 8 valid columns: 4-wide strips instead of a padded 16x16x4 tile
     const int rem = (int)(a.P % 16);
     const int str = (rem > 0 && rem <= 8) ? (rem + 3) / 4 : 0;
-    if (prof) prof_open(st, flops, 3, str * 1000 + npt * 100 + spt, str > 0, dring == 4);
+    ProfBracket prof(st, PROF_CURRENT, flops, "skinny_s_kernel<%d, %d, %d, %d>", npt, spt, dring, str);
 #define TTSK_S_GO(D) (str == 2 ? launch_skinny_s_depth<D, 2>(a, npt, spt, lds, grid, st) \
                       : str == 1 ? launch_skinny_s_depth<D, 1>(a, npt, spt, lds, grid, st) \
                                  : launch_skinny_s_depth<D, 0>(a, npt, spt, lds, grid, st))
@@ -283,16 +284,15 @@ static int try_r(const ttsk_gemm_desc &d, int nb, const double *const *A, const 
     const int64_t nslab = (int64_t)nb * r.m_tiles * chunks;
     r.slab = (double *)scratch(stream, SCRATCH_GEMM, (size_t)nslab * nsub * r.M * r.N * 8 + 64);
     if (!r.slab) return TTSK_ERR_HIP;
-    const bool prof = prof_on();
     int rc;
     // (a chunk -> XCD mapping that makes all problems of a batch fetch the shared operand into one L2
     // halved the L2-fabric traffic of the batched GEMM2 but not its time)
-    if (prof) prof_open(st, 2.0 * nb * (double)d.M * (double)d.N * (double)K, 4, nmt * 10 + nnt, false, false);
+    ProfBracket prof(st, PROF_CURRENT, 2.0 * nb * (double)d.M * (double)d.N * (double)K, "skinny_r_kernel<%d, %d, 4>", nmt, nnt);
     if (nmt <= 4) rc = launch_skinny_r_0(r, nmt, nnt, (int)nslab, st);
     else if (nmt <= 6) rc = launch_skinny_r_1(r, nmt, nnt, (int)nslab, st);
     else if (nmt == 7) rc = launch_skinny_r_2(r, nmt, nnt, (int)nslab, st);
     else rc = launch_skinny_r_3(r, nmt, nnt, (int)nslab, st);
-    if (prof) prof_close(st);
+    prof.close();                                               // the slab kernel alone, not the reduce
     if (rc != TTSK_OK) return rc;
     const int64_t mn = (int64_t)r.M * r.N;
     ReduceOut ro{};
@@ -376,10 +376,7 @@ int skinny_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, co
     s.big = (reach >= (1ll << 32) - 64 || reach_c >= (1ll << 32) - 64) ? 1 : 0;
     const int npt = (int)cdiv(s.P, 16);
     if ((size_t)((cdiv(K, 4) + 4) * 4 * ldmf(16 * npt) + 16) * 8 + 2048 > 160 * 1024) return 0;
-    const bool prof = prof_on();
-    int sh = 0;
-    int rc = run_s(s, st, prof ? &sh : nullptr, 2.0 * nb * (double)d.batch * (double)d.M * (double)d.N * (double)K);
-    if (prof) prof_close(st);
+    const int rc = run_s(s, st, 2.0 * nb * (double)d.batch * (double)d.M * (double)d.N * (double)K);
     return rc == TTSK_OK ? 1 : rc;
 }
 

@@ -6,6 +6,7 @@
 // workgroup, the partial tiles summed in wave order through LDS.
 // tensor_train_sketch.py:8-19 (Omega), tensor_train_drm.py:79-88 (first mode) in the reference.
 #include <cstdlib>
+#include "prof.h"
 #include "skinny.h"
 
 #ifndef SMALL_DEPTH
@@ -171,11 +172,9 @@ int small_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, con
     g.a_extent = e[0]; g.b_extent = e[1]; g.c_extent = e[2];
     g.alpha = d.alpha;
     g.accumulate = d.accumulate;
-    const bool prof = prof_on();
-    if (prof) prof_open(st, 2.0 * count * (double)d.M * (double)d.N * (double)K, 5, 0, false, false);
+    ProfBracket prof(st, PROF_CURRENT, 2.0 * count * (double)d.M * (double)d.N * (double)K, "small_gemm_kernel");
     const int ksplit = K >= 512 ? 8 : (K >= 256 ? 4 : (K >= 128 ? 2 : 1));
     const int rc = launch(small_gemm_kernel, dim3((unsigned)(count * g.tiles_m * g.tiles_n)), dim3(64 * ksplit), 0, st, g);
-    if (prof) prof_close(st);
     return rc == TTSK_OK ? 1 : rc;
 }
 

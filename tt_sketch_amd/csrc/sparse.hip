@@ -2,6 +2,7 @@
 // Gaussian DRM, and the Psi scatter.  All HBM-bound streaming of (nnz x rank) panels.
 #include <hipcub/hipcub.hpp>
 #include "common.h"
+#include "prof.h"
 
 namespace ttsk {
 
@@ -366,11 +367,9 @@ int ttsk_sparse_psi(const double *dev_val, const int64_t *dev_idx_row, const int
     TTSK_ARG(l >= 1 && r >= 1 && n >= 1, "ttsk_sparse_psi: bad shape");
     TTSK_ARG(dev_idx_row || n == 1, "ttsk_sparse_psi: a NULL index row means a single slice (n = 1)");
     if (N == 0) return TTSK_OK;
-    struct ProfScope {      // device time of the segmented sum (work unit: algorithmic bytes = panels + values + indices)
-        hipStream_t st; bool on;
-        ProfScope(hipStream_t s, double bytes) : st(s), on(prof_on()) { if (on) prof_open_named(st, PROF_SPARSE, bytes, "sparse_psi_mfma_kernel"); }
-        ~ProfScope() { if (on) prof_close(st); }
-    } prof_scope(st, 8.0 * (double)N * (double)((dev_Lv ? l : 0) + (dev_Rv ? r : 0) + 1 + (dev_idx_row ? 1 : 0) + (dev_perm ? 1 : 0)));
+    // the segmented sum, whichever kernel takes it (work unit: algorithmic bytes = panels + values + indices)
+    ProfBracket prof(st, PROF_SPARSE, 8.0 * (double)N * (double)((dev_Lv ? l : 0) + (dev_Rv ? r : 0) + 1 + (dev_idx_row ? 1 : 0) + (dev_perm ? 1 : 0)),
+                     "sparse_psi_mfma_kernel");
     // MFMA kernel: small ranks, and either one slice or mode-sorted input with long slices
     const bool single = dev_idx_row == nullptr || n == 1;
     if (l <= 32 && r <= 32 && N < (1ull << 40) && (single || (dev_perm && N / (size_t)n >= 32))) {

@@ -24,6 +24,7 @@
 #include <type_traits>
 #include <hipcub/hipcub.hpp>
 #include "sampler_dev.h"
+#include "prof.h"
 
 namespace ttsk {
 
@@ -783,8 +784,7 @@ static int sg_gauss_pass(const void *dev_fl, const void *dev_fr, int w32, const 
     a.part_psi = (double *)ws;
     a.part_om = a.part_psi + wtot * 2 * cellsP;
     a.part_j = (int *)(a.part_om + wtot * (size_t)cellsO);
-    const bool prof = prof_on();
-    if (prof) prof_open_named(st, PROF_SPARSE, (w32 ? 20.0 : 28.0) * (double)N, "sg_pass_kernel");
+    ProfBracket prof(st, PROF_SPARSE, (w32 ? 20.0 : 28.0) * (double)N, "sg_pass_kernel");
     auto kern = NT == 1    ? sg_pass_kernel<1, 0, 32>
                 : T == 32  ? (NS == 1 ? sg_pass_kernel<2, 1, 32> : NS == 2 ? sg_pass_kernel<2, 2, 32> : sg_pass_kernel<2, 0, 32>)
                            : (NS == 1 ? sg_pass_kernel<2, 1, 16> : NS == 2 ? sg_pass_kernel<2, 2, 16> : sg_pass_kernel<2, 0, 16>);
@@ -795,7 +795,6 @@ static int sg_gauss_pass(const void *dev_fl, const void *dev_fr, int w32, const 
     if (a.has_om) {
         if ((rc = launch(sg_om_reduce_kernel, dim3((unsigned)cellsO), dim3(256), 0, st, a.part_om, (int)wtot, cellsO, dev_omega))) return rc;
     }
-    if (prof) prof_close(st);
     return TTSK_OK;
 }
 

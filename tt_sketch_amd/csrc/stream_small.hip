@@ -1,6 +1,7 @@
 // Host side of stream_small_kernel (stream_small.h) + its instantiations.
 #include <cstdlib>
 #include "stream_small.h"
+#include "prof.h"
 
 namespace ttsk {
 
@@ -71,10 +72,8 @@ int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st)
         if (((uintptr_t)c.S[b] | (uintptr_t)c.W[b] | (uintptr_t)c.C[b]) & 7) return 0;
         a.S[b] = c.S[b]; a.W[b] = c.W[b]; a.C[b] = c.C[b];
     }
-    const bool prof = prof_on();
-    if (prof) prof_open(st, 2.0 * c.nb * (double)c.J * c.K1 * c.A, 7, nf * 10 + str, unr == 25, false);
+    ProfBracket prof(st, PROF_CURRENT, 2.0 * c.nb * (double)c.J * c.K1 * c.A, "stream_small_kernel<%d, %d, 5, %d>", nf, str, unr);
     const int rc = launch_ss(a, nf, str, unr, lds, c.nb * wpp * nac, st);
-    if (prof) prof_close(st);
     return rc == TTSK_OK ? 1 : (rc == 1 ? 0 : rc);
 }
 
@@ -143,14 +142,8 @@ int stream_small_sum_try(const StreamSmallSumArgs &c, int stream, hipStream_t st
     const int units = groups * nac;
     a.xcd_map = units % 8 == 0 ? 1 : 0;
     const size_t lds = (size_t)2 * 4 * (KB1 + 1) * a.AP * 8;
-    const bool prof = prof_on();
-    if (prof) {
-        char name[96];
-        snprintf(name, sizeof(name), "stream_small_sum_kernel<%d, %d, 5, %d>", nf, str, unr);
-        prof_open_named(st, -2, 2.0 * c.nb * (double)c.J * c.K1 * c.A, name);
-    }
+    ProfBracket prof(st, PROF_CURRENT, 2.0 * c.nb * (double)c.J * c.K1 * c.A, "stream_small_sum_kernel<%d, %d, 5, %d>", nf, str, unr);
     const int rc = launch_sss(a, nf, str, unr, lds, units, st);
-    if (prof) prof_close(st);
     return rc == TTSK_OK ? 1 : (rc == 1 ? 0 : rc);
 }
 

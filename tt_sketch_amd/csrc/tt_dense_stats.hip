@@ -29,6 +29,7 @@
 // wave by a butterfly, the four waves and then the workgroups' quadruples by one workgroup in index order: no atomics,
 // the same bits on every call, with or without the output array.
 #include "common.h"
+#include "prof.h"
 
 namespace ttsk {
 
@@ -39,7 +40,6 @@ constexpr int DS_LP = DS_KC + 2;                    // row pitch of the L image 
 constexpr int DS_RP = DS_BN + 16;                   // row pitch of the R image
 constexpr int DS_LDS_BYTES = (DS_BM * DS_LP + DS_KC * DS_RP) * 8;
 constexpr unsigned DS_MAX_BLOCKS = 4096;
-constexpr int PROF_EVAL = 9;                        // profiling class of the dense evaluation kernels
 
 struct DenseStats {
     const double *L, *R, *X;
@@ -253,12 +253,10 @@ int ttsk_tt_dense_stats_ld(const double *dev_L, int64_t M, const double *dev_R, 
         a.part = (double *)scratch(stream, SCRATCH_MISC, (size_t)blocks * 4 * 8);
         if (!a.part) return TTSK_ERR_HIP;
     }
-    const bool prof = prof_on();
-    if (prof) prof_open_named(st, PROF_EVAL, 2.0 * (double)rho * (double)M * (double)N, "tt_dense_stats_kernel");
+    ProfBracket prof(st, PROF_EVAL, 2.0 * (double)rho * (double)M * (double)N, "tt_dense_stats_kernel");
     int rc = launch(tt_dense_stats_kernel, dim3(blocks), dim3(256), (size_t)DS_LDS_BYTES, st, a);
     if (rc == TTSK_OK && dev_stats)
         rc = launch(dense_sums_reduce_kernel, dim3(1), dim3(256), 0, st, a.part, blocks, 4, dev_stats, accumulate);
-    if (prof) prof_close(st);
     return rc;
 }
 
@@ -279,11 +277,8 @@ int ttsk_sumsq(const double *dev_x, size_t n, double *dev_out, int stream)
     if (blocks) {
         part = (double *)scratch(stream, SCRATCH_MISC, (size_t)blocks * 8);
         if (!part) return TTSK_ERR_HIP;
-        const bool prof = prof_on();
-        if (prof) prof_open_named(st, PROF_EVAL, 2.0 * (double)n, "sumsq_kernel");
-        const int rc = launch(sumsq_kernel, dim3(blocks), dim3(256), 0, st, dev_x, n, part);
-        if (prof) prof_close(st);
-        if (rc != TTSK_OK) return rc;
+        ProfBracket prof(st, PROF_EVAL, 2.0 * (double)n, "sumsq_kernel");      // closed before the reduce below
+        if (int rc = launch(sumsq_kernel, dim3(blocks), dim3(256), 0, st, dev_x, n, part)) return rc;
     }
     return launch(dense_sums_reduce_kernel, dim3(1), dim3(256), 0, st, part, blocks, 1, dev_out, 0);
 }

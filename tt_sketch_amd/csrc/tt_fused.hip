@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <vector>
 #include "common.h"
+#include "prof.h"
 #include "skinny.h"
 #include "chain_fused.h"
 #include "chain_wide.h"
@@ -12,87 +13,6 @@
 #include "stream_small.h"
 
 namespace ttsk {
-
-constexpr int NCLS = 12;      // 0-5 TT pipeline classes, 6 samplers, 7 sparse Psi / Omega, 8 small factorisations, 9-10 free, 11 everything else
-struct ProfRec { hipEvent_t a, b; int cls; double flops; };
-static char g_kname[NCLS][96];
-static double g_kname_flops[NCLS];   // the name kept per class is that of its largest launch
-static bool g_prof = false;
-static int g_cls = NCLS - 1;
-static std::vector<ProfRec> g_recs;
-static int64_t g_launches[NCLS];
-static double g_ms[NCLS], g_flops[NCLS];
-
-static void prof_record(hipStream_t st, int cls, double work)
-{
-    ProfRec r{};
-    (void)hipEventCreate(&r.a);
-    (void)hipEventCreate(&r.b);
-    (void)hipEventRecord(r.a, st);
-    r.cls = cls;
-    r.flops = work;
-    g_recs.push_back(r);
-}
-
-// called by ttsk_gemm around its main kernel launch (not the split-K reduce / zero fill)
-bool prof_on() { return g_prof; }
-void prof_open(hipStream_t st, double flops, int family, int tiles, bool ak, bool bk)
-{
-    // name of the contraction-kernel instantiation as rocprofv3 prints it
-    const int wm = family == 0 ? 2 : (family == 1 ? 1 : 4), wn = family == 0 ? 2 : (family == 1 ? 4 : 1);
-    const int tm = family == 0 ? 2 : (family == 1 ? tiles : 1), tn = family == 0 ? 2 : (family == 1 ? 1 : tiles);
-    if (flops < g_kname_flops[g_cls]) family = -1;
-    else g_kname_flops[g_cls] = flops;
-    if (family < 0) {
-    } else if (family == 3)        // streamed x small: tiles = 10 * column tiles of the small operand + mode, ak = strips > 0
-        snprintf(g_kname[g_cls], sizeof(g_kname[0]), "skinny_s_kernel<%d, %d, %d, %d>",
-                 tiles / 100 % 10, tiles % 10, bk ? 4 : 5, tiles / 1000);
-    else if (family == 5)
-        snprintf(g_kname[g_cls], sizeof(g_kname[0]), "small_gemm_kernel");
-    else if (family == 7)   // streamed x small, contiguous form: tiles = 10 * full tiles + strips
-        snprintf(g_kname[g_cls], sizeof(g_kname[0]), "stream_small_kernel<%d, %d, 5, %d>", tiles / 10, tiles % 10, ak ? 25 : 5);
-    else if (family == 6)   // fused chain step: tiles = 100 * full tiles + 10 * strips + (T written)
-        snprintf(g_kname[g_cls], sizeof(g_kname[0]), "chain_step_kernel<%d, %d, %d, %d, 5, %s, 1, %d, %d>", tiles / 100, tiles / 10 % 10,
-                 tiles / 100, tiles / 10 % 10, tiles % 10 ? "true" : "false", tiles / 100 <= 4 ? 2 : 1, ak ? 25 : 5);
-    else if (family == 4)   // long-K: tiles = 10 * row tiles + column tiles
-        snprintf(g_kname[g_cls], sizeof(g_kname[0]), "skinny_r_kernel<%d, %d, 4>", tiles / 10, tiles % 10);
-    else
-        snprintf(g_kname[g_cls], sizeof(g_kname[0]), "gemm_f64_kernel<%d, %d, %d, %d, %s, %s>", wm, wn, tm, tn,
-                 ak ? "true" : "false", bk ? "true" : "false");
-    prof_record(st, g_cls, flops);
-}
-void prof_close(hipStream_t st) { (void)hipEventRecord(g_recs.back().b, st); }
-
-// brackets for kernels outside ttsk_gemm (samplers, sparse segmented sums, factorisations): class and name given
-// by the caller, `work` in the class's own unit (samples, bytes, flops)
-void prof_open_named(hipStream_t st, int cls, double work, const char *name)
-{
-    if (cls == -2) cls = g_cls;                   // the class the TT driver has set for this product
-    if (cls < 0 || cls >= NCLS) cls = NCLS - 1;
-    if (work >= g_kname_flops[cls]) {
-        g_kname_flops[cls] = work;
-        snprintf(g_kname[cls], sizeof(g_kname[0]), "%s", name);
-    }
-    prof_record(st, cls, work);
-}
-
-static void prof_flush()
-{
-    for (auto &r : g_recs) {
-        float ms = 0;
-        if (hipEventSynchronize(r.b) == hipSuccess && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
-            g_launches[r.cls]++;
-            g_ms[r.cls] += ms;
-            g_flops[r.cls] += r.flops;
-        }
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
-    }
-    g_recs.clear();
-}
-
-// The launches of a scope carry profiling class `cls`; everything outside such a scope is class NCLS - 1.
-struct ProfClass { explicit ProfClass(int cls) { g_cls = cls; } ~ProfClass() { g_cls = NCLS - 1; } };
 
 // C (+)= A * B as described by d, tagged with its profiling class.
 static int gemm(int cls, const ttsk_gemm_desc &d, const double *A, const double *B, double *C, int stream)
@@ -601,35 +521,6 @@ static int tail_sum(const Ctx &c, bool &om_batched, bool &psi_batched)
 using namespace ttsk;
 
 extern "C" {
-
-int ttsk_prof_enable(int on)
-{
-    if (ensure_init() != TTSK_OK) return TTSK_ERR_HIP;
-    if (!on) prof_flush();
-    else {
-        prof_flush();
-        for (int i = 0; i < NCLS; ++i) { g_launches[i] = 0; g_ms[i] = 0; g_flops[i] = 0; g_kname_flops[i] = 0; g_kname[i][0] = 0; }
-    }
-    g_prof = on != 0;
-    return TTSK_OK;
-}
-
-int ttsk_prof_kernel_name(int cls, char *buf, size_t len)
-{
-    TTSK_ARG(cls >= 0 && cls < NCLS && buf && len > 0, "ttsk_prof_kernel_name: bad argument");
-    snprintf(buf, len, "%s", g_kname[cls]);
-    return TTSK_OK;
-}
-
-int ttsk_prof_read(int cls, int64_t *launches, double *total_ms, double *flops)
-{
-    TTSK_ARG(cls >= 0 && cls < NCLS, "ttsk_prof_read: class %d", cls);
-    prof_flush();
-    if (launches) *launches = g_launches[cls];
-    if (total_ms) *total_ms = g_ms[cls];
-    if (flops) *flops = g_flops[cls];
-    return TTSK_OK;
-}
 
 int64_t ttsk_tt_sketch_size(int d, const int64_t *n, const int64_t *l_lo, const int64_t *l_hi,
                             const int64_t *r_lo, const int64_t *r_hi)
