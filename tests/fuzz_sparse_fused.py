@@ -2,7 +2,9 @@
 (sampler.hip + sparse.hip, itself pinned to the oracle) and, for small cases, the oracle -- a tool, not part of the
 collected suite: `python tests/fuzz_sparse_fused.py SEED SECONDS` on a GPU box.  Random orders 2..6, mode sizes 1..400,
 nonzero counts 1..3e5 (duplicates included), ranks 1..32 with rank slices, SparseGaussianDRM / SparseSignDRM in every pairing
-(sign rows with random non-zero counts), table / in-pass factors in every mix."""
+(sign rows with random non-zero counts), table / in-pass factors in every mix.
+The collected counterpart, with chosen slice structures and every kernel instantiation, is tests/test_gpu_sparse_pass.py (the
+stream builders and ttsk_sparse_psi: tests/test_gpu_sparse_stream.py)."""
 import os
 import sys
 import time

@@ -479,3 +479,25 @@ def test_shipped_library_reads_no_ab_switches():
         named += re.findall(r"\bgetenv\s*\(\s*\"(\w+)\"\s*\)", text)
     assert len(named) == len(calls) >= 2          # every read names its variable literally
     assert set(named) == {"TTSK_SINGLE_STREAM", "TTSK_GEMM_TRACE"}, sorted(set(named))
+
+
+def test_sparse_pass_configurations_reach_every_instantiation():
+    """tests/test_gpu_sparse_pass.py runs the configurations of tests/sparse_cases.py; sparse_cases.instantiation restates how
+    sg_gauss_pass (csrc/sparse_fused.hip) chooses among the seven instantiations of sg_pass_kernel.  Every one of them is
+    reached, and the configurations the design document names for each land where it says."""
+    from tests import sparse_cases as sc
+    reached = {}
+    for cfg in sc.CONFIGS:
+        reached.setdefault(sc.instantiation(cfg), []).append(cfg.name)
+    assert set(reached) == set(sc.INSTANTIATIONS), sorted(reached)
+    by_name = {cfg.name: sc.instantiation(cfg) for cfg in sc.CONFIGS}
+    assert len(by_name) == len(sc.CONFIGS)             # the names are the test ids: no two alike
+    assert by_name["t16-16-16-both-left"] == (1, 0, 32)
+    assert by_name["t16-32-16-both-left"] == (2, 0, 32) and by_name["sign32-B-nnz1"] == (2, 0, 32)      # NT = 2 from the sign row alone
+    assert by_name["t20-20-20-both-left"] == (2, 1, 32) and by_name["t17-4-9-both-right"] == (2, 1, 32)
+    assert by_name["t5-21-1-both-left"] == (2, 2, 32) and by_name["t24-24-24-both-noC"] == (2, 2, 32)
+    assert by_name["t32-32-8-both-left"] == (2, 0, 16) and by_name["t32-32-32-both-right"] == (2, 0, 16)
+    assert by_name["normal20"] == (2, 1, 16)
+    assert by_name["t24-24-24-both-left"] == (2, 2, 16)
+    # (32, 32, 8) is just over the threshold of the 16-record tile: one table column pair less keeps 32
+    assert sc.instantiation(sc.table_config((32, 32, 6), "both", "left")) == (2, 0, 32)
