@@ -7,10 +7,10 @@ from collections import namedtuple
 import numpy as np
 
 # ------------------------------------------------------------------ slice structures
-# Streams are ascending in j.  Every structure here has N <= 2^17, fewer than 256 records per resident wave, so
-# sg_gauss_pass gives each wave a stretch (`chunk`) of 256 records: 8 staged tiles of 32 records (16 tiles of 16 in the
-# T = 16 instantiations), a tile being 8 (4) k-blocks of 4 records.  Wave w holds records 256 w .. 256 w + 255; waves up
-# to the next multiple of four are padding.
+# Streams are ascending in j.  Every structure here has N <= 2^17, fewer than 256 records per resident wave, so sg_plan
+# (csrc/sparse_plan.h; held to this by tests/test_sparse_plan.py) gives each wave a stretch (`chunk`) of 256 records:
+# 8 staged tiles of 32 records (16 tiles of 16 in the T = 16 instantiations), a tile being 8 (4) k-blocks of 4 records.
+# Wave w holds records 256 w .. 256 w + 255; waves up to the next multiple of four are padding.
 Structure = namedtuple("Structure", "name j n null_j")
 
 
@@ -86,12 +86,13 @@ INSTANTIATIONS = ((1, 0, 32), (2, 0, 32), (2, 1, 32), (2, 2, 32), (2, 0, 16), (2
 
 
 def _per_wave(tcols, tab, qcols, T):
-    """sg_per_wave of csrc/sparse_fused.hip: doubles of LDS per wave"""
+    """sg_lds_layout(...).total of csrc/sparse_plan.h: doubles of LDS per wave"""
     return T * tcols + tab + 4 * T + T // 2 + (T * qcols + 3) // 4
 
 
 def instantiation(cfg):
-    """(NT, NS, T) of sg_pass_kernel as sg_gauss_pass chooses it for the factors of ``cfg``"""
+    """(NT, NS, T) of sg_pass_kernel as sg_plan (csrc/sparse_plan.h) chooses it for the factors of ``cfg``; restated here on
+    purpose: tests/test_sparse_plan.py holds it against the plan itself"""
     cols = tab = qcols = 0
     widest = wmax = 1
     for F in (cfg.A, cfg.B, cfg.C):

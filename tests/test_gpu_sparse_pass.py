@@ -1,7 +1,8 @@
-"""The one-pass sparse kernel (csrc/sparse_fused.hip) at the C ABI, ttsk_sparse_gauss_pass and ttsk_sparse_gauss_pass_u32
-called directly with hand-made streams, so that the slice structure, the factor widths and therefore the kernel
+"""The one-pass sparse kernel (csrc/sparse_pass.h, launched by csrc/sparse_fused.hip) at the C ABI, ttsk_sparse_gauss_pass and
+ttsk_sparse_gauss_pass_u32 called directly with hand-made streams, so that the slice structure, the factor widths and therefore the kernel
 instantiation of every case are chosen and not what a random tensor happens to give (tests/sparse_cases.py holds the
-catalogues; test_host_logic.test_sparse_pass_configurations_reach_every_instantiation holds the list against the launcher).
+catalogues; test_host_logic.test_sparse_pass_configurations_reach_every_instantiation and tests/test_sparse_plan.py hold the
+list against the launcher's plan, csrc/sparse_plan.h).
 
 Reference: explicit row matrices A[e, :], B[e, :], C[e, :] (a table gathered at the factor's flat index, ones, or the host
 sampler on that flat index) and

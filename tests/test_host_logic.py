@@ -483,7 +483,8 @@ def test_shipped_library_reads_no_ab_switches():
 
 def test_sparse_pass_configurations_reach_every_instantiation():
     """tests/test_gpu_sparse_pass.py runs the configurations of tests/sparse_cases.py; sparse_cases.instantiation restates how
-    sg_gauss_pass (csrc/sparse_fused.hip) chooses among the seven instantiations of sg_pass_kernel.  Every one of them is
+    sg_plan (csrc/sparse_plan.h) chooses among the seven instantiations of sg_pass_kernel (csrc/sparse_pass.h;
+    tests/test_sparse_plan.py holds the restatement against the plan).  Every one of them is
     reached, and the configurations the design document names for each land where it says."""
     from tests import sparse_cases as sc
     reached = {}

@@ -23,10 +23,9 @@ __device__ __forceinline__ void ndtri_block(bool live, double u, size_t g, doubl
     __shared__ double q_u[256];
     __shared__ size_t q_g[256];
     __shared__ int q_n;
-    const double expm2 = 0.13533528323661269189;
     if (threadIdx.x == 0) q_n = 0;
     __syncthreads();
-    const bool central = live && u > expm2 && u <= 1.0 - expm2;
+    const bool central = live && nd_central(u);
     if (central) {
         out[g] = scale * ndtri_dev(u);
     } else if (live) {
@@ -46,8 +45,7 @@ __device__ __forceinline__ void ndtri_block(bool live, double u, size_t g, doubl
 // 256 samples, i.e. per column of a row tile.)
 __device__ __forceinline__ void tile_sample(double u, int slot, double scale, double *tile, unsigned short *q, int *qn)
 {
-    const double expm2 = 0.13533528323661269189;
-    if (u > expm2 && u <= 1.0 - expm2) {
+    if (nd_central(u)) {
         tile[slot] = scale * ndtri_dev(u);
     } else {
         tile[slot] = u;
@@ -120,8 +118,7 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const int64_t *__restr
         if (tid == 0) tq_n = 0;
         __syncthreads();
         for (int j = 0; j < rank; ++j) {
-            const uint64_t h = mix64(flat + salt[j]);
-            const uint64_t bits = (h | 0x2000000000000000ULL) & 0x3FFFFFFFFFFFFFFFULL;
+            const uint64_t bits = force_exponent(mix64(flat + salt[j]));
             if (MODE == 0) tile[tid * rank + j] = __longlong_as_double(bits);
             else if (live) tile_sample(mant_unit(bits), tid * rank + j, 1.0, tile, tq, &tq_n);
         }
@@ -146,13 +143,11 @@ __global__ void sign_kernel(const int64_t *__restrict__ idx, IndexMap im, size_t
     for (int j = 0; j < rank; ++j) ws[(size_t)j * N + e] = 0;
     for (int j = 0; j < nnz; ++j) {
         uint64_t bits = rand_bits(flat, j, seed);
-        int ex = (int)((bits >> 52) & 0x7FF) - 1022;  // frexp exponent
-        int par = ((ex % 2) + 2) % 2;                 // Python-style modulo (pyx:145)
-        ws[(size_t)j * N + e] = (int8_t)(par * 2 - 1);
+        ws[(size_t)j * N + e] = (int8_t)sign_entry(bits);
     }
     for (int j = 0; j < nnz; ++j) {
         double u = mant_unit(rand_bits(flat, j, seed));
-        int pick = (int)(u * (double)(rank - j) + (double)j);
+        int pick = swap_pick(u, j, rank);
         int8_t a = ws[(size_t)j * N + e], b = ws[(size_t)pick * N + e];
         ws[(size_t)j * N + e] = b;
         ws[(size_t)pick * N + e] = a;
@@ -176,9 +171,7 @@ __device__ __forceinline__ void fill_normal_body(double *out, size_t n, uint64_t
             const int slot = threadIdx.x + 256 * k;
             const size_t i = i0 + slot;
             if (i < n) {
-                uint64_t h = mix64((uint64_t)i + key);
-                h = (h | 0x2000000000000000ULL) & 0x3FFFFFFFFFFFFFFFULL;
-                double u = mant_unit(h);
+                double u = mant_unit(force_exponent(mix64((uint64_t)i + key)));
                 if (u == 0.0) u = 0x1p-53;
                 tile_sample(u, slot, scale, tile, tq, &tq_n);
             }
@@ -230,20 +223,18 @@ __global__ __launch_bounds__(256) void ndtri_probe_kernel(double *sink, int reps
     double *T = tile[wv];
     unsigned short *q = tq[wv];
     const uint64_t row0 = ((uint64_t)blockIdx.x * 256 + tid) * (uint64_t)reps;
-    const double expm2 = 0.13533528323661269189;
     double acc = 0.0;
     for (int r = 0; r < reps; ++r) {
         const uint64_t flat = row0 + r;
         int qn = 0;
 #pragma unroll 4
         for (int c = 0; c < PROBE_COLS; ++c) {
-            const uint64_t h = mix64(flat + salt[c]);
-            const double u = mant_unit((h | 0x2000000000000000ULL) & 0x3FFFFFFFFFFFFFFFULL);
+            const double u = mant_unit(force_exponent(mix64(flat + salt[c])));
             if (MODE == 1) {
                 acc += ndtri_dev(u);
             } else {
                 const int slot = lane * PROBE_COLS + c;
-                const bool central = u > expm2 && u <= 1.0 - expm2;
+                const bool central = nd_central(u);
                 if (central) T[slot] = ndtri_dev(u);
                 const unsigned long long m = __ballot(!central);
                 if (!central) {

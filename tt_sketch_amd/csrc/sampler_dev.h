@@ -50,11 +50,13 @@ __device__ __forceinline__ uint64_t flat_index(const int64_t *idx, const IndexMa
     return f;
 }
 
+// a hash with its exponent field forced to 001x...: a normal positive double (pyx:91-101)
+__device__ __forceinline__ uint64_t force_exponent(uint64_t h) { return (h | 0x2000000000000000ULL) & 0x3FFFFFFFFFFFFFFFULL; }
+
 __device__ __forceinline__ uint64_t rand_bits(uint64_t flat, int col, uint64_t seed)
 {
     uint64_t salt = mix64((uint64_t)col) + seed;
-    uint64_t h = mix64(flat + salt);
-    return (h | 0x2000000000000000ULL) & 0x3FFFFFFFFFFFFFFFULL;  // exponent field 001x..., pyx:91-101
+    return force_exponent(mix64(flat + salt));
 }
 
 // frexp(x)*2-1 for a normal positive double: the 52 mantissa bits as a fraction in [0,1)
@@ -62,6 +64,16 @@ __device__ __forceinline__ double mant_unit(uint64_t bits)
 {
     return __longlong_as_double((bits & 0x000FFFFFFFFFFFFFULL) | 0x3FF0000000000000ULL) - 1.0;
 }
+
+// sparse-sign rows (pyx:121-180): entry c of the first nnz is +-1 by the parity of its sample's frexp exponent (Python-style
+// modulo, pyx:145); swap c then exchanges entries c and c + floor(u (full - c)) of the row
+__device__ __forceinline__ int sign_entry(uint64_t bits)
+{
+    const int ex = (int)((bits >> 52) & 0x7FF) - 1022;
+    return ((ex % 2) + 2) % 2 * 2 - 1;
+}
+
+__device__ __forceinline__ int swap_pick(double u, int c, int full) { return (int)(u * (double)(full - c) + (double)c); }
 
 // ---- Cephes ndtri (fast_lazy_gaussian.pyx:183-202 -> scipy.special.cython_special.ndtri), restated for the vector ALU.
 // The operations and their order are those of the C source, so the results are its bits wherever the host libm's log agrees with
@@ -73,6 +85,9 @@ __device__ __forceinline__ double mant_unit(uint64_t bits)
 //     rescale operands near the ends of the exponent range and patch infinities, zeros and NaNs, none of which occur for the
 //     polynomial values and x in [2, 38.6] divided here (same bits otherwise: the frame multiplies by 1);
 //   * the far tail (x >= 8: y < exp(-32), one sample in 10^14) is a real branch, not both rational functions and a select.
+constexpr double ND_EXPM2 = 0.13533528323661269189;                              // exp(-2): the central branch is (exp(-2), 1 - exp(-2)]
+__device__ __forceinline__ bool nd_central(double u) { return u > ND_EXPM2 && u <= 1.0 - ND_EXPM2; }
+
 __device__ __forceinline__ double nd_fma_c(double a, double b, double c)          // a * b + c, c a constant in scalar registers
 {
     double r;
@@ -174,10 +189,9 @@ __device__ __attribute__((noinline)) double ndtri_far_tail_dev(double z)
 // the tails alone: 0 < y0 <= exp(-2) or y0 > 1 - exp(-2)
 __device__ __forceinline__ double ndtri_tail_dev(double y0)
 {
-    const double expm2 = 0.13533528323661269189;
     int code = 1;
     double y = y0;
-    if (y > 1.0 - expm2) { y = 1.0 - y; code = 0; }
+    if (y > 1.0 - ND_EXPM2) { y = 1.0 - y; code = 0; }
     double x = sqrt(-2.0 * nd_log(y));
     const double x0 = x - nd_div(nd_log(x), x);
     const double z = nd_div(1.0, x);
@@ -210,10 +224,9 @@ __device__ __forceinline__ double ndtri_tail_dev(double y0)
 
 __device__ inline double ndtri_dev(double y0)
 {
-    const double expm2 = 0.13533528323661269189;
     if (y0 == 0.0) return -INFINITY;
     if (y0 == 1.0) return INFINITY;
-    if (y0 > expm2 && y0 <= 1.0 - expm2) return ndtri_central_dev(y0);
+    if (nd_central(y0)) return ndtri_central_dev(y0);
     return ndtri_tail_dev(y0);
 }
 
