@@ -281,6 +281,21 @@ int ttsk_cp_gather(const double *const *dev_factors, int64_t rank, const int64_t
                    const int64_t *dev_idx, int64_t row_stride, const int *row_order, size_t N,
                    const double *dev_val, double *dev_out, double *dev_stats, int stream);
 
+/* ---- Gram matrix of tensor trains (csrc/tt_gram.hip, plan in csrc/tt_gram_plan.h) ----
+ * TensorTrain.dot (tensor.py:542-557) for every pair of two lists of trains at once: dev_out[p * M + q] = <A_p, B_q>.  With
+ * it Tensor.error(fast=True) (tensor.py:68-72) of two trains is one 2 x 2 call, a Hessenberg column of tt_gmres.py:385-386
+ * one 1 x (j + 1) call.  One launch per mode over all pairs (the chunk partials of the mode before are summed, in order, as
+ * they are loaded) and one closing launch: at most d + 1 launches whatever K M is.
+ *   dev_cores_a[p * d + k]  core k of A_p, (ranks_a[p * (d + 1) + k], shape[k], ranks_a[p * (d + 1) + k + 1]) contiguous;
+ *   dev_cores_b, ranks_b    the same for the M trains B_q; all trains of the one shape, each with its own ranks
+ *   dev_out                 (K, M) row-major
+ * No atomics; the split of a mode depends on the shapes, K M and the CU count alone: the same bits on every call.
+ * TTSK_ERR_ARG: a NULL pointer, d < 1, K or M < 1, a boundary rank != 1, a rank or a mode size < 1.  TTSK_ERR_UNSUPPORTED
+ * before anything is launched: d > 32, a rank beyond 128, a mode of 2^31 or more, K + M > 128 (the caller then composes
+ * the products from ttsk_gemm, or cuts the lists). */
+int ttsk_tt_gram(const double *const *dev_cores_a, const int64_t *ranks_a, int K, const double *const *dev_cores_b,
+                 const int64_t *ranks_b, int M, const int64_t *shape, int d, double *dev_out, int stream);
+
 /* ---- a tensor train against a dense tensor (csrc/tt_dense_stats.hip) ----------
  * Tensor.error / dot / norm for a DenseTensor argument (tensor.py:53-88) and TensorTrain.dense in one pass over the
  * tensor.  The train is cut at a bond: T^{<k>} = L R, dev_L (M x rho) and dev_R (rho x N) row-major and contiguous.

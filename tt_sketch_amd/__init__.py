@@ -12,7 +12,7 @@ from .sketch import (SketchedTensorTrain, assemble_sketched_tt, blocked_stream_s
 from .sketch_container import SketchContainer
 from .sketch_dispatch import SketchMethod, general_sketch
 from .tensor import (CPTensor, DenseTensor, SparseTensor, Tensor, TensorSum, TensorTrain,
-                     TuckerTensor)
+                     TuckerTensor, tt_gram)
 from .tt_svd import tt_svd
 
 __all__ = [
@@ -20,5 +20,5 @@ __all__ = [
     "SketchedTensorTrain", "assemble_sketched_tt", "blocked_stream_sketch", "hmt_sketch",
     "orthogonal_sketch", "orthogonal_sketch_batch", "hmt_sketch_batch", "stream_sketch", "stream_sketch_batch", "to_tt_batch", "SketchContainer", "SketchMethod", "general_sketch",
     "CPTensor", "DenseTensor", "SparseTensor", "Tensor", "TensorSum", "TensorTrain", "TuckerTensor",
-    "tt_svd",
+    "tt_svd", "tt_gram",
 ]

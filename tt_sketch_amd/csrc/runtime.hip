@@ -65,6 +65,7 @@ static bool g_pa_host[PA_SLOTS];
 enum { LDS_SLOTS = 4096 };
 static std::atomic<const void *> g_lds_raised[LDS_SLOTS];
 static int g_lds_per_wg = 0;   // the device's LDS per workgroup, read at init
+static int g_num_cu = 0;       // its compute units, read at init
 
 static unsigned lds_home(const void *k) { return (unsigned)(((uintptr_t)k >> 4) * 0x9E3779B97F4A7C15ull >> 52); }   // 12 bits
 
@@ -115,6 +116,13 @@ void *persistent_alloc(int key, size_t bytes, bool host, bool zero)
     return q;
 }
 
+int device_num_cu()
+{
+    if (ensure_init() != TTSK_OK) return 0;
+    if (g_num_cu < 1) set_error("the device reports %d compute units", g_num_cu);
+    return g_num_cu < 1 ? 0 : g_num_cu;
+}
+
 hipStream_t stream_of(int s)
 {
     if (ensure_init() != TTSK_OK) return nullptr;
@@ -149,6 +157,7 @@ int ttsk_init(int device)
     TTSK_ARG(device >= 0 && device < n, "device %d out of range (%d devices)", device, n);
     TTSK_HIP(hipSetDevice(device));
     TTSK_HIP(hipDeviceGetAttribute(&g_lds_per_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+    TTSK_HIP(hipDeviceGetAttribute(&g_num_cu, hipDeviceAttributeMultiprocessorCount, device));
     for (int i = 0; i < TTSK_NUM_STREAMS; ++i) {
         TTSK_HIP(hipStreamCreateWithFlags(&g_streams[i], hipStreamNonBlocking));
         TTSK_HIP(hipEventCreate(&g_ev_start[i]));

@@ -658,10 +658,11 @@ class TensorTrain(_GatherOnDevice, Tensor):
         return float(np.linalg.norm(self.orthogonalize().cores[-1]))
 
     def gram_norm(self) -> float:
-        """sqrt(<x, x>) by the Gram chain (2 d small device products, no QR sweep).  Accurate to a few ulp
+        """sqrt(<x, x>) by the Gram chain (``tt_gram``: one device pass, no QR sweep).  Accurate to a few ulp
         for a train that is not itself a difference of nearly equal terms -- a direct sum ``a + (-b)`` with
         a ~ b cancels inside the chain and is only good to sqrt(eps) ||a||; ``norm`` (QR sweep, reference
-        tensor.py:442-444) has no such limit and is what ``error`` uses."""
+        tensor.py:442-444) has no such limit.  That is why ``error(fast=False)`` keeps the QR sweep of the direct
+        sum, and only ``fast=True`` -- whose formula has that floor by definition -- takes the Gram pass."""
         return float(np.sqrt(max(self.dot(self), 0.0)))
 
     def resident(self) -> bool:
@@ -829,12 +830,7 @@ class TensorTrain(_GatherOnDevice, Tensor):
 
     def dot(self, other, reverse=False) -> float:
         if isinstance(other, TensorTrain) and self.resident() and other.resident():
-            acc = None
-            for a, b in zip(self.cores, other.cores):
-                t = a.reshape(a.shape[1], a.shape[2]) if acc is None else contract("ij,ika->jka", acc, a)
-                b = b.reshape(b.shape[1], b.shape[2]) if acc is None else b
-                acc = contract("ka,kb->ab", t, b) if acc is None else contract("jka,jkb->ab", t, b)
-            return float(acc.get().sum())
+            return float(tt_gram([self], [other])[0, 0])        # one device call, or the chain where tt_gram routes it
         if isinstance(other, TensorTrain):
             acc = np.ones((1, 1))
             for a, b in zip(self.cores, other.cores):
@@ -867,6 +863,20 @@ class TensorTrain(_GatherOnDevice, Tensor):
             if rmse:
                 err /= np.sqrt(np.prod(self.shape))
             return float(err)
+        if isinstance(other, TensorTrain) and fast and self.resident() and other.resident():
+            # <a, a>, <a, b>, <b, b> from one 2 x 2 Gram in the reference's formula (tensor.py:68-72; its floor is a
+            # relative error of about 1e-8)
+            G = tt_gram([self, other])
+            tot = G[0, 0] + G[1, 1]
+            err = float(np.sqrt(tot) * np.sqrt(abs(1 - 2 * G[0, 1] / tot))) if tot > 0 else 0.0
+            if relative:
+                ref_norm = float(np.sqrt(abs(G[1, 1])))
+                if ref_norm == 0:
+                    return np.inf
+                err /= ref_norm
+            if rmse:
+                err /= np.sqrt(np.prod(self.shape))
+            return float(err)
         if isinstance(other, TensorTrain):
             err = self.add(-other).norm()
             if relative:
@@ -881,6 +891,106 @@ class TensorTrain(_GatherOnDevice, Tensor):
 
     def __repr__(self) -> str:
         return f"<Tensor train of shape {self.shape} with rank {self.rank} at {hex(id(self))}>"
+
+
+# ------------------------------------------------------------------ Gram matrix of trains (csrc/tt_gram.hip)
+_GRAM_MAX_TRAINS = 128       # K + M of one ttsk_tt_gram call
+# The routing rule of DESIGN section 12, its constants measured on one MI355X (profiles/tt_gram_bench.json): the work
+# of the pass beyond its launches against the time of the composed chain.
+_GRAM_ROUTE = True           # False: the pass wherever the entry covers the call (profiles/scripts/tt_gram_bench.py)
+_GRAM_CUS = 256              # the chip the constants were measured on; the plan's chunks per pair follow the CU count
+_GRAM_MAX_CHUNKS = 64        # GRAM_MAX_CHUNKS of tt_gram_plan.h
+_GRAM_REDUCE_MS = 0.9e-6     # per partial a workgroup adds while it forms acc (chunks x ra x rb of them per mode)
+_GRAM_WG_FLOPS_MS = 3e7      # flops per ms of one workgroup on its run of slices
+_GRAM_CHAIN_MODE_MS = 0.045  # the chain per pair and mode: two launch-bound ``contract`` calls
+
+
+def _gram_route_ms(ra: np.ndarray, rb: np.ndarray, shape) -> Tuple[float, float]:
+    """(work of the Gram pass, time of the composed chain) in ms for the rank tables ``(K, d + 1)`` and ``(M, d + 1)``.
+    The d + 1 launches and the one read-back of the pass never cost more than the 2 d launches and the read-back of
+    one pair's chain, so only what a workgroup does in a launch can make the pass the slower path: the fused reduce
+    of the previous mode's chunk partials and the two products over its run of slices, as many rounds of either as
+    the grid (pairs x chunks) has workgroups per CU."""
+    pairs = ra.shape[0] * rb.shape[0]
+    a, b = ra.max(0).astype(np.float64), rb.max(0).astype(np.float64)
+    work, prev = 0.0, 1
+    for k, n in enumerate(shape):
+        chunks = max(1, min(-(-_GRAM_CUS // pairs), _GRAM_MAX_CHUNKS, int(n)))
+        slices = -(-int(n) // chunks)
+        flops = slices * 2.0 * (a[k] * b[k] * a[k + 1] + a[k + 1] * b[k] * b[k + 1])
+        rounds = -(-pairs * chunks // _GRAM_CUS)
+        work += rounds * (_GRAM_REDUCE_MS * prev * a[k] * b[k] + flops / _GRAM_WG_FLOPS_MS)
+        prev = chunks
+    return work, pairs * len(shape) * _GRAM_CHAIN_MODE_MS
+
+
+def _tt_dot_composed(x: TensorTrain, y: TensorTrain) -> float:
+    """<x, y> of two resident trains as a chain of 2 d ``contract`` launches: what ``tt_gram`` falls back to beyond the
+    cover of ``ttsk_tt_gram`` (a rank above 128) and where its routing rule expects the chain to be faster."""
+    acc = None
+    for a, b in zip(x.dev_cores(), y.dev_cores()):
+        t = a.reshape(a.shape[1], a.shape[2]) if acc is None else contract("ij,ika->jka", acc, a)
+        b = b.reshape(b.shape[1], b.shape[2]) if acc is None else b
+        acc = contract("ka,kb->ab", t, b) if acc is None else contract("jka,jkb->ab", t, b)
+    return float(acc.get().sum())
+
+
+def _gram_composed(As, Bs, sym: bool) -> np.ndarray:
+    G = np.empty((len(As), len(Bs)))
+    for p, a in enumerate(As):
+        for q, b in enumerate(Bs):
+            G[p, q] = G[q, p] if sym and q < p else _tt_dot_composed(a, b)
+    return G
+
+
+def _gram_block(As: Sequence[TensorTrain], Bs: Sequence[TensorTrain], sym: bool = False) -> np.ndarray:
+    from . import _native as nat
+    d = As[0].ndim
+    cores = [[c.contiguous() for c in t.dev_cores()] for t in list(As) + list(Bs)]
+    ranks = [[c.shape[0] for c in cs] + [cs[-1].shape[2]] for cs in cores]
+    K, M = len(As), len(Bs)
+    if _GRAM_ROUTE:
+        work, chain = _gram_route_ms(np.array(ranks[:K]), np.array(ranks[K:]), As[0].shape)
+        if work > (chain * (K + 1) / (2 * M) if sym else chain):   # of a symmetric block the chain forms the upper triangle
+            return _gram_composed(As, Bs, sym)
+    out = DevArray.empty((K, M))
+    try:
+        nat.call("ttsk_tt_gram", nat.ptr_array([c for cs in cores[:K] for c in cs]), nat.i64_array([r for rk in ranks[:K] for r in rk]), K,
+                 nat.ptr_array([c for cs in cores[K:] for c in cs]), nat.i64_array([r for rk in ranks[K:] for r in rk]), M,
+                 nat.i64_array(As[0].shape), d, out, 0)
+    except nat.TtskUnsupported:
+        return _gram_composed(As, Bs, sym)
+    return out.get()
+
+
+def tt_gram(As: Sequence[TensorTrain], Bs: Optional[Sequence[TensorTrain]] = None) -> np.ndarray:
+    """``G[p, q] = <As[p], Bs[q]>`` as a ``(K, M)`` array (``Bs=None``: ``As``).  The trains share one shape and have each
+    their own ranks; a host train is uploaded once (``dev_cores``).
+
+    On the device pass, ``ttsk_tt_gram``, that is one call (one launch per mode over all pairs) per block of at most
+    ``_GRAM_MAX_TRAINS`` trains, and the same bits on every call.  Both hold on that pass only: beyond the cover of the
+    entry (a rank above 128), and where the routing rule of DESIGN section 12 (``_gram_route_ms``: few pairs of large
+    ranks) expects the chain to be faster, a block is composed pair by pair from ``contract``, 2 d launches and a
+    read-back each.  With ``Bs=None`` a single block computes only its upper triangle on the composed path; lists cut
+    into several blocks (``K + M > _GRAM_MAX_TRAINS``) compute every block in full, the lower ones too."""
+    As = list(As)
+    sym = Bs is None
+    Bs = As if sym else list(Bs)
+    if not As or not Bs:
+        raise ValueError("tt_gram: an empty list of trains")
+    for t in As + Bs:
+        if not isinstance(t, TensorTrain):
+            raise TypeError(f"tt_gram: {type(t).__name__} is not a TensorTrain")
+        if t.shape != As[0].shape:
+            raise ValueError(f"tt_gram: trains of shapes {As[0].shape} and {t.shape}")
+    K, M, half = len(As), len(Bs), _GRAM_MAX_TRAINS // 2
+    if K + M <= _GRAM_MAX_TRAINS:
+        return _gram_block(As, Bs, sym)
+    out = np.empty((K, M))
+    for p in range(0, K, half):
+        for q in range(0, M, half):
+            out[p:p + half, q:q + half] = _gram_block(As[p:p + half], Bs[q:q + half])
+    return out
 
 
 # --------------------------------------------------------------------------- sums

@@ -23,7 +23,7 @@ import scipy.linalg
 
 from .device import DevArray, as_dev, axpby, contract
 from .sketch import orthogonal_sketch, stream_sketch
-from .tensor import Tensor, TensorSum, TensorTrain, _host
+from .tensor import Tensor, TensorSum, TensorTrain, _host, tt_gram
 from .utils import ArrayList, TTRank, process_tt_rank
 
 
@@ -272,8 +272,11 @@ def tt_sum_gmres(A: TTLinearMapSum, b: TensorTrain, max_rank: TTRank,
         w = round_tt_sum(operator(basis[-1]), eps=delta, max_rank=max_rank, method=rounding_method)
 
         lo = max(0, j - 2) if symmetric else 0
-        for i in range(lo, j + 1):
-            H[i, j] = w.dot(basis[i])
+        if w.resident() and all(v.resident() for v in basis[lo:j + 1]):
+            H[lo:j + 1, j] = tt_gram([w], basis[lo:j + 1])[0]          # the whole column from one device call
+        else:
+            for i in range(lo, j + 1):
+                H[i, j] = w.dot(basis[i])
         # Gram-Schmidt against the (recent) basis, rounded again
         w = round_tt_sum(w - TensorSum(basis[lo:j + 1]) * H[lo:j + 1, j], eps=delta,
                          max_rank=max_rank, method=rounding_method)
