@@ -296,6 +296,27 @@ int ttsk_cp_gather(const double *const *dev_factors, int64_t rank, const int64_t
 int ttsk_tt_gram(const double *const *dev_cores_a, const int64_t *ranks_a, int K, const double *const *dev_cores_b,
                  const int64_t *ranks_b, int M, const int64_t *shape, int d, double *dev_out, int stream);
 
+/* ---- operator-times-train products, never formed (csrc/op_apply.hip, plan in csrc/op_apply_plan.h) ----
+ * One step of sketching the product of a matrix product operator and a tensor train (tt_gmres.py:91-101) without its
+ * cores: for every term p of a sum, with operator core M (R, n_in, n_out, R'), train core C (r, n_in, r') and the chain
+ * so far L (R, r, l),
+ *   W[l, i, w_off + beta' r' + a'] = sum_{beta, j} M[beta, j, i, beta'] sum_a L[beta, a, l] C[a, j, a'];
+ * the inner sum stays on the chip.  The chain step, Psi and Omega of the sum are one ttsk_gemm each on W.
+ *   L[p]      contiguous (R, r, l)
+ *   M[p]      strided, or NULL: a plain train in the sum, W[l, i, w_off + a'] = sum_a L[a, l] C[a, i, a'] (R = R' = 1,
+ *             n_in = n_out)
+ *   C[p]      strided
+ *   dims      K rows of 7: R, R', r, r', n_in, n_out, w_off
+ *   strides   K rows of 7, in elements: M over (beta, j, i, beta'), then C over (a, j, a')
+ *   W         contiguous (l, n_out, w_cols); term p writes the columns w_off .. w_off + R' r' and nothing else
+ * n_out and l are those of every term.  One workgroup forms each element in a fixed order, no atomics: the same bits on
+ * every call.  TTSK_ERR_ARG: a NULL pointer, K < 1, an extent below 1, a term without operator that has R or R' != 1 or
+ * n_in != n_out, w_off + R' r' > w_cols, differing n_out.  TTSK_ERR_UNSUPPORTED before anything is launched: an extent,
+ * R n_in or n_out R' of 2^31 or more, K > 24 (the terms travel as the kernel's argument; the caller cuts longer lists into
+ * several calls, which the column offsets allow).  Inside those bounds every shape runs. */
+int ttsk_op_apply(int K, const double *const *L, const double *const *M, const double *const *C, const int64_t *dims,
+                  const int64_t *strides, int64_t l, double *W, int64_t w_cols, int stream);
+
 /* ---- a tensor train against a dense tensor (csrc/tt_dense_stats.hip) ----------
  * Tensor.error / dot / norm for a DenseTensor argument (tensor.py:53-88) and TensorTrain.dense in one pass over the
  * tensor.  The train is cut at a bond: T^{<k>} = L R, dev_L (M x rho) and dev_R (rho x N) row-major and contiguous.

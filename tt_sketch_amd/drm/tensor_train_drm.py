@@ -15,13 +15,13 @@ import numpy as np
 from .. import _native as nat
 from ..device import DevArray, as_dev, contract
 from ..drm_base import CanSlice, handle_transpose
-from ..sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchSparse,
-                                                  CansketchTT, CanSketchTucker)
+from ..sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchOperatorProduct,
+                                                  CansketchSparse, CansketchTT, CanSketchTucker)
 from ..utils import random_normal_dev_many
 
 
 class TensorTrainDRM(CansketchSparse, CansketchTT, CansketchCP, CanSlice, CansketchDense,
-                     CanSketchTucker):
+                     CanSketchTucker, CansketchOperatorProduct):
     cores: list
 
     def __init__(self, rank: Union[Tuple[int, ...], int], shape: Tuple[int, ...], transpose: bool,
@@ -75,6 +75,23 @@ class TensorTrainDRM(CansketchSparse, CansketchTT, CansketchCP, CanSlice, Canske
                 T = contract("ij,ikl->jkl", L, X)
                 L = contract("jkl,jkm->lm", T, D)
             yield self._cut(mu, L)
+
+    # ------------------------------------------------------------------ operator-times-train input
+    @handle_transpose
+    def sketch_operator_product(self, tensor):
+        """L_mu[(b' a'), m] = sum_{l,i} W_mu[l, i, (b' a')] D_mu[l, i, m] with W_mu = L_{mu-1} o (M_mu, C_mu) from
+        ``op_apply`` -- one ``ttsk_op_apply`` call, or W composed from two ``contract`` calls where its routing rule has it,
+        which for one term it does at every measured shape: the product core of ``MPO.__call__`` (reference
+        tt_gmres.py:90-101) is never formed either way."""
+        from ..operator_product import chain_start, op_apply
+        Ms, Cs = tensor.dev_parts()
+        L = chain_start()
+        for mu in range(len(self.shape) - 1):
+            M, C = Ms[mu], Cs[mu]
+            W, _ = op_apply([L], [M], [C])
+            Lm = contract("lic,lim->cm", W, self._core(mu))
+            yield self._cut(mu, Lm)
+            L = Lm.reshape(M.shape[3], C.shape[2], Lm.shape[1])
 
     # ------------------------------------------------------------------ CP input
     @handle_transpose

@@ -22,10 +22,12 @@ from .device import DevArray, as_dev, axpby, contract
 from .drm import TensorTrainDRM
 from .drm_base import DRM
 from .sketch_container import SketchContainer
-from .sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchSparse,
+from .operator_product import OperatorProduct
+from .sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchOperatorProduct, CansketchSparse,
                                                  CansketchTT, CanSketchTucker)
 from .sketching_methods.cp_sketch import sketch_omega_cp, sketch_psi_cp
 from .sketching_methods.dense_sketch import sketch_omega_dense, sketch_psi_dense
+from .sketching_methods.operator_product_sketch import sketch_omega_operator_product, sketch_psi_operator_product
 from .sketching_methods.sparse_sketch import sketch_omega_sparse, sketch_psi_sparse
 from .sketching_methods.tensor_train_sketch import sketch_omega_tt, sketch_psi_tt
 from .sketching_methods.tucker_sketch import sketch_omega_tucker, sketch_psi_tucker
@@ -35,19 +37,19 @@ from .utils import pinv_dev
 
 ABSTRACT_TENSOR_SKETCH_DISPATCH = {
     SparseTensor: CansketchSparse, TensorTrain: CansketchTT, DenseTensor: CansketchDense,
-    CPTensor: CansketchCP, TuckerTensor: CanSketchTucker,
+    CPTensor: CansketchCP, TuckerTensor: CanSketchTucker, OperatorProduct: CansketchOperatorProduct,
 }
 DRM_SKETCH_METHOD_DISPATCH = {
     SparseTensor: "sketch_sparse", TensorTrain: "sketch_tt", DenseTensor: "sketch_dense",
-    CPTensor: "sketch_cp", TuckerTensor: "sketch_tucker",
+    CPTensor: "sketch_cp", TuckerTensor: "sketch_tucker", OperatorProduct: "sketch_operator_product",
 }
 OMEGA_METHODS = {
     SparseTensor: sketch_omega_sparse, TensorTrain: sketch_omega_tt, DenseTensor: sketch_omega_dense,
-    CPTensor: sketch_omega_cp, TuckerTensor: sketch_omega_tucker,
+    CPTensor: sketch_omega_cp, TuckerTensor: sketch_omega_tucker, OperatorProduct: sketch_omega_operator_product,
 }
 PSI_METHODS = {
     SparseTensor: sketch_psi_sparse, TensorTrain: sketch_psi_tt, DenseTensor: sketch_psi_dense,
-    CPTensor: sketch_psi_cp, TuckerTensor: sketch_psi_tucker,
+    CPTensor: sketch_psi_cp, TuckerTensor: sketch_psi_tucker, OperatorProduct: sketch_psi_operator_product,
 }
 
 
@@ -289,9 +291,11 @@ def _sketch_pass(tensor: Tensor, left_drm: Optional[DRM], right_drm: DRM, method
 def general_sketch(tensor: Tensor, left_drm: Optional[DRM], right_drm: DRM,
                    method: SketchMethod) -> SketchContainer:
     """Sketch on the device, result copied to a host ``SketchContainer``."""
-    from . import sparse_fused, tt_fused
+    from . import operator_fused, sparse_fused, tt_fused
     fused = tt_fused.try_stream_sketch(tensor, left_drm, right_drm, method)
     if fused is None:
         fused = sparse_fused.try_sparse_gauss_sketch(tensor, left_drm, right_drm, method)
+    if fused is None:
+        fused = operator_fused.try_operator_sketch(tensor, left_drm, right_drm, method)
     Psi, Omega = fused if fused is not None else general_sketch_device(tensor, left_drm, right_drm, method)
     return SketchContainer(Psi, Omega)

@@ -13,6 +13,13 @@ class CansketchTT(DRM, ABC):
         """yields (tensor.rank[mu], drm.rank[mu]): DRM_mu^T contracted with cores 0..mu."""
 
 
+class CansketchOperatorProduct(DRM, ABC):
+    @abstractmethod
+    def sketch_operator_product(self, tensor):
+        """yields (mpo.rank[mu] * tt.rank[mu], drm.rank[mu]): DRM_mu^T contracted with the product cores 0..mu, which
+        are never formed; rows in (operator rank, train rank) order."""
+
+
 class CansketchSparse(DRM, ABC):
     @abstractmethod
     def sketch_sparse(self, tensor):

@@ -22,6 +22,7 @@ import numpy.typing as npt
 import scipy.linalg
 
 from .device import DevArray, as_dev, axpby, contract
+from .operator_product import OperatorProduct
 from .sketch import orthogonal_sketch, stream_sketch
 from .tensor import Tensor, TensorSum, TensorTrain, _host, tt_gram
 from .utils import ArrayList, TTRank, process_tt_rank
@@ -49,13 +50,28 @@ class MPO(Tensor, TTLinearMap):
         self.rank = tuple(int(C.shape[0]) for C in cores[1:])
         self.shape = tuple(a * b for a, b in zip(self.in_shape, self.out_shape))
         self._dev = None
+        self._views = None
         self._dev_key = None
 
-    def dev_cores(self) -> List[DevArray]:
+    def resident(self) -> bool:
+        """True if ``dev_views`` has the cores of this very list in HBM already"""
         key = self._dev_key
-        if self._dev is None or key is None or len(key) != len(self.cores) or any(a is not b for a, b in zip(key, self.cores)):
-            self._dev = [as_dev(c).contiguous() for c in self.cores]
+        return self._views is not None and key is not None and len(key) == len(self.cores) and all(a is b for a, b in zip(key, self.cores))
+
+    def dev_views(self) -> List[DevArray]:
+        """The cores in HBM as they are laid out, uploaded once per list of cores: a strided view (the mode reversal of
+        ``OperatorProduct.T``) stays a view."""
+        if not self.resident():
+            self._views = [as_dev(c) for c in self.cores]
+            self._dev = None
             self._dev_key = tuple(self.cores)
+        return self._views
+
+    def dev_cores(self) -> List[DevArray]:
+        """The same, contiguous."""
+        views = self.dev_views()
+        if self._dev is None:
+            self._dev = [c.contiguous() for c in views]
         return self._dev
 
     prepare_device = dev_cores
@@ -98,6 +114,10 @@ class MPO(Tensor, TTLinearMap):
                 contract("jkl,ajb->aklb", M[i], C, out=new[i])
             cores.append(new.reshape(ri * ra, no, rl * rb))
         return TensorTrain(cores)
+
+    def lazy(self, other: TensorTrain) -> OperatorProduct:
+        """``self(other)`` as a tensor that keeps its two factors: the sketches take it without forming the product."""
+        return OperatorProduct(self, other)
 
     @classmethod
     def random(cls, rank: TTRank, in_shape: Tuple[int, ...], out_shape: Tuple[int, ...]) -> "MPO":
@@ -142,6 +162,13 @@ class TTPrecond(TTLinearMap):
         return self._dev
 
     def _apply(self, other: TensorTrain, mats) -> TensorTrain:
+        if isinstance(other, OperatorProduct):         # into the operator core of the mode: the product stays unformed
+            cores = list(other.mpo.dev_views())        # resident once per MPO: nothing is uploaded per Krylov step
+            M = cores[self.mode]
+            for mat in mats:
+                M = contract("ki,bjic->bjkc", mat, M)
+            cores[self.mode] = M
+            return OperatorProduct(type(other.mpo)(cores), other.tt)
         cores = list(other.dev_cores())
         C = cores[self.mode]
         for mat in mats:
@@ -161,12 +188,14 @@ class TTPrecond(TTLinearMap):
 
 class TTLinearMapSum:
     """A list of ``TTLinearMap`` applied to a train (or to each term of a sum of trains); the result
-    is the lazy sum of all products (reference tt_gmres.py:171-207)."""
+    is the lazy sum of all products (reference tt_gmres.py:171-207).  ``lazy=True``: the ``MPO`` maps among them return
+    ``OperatorProduct``s, which the sketched roundings take as they are; other maps are applied as before."""
 
-    def __init__(self, linear_maps: List[TTLinearMap]) -> None:
+    def __init__(self, linear_maps: List[TTLinearMap], lazy: bool = False) -> None:
         if len(linear_maps) == 0:
             raise ValueError("linear_maps cannot be empty")
         self.linear_maps = linear_maps
+        self.lazy = bool(lazy)
         self.in_shape = linear_maps[0].in_shape
         self.out_shape = linear_maps[0].out_shape
         for lm in linear_maps[1:]:
@@ -177,6 +206,9 @@ class TTLinearMapSum:
 
     def __call__(self, input_tensor: Union[TensorTrain, TensorSum]) -> TensorSum:
         terms = [input_tensor] if isinstance(input_tensor, TensorTrain) else input_tensor.tensors
+        if self.lazy:
+            return TensorSum([lm.lazy(t) if isinstance(lm, MPO) and type(t) is TensorTrain else lm(t)
+                              for lm in self.linear_maps for t in terms])
         return TensorSum([lm(t) for lm in self.linear_maps for t in terms])
 
 
@@ -188,7 +220,10 @@ def round_tt_sum(tt_sum: TensorSum, max_rank: TTRank, eps: Optional[float] = Non
     """Round a sum of trains to ``max_rank`` (reference tt_gmres.py:258-305): ``"exact"`` = direct
     sum then TT-SVD, ``"pairwise"`` = add and round term by term, ``"sketch"`` = streaming sketch
     with right rank ``ceil(oversample_factor * left)``, ``"orth_sketch"`` = orthogonal sketch,
-    ``None`` = no rounding.  The two SVD variants run ``add`` / ``round_dev`` on the device."""
+    ``None`` = no rounding.  The two SVD variants run ``add`` / ``round_dev`` on the device.  Only the two sketches take
+    an ``OperatorProduct`` term as it is; the other methods form it first."""
+    if method in ("exact", "pairwise", None) and any(isinstance(t, OperatorProduct) for t in tt_sum.tensors):
+        tt_sum = TensorSum([t.to_tt() if isinstance(t, OperatorProduct) else t for t in tt_sum.tensors])
     if method == "exact":
         terms = [t.to_device() for t in tt_sum.tensors]
         tt = terms[0]
@@ -217,10 +252,15 @@ def tt_sum_gmres(A: TTLinearMapSum, b: TensorTrain, max_rank: TTRank,
                  x0: Optional[TensorTrain] = None, tolerance: float = 1e-6, maxiter: int = 100,
                  symmetric: bool = False, rounding_method: ROUNDING_MODE = "pairwise",
                  rounding_method_final: Optional[ROUNDING_MODE] = None, save_basis: bool = False,
-                 verbose: bool = False) -> Tuple[TensorTrain, Dict[str, List]]:
+                 verbose: bool = False, lazy_products: bool = False) -> Tuple[TensorTrain, Dict[str, List]]:
     """GMRES for a ``TTLinearMapSum`` (reference tt_gmres.py:308-432; Dolgov, arXiv:1206.5512, with
     the rounding after each operator product and each Gram-Schmidt step done by ``round_tt_sum``).
-    Returns the rounded solution and the history dictionary with the reference's keys."""
+    Returns the rounded solution and the history dictionary with the reference's keys.  ``lazy_products=True`` leaves the
+    operator products of every Krylov step unformed (``OperatorProduct``); it needs a sketched ``rounding_method``."""
+    if lazy_products:
+        if rounding_method not in ("sketch", "orth_sketch"):
+            raise ValueError(f"lazy_products needs rounding_method 'sketch' or 'orth_sketch', got {rounding_method!r}")
+        A = TTLinearMapSum(A.linear_maps, lazy=True)
     if final_round_rank is None:
         final_round_rank = max_rank
     if rounding_method_final is None:
