@@ -317,6 +317,37 @@ int ttsk_tt_gram(const double *const *dev_cores_a, const int64_t *ranks_a, int K
 int ttsk_op_apply(int K, const double *const *L, const double *const *M, const double *const *C, const int64_t *dims,
                   const int64_t *strides, int64_t l, double *W, int64_t w_cols, int stream);
 
+/* ---- CP tensors against tensor-train DRMs, no panels (csrc/cp_pass.hip, plan in csrc/cp_pass_plan.h) ----
+ * A CP tensor of rank N has factor matrices V_mu (n x N).  The step of TensorTrainDRM.sketch_cp (tensor_train_drm.py:90-107)
+ * and the Psi / Omega of cp_sketch.py:6-36 are one GEMM each whose Khatri-Rao operand is formed in registers; the N x n x
+ * rank panels of the reference never exist.  All sizes and strides count doubles (elements, not bytes).
+ *
+ * ttsk_cp_chain_step:  out[j, m] = sum_{a, k} L[j, a] V[k, j] D[a, k, m]
+ *   L      (N x rho), row j at L + j ldl, columns contiguous; NULL: rho = 1 and L == 1 (the first mode; ldl is not read)
+ *   V      (n x N), element (k, j) at V + k v_k + j v_j: any view of a factor matrix, transposed or a column slice
+ *   D      (rho, n, rho') contiguous, the DRM core
+ *   out    (N x rho'), row j at out + j ldo; columns from rho' on are not touched
+ * ttsk_cp_psi_omega:   psi[i, k, m] = sum_j L[j, i] V[k, j] R[j, m]   and   omega[i, m] = sum_j L[j, i] R_om[j, m]
+ *   L      (N x l), row j at L + j ldl; NULL: l = 1 and L == 1 (the first mode)
+ *   R      (N x r), row j at R + j ldr; NULL: r = 1 and R == 1 (the last mode)
+ *   V      as above; may be NULL when psi is
+ *   psi    (l, n, r) contiguous, or NULL (n is not read then)
+ *   R_om   (N x r_om), row j at R_om + j ld_om: in a sketch Psi_mu and Omega_{mu-1} share the left contraction L_{mu-1}, but
+ *          Omega pairs it with the right contraction of its own bond.  NULL: R itself, omega[i, m] = sum_j L[j, i] R[j, m]
+ *          (ld_om and r_om are not read)
+ *   omega  (l, r_om) contiguous, or NULL: the columns of Omega ride in the same launch as further columns with V == 1
+ * The sum over j is cut into chunks of 512 whose partials (workspace of the library, chunks x the outputs) a closing
+ * launch adds in ascending chunk order; with N <= 512 the one launch writes the outputs itself.  No atomics: the same bits
+ * on every call.  TTSK_ERR_ARG: a NULL V, D or out, neither psi nor omega, a size below 1, a NULL L or R with its rank
+ * != 1, a leading dimension below its width.  TTSK_ERR_UNSUPPORTED before anything is launched: rho, rho', l, r or r_om beyond
+ * 128, N or n of 2^31 or more, rho n beyond 2^31 - 65, more than 2^31 - 1 workgroups, partials that 64 bits do not
+ * address (the caller then composes the products from ttsk_gemm).  Inside those bounds every shape runs. */
+int ttsk_cp_chain_step(const double *L, int64_t ldl, const double *V, int64_t v_k, int64_t v_j, const double *D, double *out,
+                       int64_t ldo, int64_t N, int64_t rho, int64_t n, int64_t rho1, int stream);
+int ttsk_cp_psi_omega(const double *L, int64_t ldl, const double *R, int64_t ldr, const double *V, int64_t v_k, int64_t v_j,
+                      double *psi, const double *R_om, int64_t ld_om, int64_t r_om, double *omega, int64_t N, int64_t l, int64_t n,
+                      int64_t r, int stream);
+
 /* ---- a tensor train against a dense tensor (csrc/tt_dense_stats.hip) ----------
  * Tensor.error / dot / norm for a DenseTensor argument (tensor.py:53-88) and TensorTrain.dense in one pass over the
  * tensor.  The train is cut at a bond: T^{<k>} = L R, dev_L (M x rho) and dev_R (rho x N) row-major and contiguous.

@@ -96,12 +96,18 @@ class TensorTrainDRM(CansketchSparse, CansketchTT, CansketchCP, CanSlice, Canske
     # ------------------------------------------------------------------ CP input
     @handle_transpose
     def sketch_cp(self, tensor):
-        """L_mu[i,l] = sum_{j,k} L_{mu-1}[i,j] V_mu[k,i] D_mu[j,k,l] (reference :90-107)."""
+        """L_mu[i,l] = sum_{j,k} L_{mu-1}[i,j] V_mu[k,i] D_mu[j,k,l] (reference :90-107): one ``ttsk_cp_chain_step`` per mode
+        that forms L_{mu-1} o V_mu in registers, or, where its plan refuses the shape, the two ``contract`` calls below with
+        their N x n x rank panel W."""
+        from ..cp_fused import chain_step
         Vs = tensor.dev_cores()
         L = None
         for mu in range(len(self.shape) - 1):
             V, D = Vs[mu], self._core(mu)
-            if mu == 0:
+            Lk = chain_step(L, V, D)
+            if Lk is not None:
+                L = Lk
+            elif mu == 0:
                 L = contract("ij,ik->jk", V, D[0])
             else:
                 W = contract("ij,jkl->ikl", L, D)

@@ -291,11 +291,13 @@ def _sketch_pass(tensor: Tensor, left_drm: Optional[DRM], right_drm: DRM, method
 def general_sketch(tensor: Tensor, left_drm: Optional[DRM], right_drm: DRM,
                    method: SketchMethod) -> SketchContainer:
     """Sketch on the device, result copied to a host ``SketchContainer``."""
-    from . import operator_fused, sparse_fused, tt_fused
+    from . import cp_fused, operator_fused, sparse_fused, tt_fused
     fused = tt_fused.try_stream_sketch(tensor, left_drm, right_drm, method)
     if fused is None:
         fused = sparse_fused.try_sparse_gauss_sketch(tensor, left_drm, right_drm, method)
     if fused is None:
         fused = operator_fused.try_operator_sketch(tensor, left_drm, right_drm, method)
+    if fused is None:
+        fused = cp_fused.try_cp_sketch(tensor, left_drm, right_drm, method)
     Psi, Omega = fused if fused is not None else general_sketch_device(tensor, left_drm, right_drm, method)
     return SketchContainer(Psi, Omega)
