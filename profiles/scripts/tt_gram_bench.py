@@ -7,7 +7,8 @@ device events on library stream 0:
 at two shapes:
 
   (a) the recompression check: d = 6, n = 200, ranks 50 against 100.  `gram` is the 2 x 2 Gram of error(fast=True), with
-      the routing rule of tt_gram (DESIGN section 12) switched off, here and below, so that the pass itself is timed;
+      the routing rule of tt_gram switched off (route="kernel"), here and below, so that the pass
+      itself is timed;
       `composed` is error(relative=True) as it is without `fast`: add + QR sweep (norm) of the rank-150 direct sum and
       the QR sweep of the reference norm.  `chain` is the `contract` chain of dot() for the three products the formula
       needs.
@@ -33,6 +34,7 @@ import numpy as np
 from tt_sketch_amd import TensorTrain, tt_gram, _native as nat
 from tt_sketch_amd import tensor as tmod
 from tt_sketch_amd.device import DevArray
+from tt_sketch_amd.paths import forced
 from tt_sketch_amd.tensor import _tt_dot_composed
 
 WARM = 2
@@ -90,7 +92,8 @@ def case_a(reps):
     got = {}
 
     def gram():
-        got["gram"] = a.error(b, fast=True, relative=True)
+        with forced("kernel"):                  # error() calls tt_gram without a keyword
+            got["gram"] = a.error(b, fast=True, relative=True)
 
     def composed():
         got["composed"] = a.error(b, relative=True)
@@ -117,7 +120,7 @@ def case_b(reps):
     got = {}
 
     def gram():
-        got["gram"] = tt_gram([w], basis)[0]
+        got["gram"] = tt_gram([w], basis, route="kernel")[0]
 
     def composed():
         got["composed"] = np.array([_tt_dot_composed(w, v) for v in basis])
@@ -138,7 +141,7 @@ def case_mid(name, shape, r, K, M, reps):
     got = {}
 
     def gram():
-        got["gram"] = tt_gram(As, Bs)
+        got["gram"] = tt_gram(As, Bs, route="kernel")
 
     def composed():
         got["composed"] = np.array([[_tt_dot_composed(a, b) for b in Bs] for a in As])
@@ -161,7 +164,6 @@ def main():
     ap.add_argument("--reps", type=int, default=21)
     args = ap.parse_args()
     nat.call("ttsk_init", 0)
-    tmod._GRAM_ROUTE = False                # the pass itself at every shape, wherever the API's routing rule would send it
     recs = []
     if "a" in args.cases:
         recs.append(case_a(args.reps))

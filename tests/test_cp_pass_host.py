@@ -358,30 +358,121 @@ def test_oracle_matches_the_recorded_reference_runs(method):
 
 
 # ---- 4. the routing switch
+class _Reached(Exception):
+    """the call got as far as this"""
+
+
+def _reach(name):
+    def stop(*args, **kwargs):
+        raise _Reached(name)
+    return stop
+
+
 def test_route_switch_of_cp_fused():
     """no device behind it: what the switch does before any call"""
-    from tt_sketch_amd import cp_fused
-    assert cp_fused._route is None
+    from tt_sketch_amd import cp_fused, paths
+    assert cp_fused.forced is paths.forced and paths.ROUTES == (None, "kernel", "composed")
+    assert paths._forced is None
     with cp_fused.forced("composed"):
-        assert cp_fused._resolve(None) == "composed" and cp_fused._resolve("kernel") == "kernel"
+        assert paths.resolve(None) == "composed" and paths.resolve("kernel") == "kernel"
         assert cp_fused.chain_step(None, None, None) is None and cp_fused.psi_omega(None, None, None) is None
         with cp_fused.forced("kernel"):
-            assert cp_fused._resolve(None) == "kernel"
-        assert cp_fused._route == "composed"
-    assert cp_fused._route is None
+            assert paths.resolve(None) == "kernel"
+        assert paths._forced == "composed"
+    assert paths._forced is None
     with pytest.raises(ValueError):
-        cp_fused._resolve("fastest")
+        paths.resolve("fastest")
     with pytest.raises(ValueError):
         with cp_fused.forced("fastest"):
             pass
+    assert paths._forced is None
     assert cp_fused.try_cp_sketch(object(), None, None, None, route="composed") is None
+    # a route that is set is taken, None is the cost rule: the composition only where it is expected to be strictly faster
+    assert paths.taken("kernel", 2.0, 1.0) == "kernel" and paths.taken("composed", 1.0, 2.0) == "composed"
+    assert paths.taken(None, 2.0, 1.0) == "composed" and paths.taken(None, 1.0, 2.0) == "kernel" and paths.taken(None, 1.0, 1.0) == "kernel"
 
 
-def test_general_sketch_tries_the_cp_path():
-    import inspect
-    from tt_sketch_amd import sketch_dispatch
-    src = inspect.getsource(sketch_dispatch.general_sketch)
-    assert "cp_fused.try_cp_sketch(tensor, left_drm, right_drm, method)" in src
+def test_route_switch_through_op_apply(monkeypatch):
+    """the keyword, the context, their nesting and the rejection of an unknown route, all before any device call"""
+    import types
+    from tt_sketch_amd import _native as nat, operator_product as opm, paths
+    from tt_sketch_amd.device import DevArray, c_strides
+    fake = lambda *shape: DevArray(types.SimpleNamespace(ptr=4096), 0, shape, c_strides(shape))      # never dereferenced
+    L, M, C = fake(2, 3, 4), fake(2, 5, 6, 2), fake(3, 5, 3)
+    monkeypatch.setattr(opm, "_composed", _reach("composed"))
+    monkeypatch.setattr(nat, "call", lambda name, *a: _reach(name)())
+    run = lambda **kw: opm.op_apply([L], [M], [C], **kw)
+    with pytest.raises(ValueError, match="'kernel', 'composed' or None"):
+        opm.op_apply(None, None, None, route="fastest")
+    with pytest.raises(_Reached, match="composed"):
+        run(route="composed")
+    with pytest.raises(_Reached, match="ttsk_"):
+        run(route="kernel")
+    with paths.forced("composed"):
+        with pytest.raises(_Reached, match="composed"):
+            run()
+        with pytest.raises(_Reached, match="ttsk_"):
+            run(route="kernel")                     # the keyword goes before the context
+        with paths.forced("kernel"):
+            with pytest.raises(_Reached, match="ttsk_"):
+                run()
+        with pytest.raises(_Reached, match="composed"):
+            run()
+        with pytest.raises(ValueError, match="'kernel', 'composed' or None"):
+            run(route="fastest")
+    assert paths.resolve(None) is None
+    with pytest.raises(_Reached, match="composed"):          # the rule again: one small term is composed
+        run()
+
+
+def test_route_switch_through_tt_gram(monkeypatch):
+    from tt_sketch_amd import TensorTrain, _native as nat, paths, tensor as tmod, tt_gram
+    tts = [TensorTrain([np.ones((1, 3, 2)), np.ones((2, 4, 1))]) for _ in range(2)]
+    monkeypatch.setattr(tmod, "_gram_composed", _reach("composed"))
+    monkeypatch.setattr(nat, "call", lambda name, *a: _reach(name)())
+    with pytest.raises(ValueError, match="'kernel', 'composed' or None"):
+        tt_gram([], route="fastest")                # before the lists are looked at
+    with pytest.raises(_Reached, match="composed"):
+        tt_gram(tts, route="composed")
+    with pytest.raises(_Reached, match="ttsk_"):
+        tt_gram(tts, route="kernel")
+    with paths.forced("composed"):
+        with pytest.raises(_Reached, match="composed"):
+            tt_gram(tts)
+        with pytest.raises(_Reached, match="ttsk_"):
+            tt_gram(tts, route="kernel")
+        with paths.forced("kernel"):
+            with pytest.raises(_Reached, match="ttsk_"):
+                tt_gram(tts, tts)
+        with pytest.raises(_Reached, match="composed"):
+            tt_gram(tts, tts)
+    assert paths.resolve(None) is None
+    with pytest.raises(_Reached, match="ttsk_"):    # None: the rule is asked once the cores are on the device
+        tt_gram(tts)
+
+
+def test_general_sketch_asks_the_fused_paths_in_order(monkeypatch):
+    """TT streaming, sparse one-pass, operator product, CP: the first that returns a pair wins, and only when all four
+    decline does the generic driver run"""
+    from tt_sketch_amd import cp_fused, operator_fused, sketch_dispatch as sd, sparse_fused, tt_fused
+    assert sd.FUSED_PATHS == (tt_fused.try_stream_sketch, sparse_fused.try_sparse_gauss_sketch,
+                              operator_fused.try_operator_sketch, cp_fused.try_cp_sketch)
+    args = (object(), object(), object(), sd.SketchMethod.streaming)
+    pair = ([np.ones((1, 2, 1))], [])
+    for winner in range(5):
+        asked = []
+
+        def recorder(k):
+            def path(*a):
+                assert all(x is y for x, y in zip(a, args)) and len(a) == 4
+                asked.append(k)
+                return pair if k == winner else None
+            return path
+        monkeypatch.setattr(sd, "FUSED_PATHS", tuple(recorder(k) for k in range(4)))
+        monkeypatch.setattr(sd, "general_sketch_device", lambda *a: asked.append("generic") or pair)
+        out = sd.general_sketch(*args)
+        assert asked == (list(range(winner + 1)) if winner < 4 else [0, 1, 2, 3, "generic"])
+        assert type(out) is sd.SketchContainer and len(out.Psi_cores) == 1
 
 
 # ---- 5. the routing rule of the chain step

@@ -173,6 +173,31 @@ def test_rank_past_the_cover_is_refused_by_c_and_composed_by_python(tsa, n_cu):
     assert abs(G[0, 1] - ref) <= 2 * tol and abs(G[1, 0] - ref) <= 2 * tol
 
 
+def test_route_keyword_and_forced_context(tsa, n_cu):
+    """``route=`` of tt_gram: the pass itself under "kernel" (ranks on both sides of 16: the FMA and the matrix-instruction
+    body), the chain under "composed" and under ``forced("composed")``, and past the cover a refusal instead of the chain."""
+    from tt_sketch_amd import _native as nat, paths, tensor as tmod
+    rng = np.random.default_rng(21)
+    shape = (3, 4, 3)
+    A = [gr.random_cores(rng, shape, rk) for rk in ((1, 15), (16, 17))]
+    B = [gr.random_cores(rng, shape, rk) for rk in ((17, 1), (15, 16), (16, 16))]
+    dA, dB = [tsa.TensorTrain(a).to_device() for a in A], [tsa.TensorTrain(b).to_device() for b in B]
+    G = tsa.tt_gram(dA, dB, route="kernel")
+    assert G.shape == (2, 3)
+    check(G, A, B, n_cu, "tt_gram(route='kernel')")
+    assert np.array_equal(G, tsa.tt_gram(dA, dB, route="kernel"))
+    composed = tsa.tt_gram(dA, dB, route="composed")
+    assert np.array_equal(composed, tmod._gram_composed(dA, dB, False))
+    with paths.forced("composed"):
+        assert np.array_equal(tsa.tt_gram(dA, dB), composed)
+    w = gr.random_cores(rng, shape, (129, 5))
+    wide = tsa.TensorTrain(w).to_device()
+    with pytest.raises(nat.TtskUnsupported):
+        tsa.tt_gram([wide], dB, route="kernel")
+    # None still composes, as in the test above: the chain and NumPy each within half the bound
+    assert (np.abs(tsa.tt_gram([wide], dB) - gr.gram([w], B)) <= 2 * gr.bound([w], B, n_cu)).all()
+
+
 # ---- 3. the ABI
 def test_argument_errors(tsa):
     from tt_sketch_amd import _native as nat

@@ -450,6 +450,33 @@ def test_each_solver_decision_has_one_definition():
     assert "linalg.hip" not in src and {"jacobi.hip", "householder.hip", "cholesky.hip", "pinv.hip"} <= set(src)
 
 
+def test_each_path_decision_has_one_definition():
+    """paths.py is the only place that asks whether a DRM is a rank slice or validates a route; the module switch of
+    tt_gram is gone; and no fused module imports SketchMethod inside a function (sketch_dispatch and they no longer import
+    each other for it)."""
+    import glob
+    import re
+    import tt_sketch_amd
+    from tt_sketch_amd import paths, sketch_dispatch
+    pkg = os.path.dirname(nat.__file__)
+    src = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(pkg, "*.py"))}
+    where = lambda pat: sorted(f for f, s in src.items() if re.search(pat, s))
+    # "is this a rank slice": rank_min compared with the zeros, rank_max with true_rank
+    slice_test = r"rank_min\)?\s*[!=]=|rank_max\)?\s*[!=]=\s*(tuple\()?[\w.]*true_rank"
+    assert re.search(slice_test, "tuple(m.rank_min) != (0,) * (d - 1)") and re.search(slice_test, "m.rank_max == m.true_rank")
+    assert where(slice_test) == ["paths.py"]
+    assert where(r"'kernel', 'composed' or None") == ["paths.py"]
+    assert where(r"_GRAM_ROUTE") == []
+    for f in ("tt_fused.py", "cp_fused.py", "operator_fused.py", "sparse_fused.py"):
+        assert not re.search(r"^[ \t]+from [.\w]+ import .*\bSketchMethod\b", src[f], re.M), f
+        assert re.search(r"^from \.paths import .*\bSketchMethod\b", src[f], re.M), f
+    assert sketch_dispatch.SketchMethod is paths.SketchMethod is tt_sketch_amd.SketchMethod
+    imported = set(re.findall(r"^\s*from \.(\w+)", src["paths.py"], re.M))
+    for names in re.findall(r"^\s*from \. import (.+)$", src["paths.py"], re.M):
+        imported |= {n.split()[0] for n in names.split(",")}
+    assert not imported & {"sketch_dispatch", "sketch", "tt_fused", "cp_fused", "operator_fused", "sparse_fused"}, imported
+
+
 def _outside_lab_blocks(text):
     """text with every line inside `#ifdef TTSK_LAB` ... (`#else` | `#endif`) blanked: what the shipped library compiles."""
     import re

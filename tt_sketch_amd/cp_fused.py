@@ -12,41 +12,20 @@ Psi_mu together with Omega_{mu-1}, which shares its left contraction -- 3 d - 2 
 section 14).
 
 Routing: ``ttsk_cp_psi_omega`` wherever its plan accepts; the chain step by a cost rule (``chain_route_ms``), because one
-workgroup per 128 rows loses to the two launch-bound GEMMs at small N.  ``route="kernel"`` / ``"composed"`` (or the ``forced`` context, for the
-calls that the generic path makes without a keyword) takes that route whatever the default is; with ``"kernel"`` a refusal
+workgroup per 128 rows loses to the two launch-bound GEMMs at small N.  ``route=`` and the ``forced`` context are the switch
+of ``paths.py``: ``"kernel"`` / ``"composed"`` takes that route whatever the default is, and with ``"kernel"`` a refusal
 raises instead of falling back, so a test knows which code it ran.
 """
 from __future__ import annotations
 
-import contextlib
 from typing import List, Optional, Tuple
 
 import numpy as np
 
 from . import _native as nat
 from .device import DevArray, contract
-
-_ROUTES = (None, "kernel", "composed")
-_route: Optional[str] = None          # what `forced` has set
-
-
-@contextlib.contextmanager
-def forced(route: Optional[str]):
-    """Every CP chain step, Psi and Omega inside the block takes ``route``."""
-    global _route
-    if route not in _ROUTES:
-        raise ValueError(f"route {route!r}: 'kernel', 'composed' or None")
-    saved, _route = _route, route
-    try:
-        yield
-    finally:
-        _route = saved
-
-
-def _resolve(route: Optional[str]) -> Optional[str]:
-    if route not in _ROUTES:
-        raise ValueError(f"route {route!r}: 'kernel', 'composed' or None")
-    return _route if route is None else route
+from .paths import SketchMethod, drm_pair, forced, resolve, taken      # (`forced`: tests and profiles/scripts reach it here)
+from .tensor import CPTensor
 
 
 def _rows(A: Optional[DevArray]) -> bool:
@@ -83,7 +62,7 @@ def chain_route_ms(N: int, rho: int, n: int, rho1: int, first_mode: bool = False
 def chain_step(L: Optional[DevArray], V: DevArray, D: DevArray, route: Optional[str] = None, stream: int = 0) -> Optional[DevArray]:
     """``out[j, m] = sum_{a, k} L[j, a] V[k, j] D[a, k, m]`` as a new ``(N, rho')`` array; ``L`` None is the first mode
     (``rho = 1``).  ``V`` is taken with its strides, ``D`` is made contiguous.  None: the caller composes."""
-    route = _resolve(route)
+    route = resolve(route)
     if route == "composed":
         return None
     n, N = V.shape
@@ -94,10 +73,8 @@ def chain_step(L: Optional[DevArray], V: DevArray, D: DevArray, route: Optional[
         return _refused(route, f"chain of strides {L.strides}")
     if N == 0 or n == 0 or rho1 == 0:
         return _refused(route, "an empty operand")
-    if route is None:
-        kernel_ms, composed_ms = chain_route_ms(N, rho, n, rho1, L is None)
-        if composed_ms < kernel_ms:
-            return None
+    if route is None and taken(route, *chain_route_ms(N, rho, n, rho1, L is None)) == "composed":
+        return None
     out = DevArray.empty((N, rho1), stream=stream)
     try:
         nat.call("ttsk_cp_chain_step", L, 0 if L is None else _ld(L), V, V.strides[0], V.strides[1], D.contiguous(stream), out, rho1,
@@ -114,7 +91,7 @@ def psi_omega(L: Optional[DevArray], R: Optional[DevArray], V: Optional[DevArray
     """``(Psi, Omega)`` of one launch: ``Psi[i, k, m] = sum_j L[j, i] V[k, j] R[j, m]`` as ``(l, n, r)`` and
     ``Omega[i, m] = sum_j L[j, i] R_om[j, m]`` (``R_om`` None: ``R``), each None unless asked for.  ``L`` / ``R`` None are the
     first / last mode (rank 1, all ones).  None instead of the pair: the caller composes."""
-    route = _resolve(route)
+    route = resolve(route)
     if route == "composed":
         return None
     if not (psi or omega) or (psi and V is None):
@@ -162,21 +139,12 @@ def _chain(Vs: List[DevArray], drm, route, stream: int) -> List[DevArray]:
 def try_cp_sketch(tensor, left_drm, right_drm, method, route: Optional[str] = None) -> Optional[Tuple[list, list]]:
     """(Psi, Omega) device arrays, or None if the path does not apply: a streaming sketch of a ``CPTensor`` with a left and
     a right ``TensorTrainDRM`` (rank slices of a blocked sketch included) whose shapes the two entries cover."""
-    from .drm.tensor_train_drm import TensorTrainDRM
-    from .sketch_dispatch import SketchMethod
-    from .tensor import CPTensor
-    route = _resolve(route)
+    route = resolve(route)
     if route == "composed" or method != SketchMethod.streaming or type(tensor) is not CPTensor:
         return None
-    if type(left_drm) is not TensorTrainDRM or type(right_drm) is not TensorTrainDRM:
-        return None
-    if left_drm.transpose or not right_drm.transpose:
+    if not drm_pair(tensor.shape, left_drm, right_drm):
         return None
     d = len(tensor.shape)
-    if d < 2 or len(left_drm.cores) != d - 1 or len(right_drm.cores) != d - 1:
-        return None
-    if tuple(left_drm.shape) != tuple(tensor.shape) or tuple(right_drm.shape) != tuple(tensor.shape):
-        raise ValueError(f"Shape {left_drm.shape} of DRM doesn't match tensor's shape {tensor.shape}")
     Vs = tensor.dev_cores()
     for drm in (left_drm, right_drm):
         drm.dev_cores()                                   # uploads, if any, before the streams part

@@ -134,7 +134,7 @@ class _Buffer:
         self.ptr = None
 
 
-def _c_strides(shape):
+def c_strides(shape):
     st, acc = [], 1
     for n in reversed(shape):
         st.append(acc)
@@ -160,7 +160,7 @@ class DevArray:
         """``stream``: the library stream that touches the array first (see the pool note above)."""
         shape = tuple(int(s) for s in (shape if np.ndim(shape) else (shape,)))
         n = _prod(shape)
-        return cls(_Buffer(n * np.dtype(dtype).itemsize, stream), 0, shape, _c_strides(shape), dtype)
+        return cls(_Buffer(n * np.dtype(dtype).itemsize, stream), 0, shape, c_strides(shape), dtype)
 
     @classmethod
     def zeros(cls, shape, dtype=_F64, stream=0) -> "DevArray":
@@ -316,7 +316,7 @@ def _view_strides(shape, strides, new_shape) -> Optional[Tuple[int, ...]]:
     old = [(n, s) for n, s in zip(shape, strides) if n != 1]
     new_strides = [0] * len(new_shape)
     if _prod(new_shape) == 0:
-        return _c_strides(new_shape)
+        return c_strides(new_shape)
     oi = 0
     ni = 0
     nn = len(new_shape)

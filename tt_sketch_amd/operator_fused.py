@@ -12,8 +12,8 @@ from __future__ import annotations
 from typing import List, Optional, Tuple
 
 from .device import DevArray, contract
-from .drm.tensor_train_drm import TensorTrainDRM
 from .operator_product import OperatorProduct, chain_start, op_apply
+from .paths import SketchMethod, drm_pair
 from .tensor import TensorSum, TensorTrain
 
 
@@ -46,27 +46,19 @@ def _chain(terms, drm_cores, route=None) -> Tuple[List[DevArray], List[DevArray]
 def try_operator_sketch(tensor, left_drm, right_drm, method, route: Optional[str] = None) -> Optional[Tuple[list, list]]:
     """(Psi, Omega) device arrays, or None if the path does not apply: streaming sketches, unsliced ``TensorTrainDRM``s,
     an ``OperatorProduct`` or a ``TensorSum`` of ``OperatorProduct``s and ``TensorTrain``s with at least one product.
-    ``route`` goes to ``op_apply``: None is its routing rule, ``"kernel"`` / ``"composed"`` that route at every step."""
-    from .sketch_dispatch import SketchMethod
+    ``route`` goes to ``op_apply`` (the switch of ``paths.py``): None is its routing rule, ``"kernel"`` / ``"composed"`` that
+    route at every step."""
     if method != SketchMethod.streaming:
-        return None
-    if type(left_drm) is not TensorTrainDRM or type(right_drm) is not TensorTrainDRM:
-        return None
-    if left_drm.transpose or not right_drm.transpose:
         return None
     terms = tensor.tensors if type(tensor) is TensorSum else [tensor]
     if not terms or not all(type(t) in (OperatorProduct, TensorTrain) for t in terms):
         return None
     if not any(type(t) is OperatorProduct for t in terms):
         return None
-    d = len(tensor.shape)
-    drms = (left_drm, right_drm)
-    if d < 2 or any(len(m.cores) != d - 1 for m in drms):
+    # (a rank slice of a blocked sketch: the general path)
+    if not drm_pair(tensor.shape, left_drm, right_drm, sliced_ok=False):
         return None
-    if any(tuple(m.rank_min) != (0,) * (d - 1) or tuple(m.rank_max) != tuple(m.true_rank) for m in drms):
-        return None                                   # a rank slice of a blocked sketch: the general path
-    if any(tuple(m.shape) != tuple(tensor.shape) for m in drms):
-        raise ValueError(f"Shape {left_drm.shape} of DRM doesn't match tensor's shape {tensor.shape}")
+    d = len(tensor.shape)
     if any(tuple(t.shape) != tuple(tensor.shape) for t in terms):
         return None
     for t in terms:

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _native as nat
 from .device import DevArray, contract, copy_into
+from .paths import resolve, taken
 from .tensor import Tensor, TensorTrain, _host
 
 MAX_TERMS = 24          # OP_MAX_TERMS of csrc/op_apply_plan.h: the terms of one ttsk_op_apply call
@@ -61,7 +62,8 @@ def op_apply(Ls: Sequence[DevArray], Ms: Sequence[Optional[DevArray]], Cs: Seque
     ``Ls[p]`` is ``(R, r, l)``, ``Ms[p]`` ``(R, n_in, n_out, R')`` or None for a plain train (``W = L o C``), ``Cs[p]``
     ``(r, n_in, r')``; operator and train cores may be strided views.  Lists longer than one call holds are cut.  Where
     the routing rule expects it to be faster, W is composed from `contract` calls term by term instead; ``route="kernel"``
-    or ``"composed"`` takes that route whatever the rule says."""
+    or ``"composed"`` (or ``paths.forced``) takes that route whatever the rule says."""
+    route = resolve(route)
     dims, strides, offs, keep, off = [], [], [], [], 0
     l = int(Ls[0].shape[2])
     for L, M, C in zip(Ls, Ms, Cs):
@@ -81,11 +83,8 @@ def op_apply(Ls: Sequence[DevArray], Ms: Sequence[Optional[DevArray]], Cs: Seque
         offs.append(off)
         off += R1 * r1
     n_out = dims[0][5]
-    if route not in (None, "kernel", "composed"):
-        raise ValueError(f"route {route!r}: 'kernel', 'composed' or None")
     if route is None:
-        kernel_ms, composed_ms = route_ms([d[:6] + (l, M is None) for d, M in zip(dims, Ms)])
-        route = "composed" if composed_ms < kernel_ms else "kernel"
+        route = taken(route, *route_ms([d[:6] + (l, M is None) for d, M in zip(dims, Ms)]))
     if route == "composed":
         if len(dims) == 1:
             return _composed(keep[0], Ms[0], Cs[0], stream), offs

@@ -16,11 +16,13 @@ import numpy as np
 import numpy.typing as npt
 
 from . import _native as nat
+from . import tt_fused
 from .device import DevArray, as_dev, contract, sync, to_host
 from .drm import ALL_DRM, DenseGaussianDRM, SparseGaussianDRM, TensorTrainDRM
 from .drm_base import DRM, CanIncreaseRank, CanSlice
 from .sketch_container import SketchContainer
-from .sketch_dispatch import SketchMethod, general_sketch
+from .paths import SketchMethod, drm_pair
+from .sketch_dispatch import general_sketch, robust_reruns
 from .sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchSparse,
                                                  CansketchTT)
 from .tensor import DenseTensor, Tensor, TensorTrain
@@ -135,14 +137,11 @@ def stream_sketch_batch(tensors: Sequence[Tensor], left_rank: TTRank, right_rank
     if not tensors:
         return ([], left_drm, right_drm) if return_drm else []
     left_drm, right_drm = _stream_drms(tensors[0], left_rank, right_rank, seed, left_drm_type, right_drm_type, left_drm, right_drm)
-    from . import tt_fused
-    batched = (type(left_drm) is TensorTrainDRM and type(right_drm) is TensorTrainDRM and not left_drm.transpose
-               and right_drm.transpose and all(type(t) is TensorTrain for t in tensors)
-               and all(tuple(t.shape) == tuple(tensors[0].shape) and tuple(t.rank) == tuple(tensors[0].rank) for t in tensors))
+    batched = (all(type(t) is TensorTrain for t in tensors)
+               and all(tuple(t.shape) == tuple(tensors[0].shape) and tuple(t.rank) == tuple(tensors[0].rank) for t in tensors)
+               and drm_pair(tensors[0].shape, left_drm, right_drm, cores=False))
     out = []
     if batched:
-        if tuple(left_drm.shape) != tuple(tensors[0].shape) or tuple(right_drm.shape) != tuple(tensors[0].shape):
-            raise ValueError(f"Shape {left_drm.shape} of DRM doesn't match tensor's shape {tensors[0].shape}")
         plan = tt_fused.TTSketchPlan(tensors[0].shape, tensors[0].rank, left_drm, right_drm)
         stride = plan.size + (plan.size & 1)
         buf = DevArray.empty((len(tensors) * stride,))
@@ -165,8 +164,6 @@ def _orth_batch(tensors, left_drm, right_drm, method, one):
     """the tensors through ``ttsk_tt_orth_sketch_batch`` in slices where that applies; ``one(t)``: the per-tensor call, for
     everything else and for tensors whose fast factorisations were rejected (rank-deficient Omega, ill-conditioned
     unfolding: the verdict comes back per tensor)"""
-    from . import tt_fused
-    from .sketch_dispatch import robust_reruns
     out = []
     for b0 in range(0, len(tensors), ORTH_BATCH_SLICE):
         part = tensors[b0:b0 + ORTH_BATCH_SLICE]
@@ -362,12 +359,11 @@ def _assemble_one_call(Psi, Om, direction):
             return None
     # every output and the pseudo-inverses in ONE allocation (a dozen pool round trips cost the host more than the device idles
     # for); pieces of equal shape are equally spaced
-    from .tt_fused import _carve
     if direction == "right":
         shapes = [(1 if mu == 0 else lr[mu - 1], n[mu], lr[mu]) for mu in range(d - 1)]
     else:
         shapes = [(rr[mu - 1], n[mu], 1 if mu == d - 1 else rr[mu]) for mu in range(1, d)]
-    arrs = _carve(shapes + [(rr[k], lr[k]) for k in range(d - 1)])
+    arrs = tt_fused._carve(shapes + [(rr[k], lr[k]) for k in range(d - 1)])
     cores = arrs[:d - 1] + [Psi[-1]] if direction == "right" else [Psi[0]] + arrs[:d - 1]
     work = arrs[d - 1:]
     nat.call("ttsk_tt_assemble", d, nat.i64_array(n), nat.i64_array(lr), nat.i64_array(rr), nat.ptr_array(Psi),
@@ -435,7 +431,6 @@ def _auto_direction(sketch: SketchContainer) -> str:
 def _assemble_batch_call(group, direction):
     """One ``ttsk_tt_assemble_batch`` call over sketches of one signature whose operands are device arrays; returns the
     cores per sketch (device-resident).  Cores of one mode are equally spaced in one allocation."""
-    from .tt_fused import _carve
     arrs = [s.device_arrays() for s in group]
     Psi0, Om0 = arrs[0]
     d = len(Psi0)
@@ -448,7 +443,7 @@ def _assemble_batch_call(group, direction):
     else:
         shapes = [(rr[mu - 1], n[mu], 1 if mu == d - 1 else rr[mu]) for mu in range(1, d)]
     per = shapes + [(rr[k], lr[k]) for k in range(d - 1)]
-    out = _carve(per * len(group))
+    out = tt_fused._carve(per * len(group))
     psi, om, work, cores = [], [], [], []
     for b, (Psi, Om) in enumerate(arrs):
         Psi = [p.contiguous() for p in Psi]

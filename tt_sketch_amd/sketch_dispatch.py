@@ -11,18 +11,19 @@ from __future__ import annotations
 import ctypes
 import os
 import sys
-import enum
 from functools import partial
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 
 from . import _native as nat
+from . import cp_fused, operator_fused, sparse_fused, tt_fused
 from .device import DevArray, as_dev, axpby, contract
 from .drm import TensorTrainDRM
 from .drm_base import DRM
 from .sketch_container import SketchContainer
 from .operator_product import OperatorProduct
+from .paths import SketchMethod
 from .sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchOperatorProduct, CansketchSparse,
                                                  CansketchTT, CanSketchTucker)
 from .sketching_methods.cp_sketch import sketch_omega_cp, sketch_psi_cp
@@ -177,12 +178,6 @@ class OrthogTTDRM:
         return next(self.generator)
 
 
-class SketchMethod(enum.Enum):
-    streaming = "streaming"
-    orthogonal = "orthogonal"
-    hmt = "hmt"
-
-
 def general_sketch_device(tensor: Tensor, left_drm: Optional[DRM], right_drm: DRM,
                           method: SketchMethod) -> Tuple[List[DevArray], List[DevArray]]:
     """The sketch as device arrays ``(Psi_cores, Omega_mats)`` (reference :202-275)."""
@@ -206,7 +201,6 @@ def _general_sketch_device(tensor: Tensor, left_drm: Optional[DRM], right_drm: D
         # Optimistic pass: every orthogonalisation as one call on the fast factorisations, no verdict awaited (the
         # d - 1 steps are sequential in mu: each blocking read-back drains the queue).  ONE read-back at the end; a
         # rejected factorisation (rank-deficient Omega, ill-conditioned unfolding) repeats the sketch on the robust path.
-        from . import tt_fused
         out, flag = None, ctypes.c_int(0)
         try:
             out = tt_fused.try_orth_sketch(tensor, left_drm, right_drm, method) if _ONE_CALL_ORTH else None
@@ -288,16 +282,17 @@ def _sketch_pass(tensor: Tensor, left_drm: Optional[DRM], right_drm: DRM, method
     return Psi_cores, Omega_mats
 
 
+# The fused paths, in the order they are asked: each takes (tensor, left_drm, right_drm, method) and returns the device
+# arrays (Psi, Omega), or None where it does not apply (what each accepts of a DRM pair: ``paths.drm_pair``).
+FUSED_PATHS = (tt_fused.try_stream_sketch, sparse_fused.try_sparse_gauss_sketch, operator_fused.try_operator_sketch,
+               cp_fused.try_cp_sketch)
+
+
 def general_sketch(tensor: Tensor, left_drm: Optional[DRM], right_drm: DRM,
                    method: SketchMethod) -> SketchContainer:
     """Sketch on the device, result copied to a host ``SketchContainer``."""
-    from . import cp_fused, operator_fused, sparse_fused, tt_fused
-    fused = tt_fused.try_stream_sketch(tensor, left_drm, right_drm, method)
-    if fused is None:
-        fused = sparse_fused.try_sparse_gauss_sketch(tensor, left_drm, right_drm, method)
-    if fused is None:
-        fused = operator_fused.try_operator_sketch(tensor, left_drm, right_drm, method)
-    if fused is None:
-        fused = cp_fused.try_cp_sketch(tensor, left_drm, right_drm, method)
-    Psi, Omega = fused if fused is not None else general_sketch_device(tensor, left_drm, right_drm, method)
-    return SketchContainer(Psi, Omega)
+    for path in FUSED_PATHS:
+        fused = path(tensor, left_drm, right_drm, method)
+        if fused is not None:
+            return SketchContainer(*fused)
+    return SketchContainer(*general_sketch_device(tensor, left_drm, right_drm, method))

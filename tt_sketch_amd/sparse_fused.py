@@ -20,6 +20,7 @@ from . import _native as nat
 from .device import DevArray, axpby
 from .drm.sparse_gaussian_drm import SparseGaussianDRM
 from .drm.sparse_sign_drm import SparseSignDRM
+from .paths import SketchMethod, drm_pair
 from .tensor import SparseTensor, TensorSum
 
 last_plan: dict = {}             # what the last sketch did (bench.py reads it): sampled columns per nonzero, table rows
@@ -140,10 +141,7 @@ def _mode_stream(tensor: SparseTensor, mu: int):
 
 def try_sparse_gauss_sketch(tensor, left_drm, right_drm, method):
     """(Psi, Omega) device arrays through the one-pass-per-mode path, or None if it does not apply."""
-    from .sketch_dispatch import SketchMethod
     if method != SketchMethod.streaming or os.environ.get("TTSK_SPARSE_FUSED", "1") == "0":
-        return None
-    if type(left_drm) not in (SparseGaussianDRM, SparseSignDRM) or type(right_drm) not in (SparseGaussianDRM, SparseSignDRM):
         return None
     if type(tensor) is TensorSum and tensor.tensors and all(type(t) is SparseTensor for t in tensor.tensors):
         # a sum of sparse tensors (the nnz shards of distributed.shard_tensor, reference tensor.py:215-234): every summand
@@ -159,16 +157,14 @@ def try_sparse_gauss_sketch(tensor, left_drm, right_drm, method):
         return Psi, Omega
     if type(tensor) is not SparseTensor:
         return None
-    if left_drm.transpose or not right_drm.transpose:
-        return None
     shape = tuple(int(n) for n in tensor.shape)
     d, N = len(shape), tensor.nnz
     if d < 2 or N == 0 or N >= 2**31:
         return None
     if max(shape) > MAX_MODE:
         return None
-    if tuple(left_drm.shape) != shape or tuple(right_drm.shape) != shape:
-        raise ValueError(f"Shape {left_drm.shape} of DRM doesn't match tensor's shape {tensor.shape}")
+    if not drm_pair(shape, left_drm, right_drm, kinds=(SparseGaussianDRM, SparseSignDRM), cores=False):
+        return None
     L = _Side(left_drm, shape, N)
     R = _Side(right_drm, shape[::-1], N)          # factor nu of the right DRM = suffix of d - 1 - nu.. = R_mu with mu = d - 2 - nu
     if any(not L.covered(k) or not R.covered(k) for k in range(d - 1)):

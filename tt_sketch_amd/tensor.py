@@ -28,6 +28,7 @@ import numpy as np
 import numpy.typing as npt
 
 from .device import DevArray, as_dev, axpby, contract, copy_into
+from .paths import resolve, taken
 from .utils import ArrayList, TTRank, process_tt_rank, random_normal
 
 
@@ -897,7 +898,6 @@ class TensorTrain(_GatherOnDevice, Tensor):
 _GRAM_MAX_TRAINS = 128       # K + M of one ttsk_tt_gram call
 # The routing rule of DESIGN section 12, its constants measured on one MI355X (profiles/tt_gram_bench.json): the work
 # of the pass beyond its launches against the time of the composed chain.
-_GRAM_ROUTE = True           # False: the pass wherever the entry covers the call (profiles/scripts/tt_gram_bench.py)
 _GRAM_CUS = 256              # the chip the constants were measured on; the plan's chunks per pair follow the CU count
 _GRAM_MAX_CHUNKS = 64        # GRAM_MAX_CHUNKS of tt_gram_plan.h
 _GRAM_REDUCE_MS = 0.9e-6     # per partial a workgroup adds while it forms acc (chunks x ra x rb of them per mode)
@@ -943,15 +943,18 @@ def _gram_composed(As, Bs, sym: bool) -> np.ndarray:
     return G
 
 
-def _gram_block(As: Sequence[TensorTrain], Bs: Sequence[TensorTrain], sym: bool = False) -> np.ndarray:
+def _gram_block(As: Sequence[TensorTrain], Bs: Sequence[TensorTrain], sym: bool = False, route: Optional[str] = None) -> np.ndarray:
     from . import _native as nat
+    route = resolve(route)
+    if route == "composed":
+        return _gram_composed(As, Bs, sym)
     d = As[0].ndim
     cores = [[c.contiguous() for c in t.dev_cores()] for t in list(As) + list(Bs)]
     ranks = [[c.shape[0] for c in cs] + [cs[-1].shape[2]] for cs in cores]
     K, M = len(As), len(Bs)
-    if _GRAM_ROUTE:
+    if route is None:
         work, chain = _gram_route_ms(np.array(ranks[:K]), np.array(ranks[K:]), As[0].shape)
-        if work > (chain * (K + 1) / (2 * M) if sym else chain):   # of a symmetric block the chain forms the upper triangle
+        if taken(route, work, chain * (K + 1) / (2 * M) if sym else chain) == "composed":   # of a symmetric block the chain forms the upper triangle
             return _gram_composed(As, Bs, sym)
     out = DevArray.empty((K, M))
     try:
@@ -959,11 +962,13 @@ def _gram_block(As: Sequence[TensorTrain], Bs: Sequence[TensorTrain], sym: bool 
                  nat.ptr_array([c for cs in cores[K:] for c in cs]), nat.i64_array([r for rk in ranks[K:] for r in rk]), M,
                  nat.i64_array(As[0].shape), d, out, 0)
     except nat.TtskUnsupported:
+        if route == "kernel":
+            raise
         return _gram_composed(As, Bs, sym)
     return out.get()
 
 
-def tt_gram(As: Sequence[TensorTrain], Bs: Optional[Sequence[TensorTrain]] = None) -> np.ndarray:
+def tt_gram(As: Sequence[TensorTrain], Bs: Optional[Sequence[TensorTrain]] = None, route: Optional[str] = None) -> np.ndarray:
     """``G[p, q] = <As[p], Bs[q]>`` as a ``(K, M)`` array (``Bs=None``: ``As``).  The trains share one shape and have each
     their own ranks; a host train is uploaded once (``dev_cores``).
 
@@ -972,7 +977,11 @@ def tt_gram(As: Sequence[TensorTrain], Bs: Optional[Sequence[TensorTrain]] = Non
     entry (a rank above 128), and where the routing rule of DESIGN section 12 (``_gram_route_ms``: few pairs of large
     ranks) expects the chain to be faster, a block is composed pair by pair from ``contract``, 2 d launches and a
     read-back each.  With ``Bs=None`` a single block computes only its upper triangle on the composed path; lists cut
-    into several blocks (``K + M > _GRAM_MAX_TRAINS``) compute every block in full, the lower ones too."""
+    into several blocks (``K + M > _GRAM_MAX_TRAINS``) compute every block in full, the lower ones too.
+
+    ``route`` is the switch of ``paths.py``: None is the rule above with its fallback, ``"composed"`` the chain for every
+    block, ``"kernel"`` the pass for every block, with the entry's ``TtskUnsupported`` where it refuses."""
+    route = resolve(route)
     As = list(As)
     sym = Bs is None
     Bs = As if sym else list(Bs)
@@ -985,11 +994,11 @@ def tt_gram(As: Sequence[TensorTrain], Bs: Optional[Sequence[TensorTrain]] = Non
             raise ValueError(f"tt_gram: trains of shapes {As[0].shape} and {t.shape}")
     K, M, half = len(As), len(Bs), _GRAM_MAX_TRAINS // 2
     if K + M <= _GRAM_MAX_TRAINS:
-        return _gram_block(As, Bs, sym)
+        return _gram_block(As, Bs, sym, route)
     out = np.empty((K, M))
     for p in range(0, K, half):
         for q in range(0, M, half):
-            out[p:p + half, q:q + half] = _gram_block(As[p:p + half], Bs[q:q + half])
+            out[p:p + half, q:q + half] = _gram_block(As[p:p + half], Bs[q:q + half], route=route)
     return out
 
 

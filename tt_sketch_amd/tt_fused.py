@@ -8,13 +8,15 @@ contractions as ``TensorTrainDRM.sketch_tt`` + ``sketch_omega_tt`` / ``sketch_ps
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Tuple
 
 import numpy as np
 
 from . import _native as nat
-from .device import DevArray
+from .device import DevArray, c_strides
 from .drm.tensor_train_drm import TensorTrainDRM
+from .paths import SketchMethod, drm_pair
 from .tensor import TensorSum, TensorTrain
 
 MAX_BATCH = 32   # tensors per batched pass (SK_MAXB in csrc/skinny.h); the library slices larger batches itself
@@ -88,12 +90,8 @@ class TTSketchPlan:
                      [(self.left_rank[mu], self.right_rank[mu]) for mu in range(d - 1)]
             off, lay = 0, []
             for shp in shapes:
-                st, acc = [], 1
-                for n in reversed(shp):
-                    st.append(acc)
-                    acc *= n
-                lay.append((off, shp, tuple(reversed(st))))
-                off += acc
+                lay.append((off, shp, c_strides(shp)))
+                off += math.prod(shp)
             self._layout = lay
         if out.strides != (1,):
             out = out.contiguous()
@@ -103,21 +101,13 @@ class TTSketchPlan:
 
 def try_stream_sketch(tensor, left_drm, right_drm, method) -> Optional[Tuple[list, list]]:
     """(Psi, Omega) device arrays through the one-call path, or None if it does not apply."""
-    from .sketch_dispatch import SketchMethod
     if method != SketchMethod.streaming:
-        return None
-    if type(left_drm) is not TensorTrainDRM or type(right_drm) is not TensorTrainDRM:
-        return None
-    if left_drm.transpose or not right_drm.transpose:
         return None
     terms = tensor.tensors if isinstance(tensor, TensorSum) else [tensor]
     if not terms or not all(type(t) is TensorTrain for t in terms):
         return None
-    d = len(tensor.shape)
-    if d < 2 or len(left_drm.cores) != d - 1 or len(right_drm.cores) != d - 1:
+    if not drm_pair(tensor.shape, left_drm, right_drm):
         return None
-    if tuple(left_drm.shape) != tuple(tensor.shape) or tuple(right_drm.shape) != tuple(tensor.shape):
-        raise ValueError(f"Shape {left_drm.shape} of DRM doesn't match tensor's shape {tensor.shape}")
     # Terms of one signature (mode sizes, TT ranks) go through the device together: every chain product is one
     # launch over all of them and Psi / Omega come out already summed (ttsk_tt_sketch_sum) -- the TensorSum loop
     # of sketch_dispatch.py:85-139 without its per-term sketches.
@@ -138,91 +128,32 @@ def try_stream_sketch(tensor, left_drm, right_drm, method) -> Optional[Tuple[lis
 
 def _carve(shapes) -> List[DevArray]:
     """contiguous arrays of the given shapes as views of one allocation (16-byte aligned pieces)"""
-    sizes = [int(np.prod(sh)) for sh in shapes]
+    sizes = [math.prod(int(n) for n in sh) for sh in shapes]
     offs, tot = [], 0
     for n in sizes:
         offs.append(tot)
         tot += n + (n & 1)
     buf = DevArray.empty((max(tot, 1),))
-    out = []
-    for sh, off in zip(shapes, offs):
-        st, acc = [], 1
-        for n in reversed(sh):
-            st.append(acc)
-            acc *= int(n)
-        out.append(DevArray(buf.buf, off, sh, tuple(reversed(st))))
-    return out
+    return [DevArray(buf.buf, off, sh, c_strides(sh)) for sh, off in zip(shapes, offs)]
 
 
-def try_orth_sketch(tensor, left_drm, right_drm, method) -> Optional[Tuple[list, list]]:
-    """``orthogonal`` / ``hmt`` sketch of ONE tensor train with tensor-train DRMs through ``ttsk_tt_orth_sketch``:
-    (cores, Omega) as device arrays, or None if the one-call path does not apply.  The verdicts of its fast
-    factorisations are deferred -- the caller reads ``ttsk_deferred_status`` (reference sketch_dispatch.py:160-193)."""
-    from .sketch_dispatch import SketchMethod
-    if method not in (SketchMethod.orthogonal, SketchMethod.hmt) or type(tensor) is not TensorTrain:
-        return None
-    orth = method == SketchMethod.orthogonal
-    if type(right_drm) is not TensorTrainDRM or not right_drm.transpose:
-        return None
-    if orth and (type(left_drm) is not TensorTrainDRM or left_drm.transpose):
-        return None
-    d = len(tensor.shape)
-    drms = [right_drm] + ([left_drm] if orth else [])
-    if d < 2 or any(len(m.cores) != d - 1 or tuple(m.shape) != tuple(tensor.shape) for m in drms):
-        return None
-    if any(tuple(m.rank_min) != (0,) * (d - 1) or tuple(m.rank_max) != tuple(m.true_rank) for m in drms):
-        return None                                   # a rank slice of a blocked sketch: the general path
-    arr = nat.i64_array
-    n, s = arr(tensor.shape), arr((1,) + tuple(tensor.rank) + (1,))
-    rt = arr((1,) + tuple(right_drm.true_rank))
-    keep = [[c.contiguous() for c in tensor.dev_cores()], [c.contiguous() for c in right_drm.dev_cores()]]
-    X, DR = nat.ptr_array(keep[0]), nat.ptr_array(keep[1])
-    right_rank = tuple(right_drm.rank[::-1])
-    if orth:
-        lt = arr((1,) + tuple(left_drm.true_rank))
-        keep.append([c.contiguous() for c in left_drm.dev_cores()])
-        DL = nat.ptr_array(keep[2])
-        out_rank = tuple(left_drm.rank)
-        om_shapes = [(out_rank[mu], right_rank[mu]) for mu in range(d - 1)]
-    else:
-        lt, DL, om_shapes = None, None, []
-        out_rank = right_rank
-    kr = (1,) + out_rank + (1,)
-    # every output of the call in ONE allocation (a dozen pool round trips cost the host more than the device idles for)
-    arrs = _carve([(kr[mu], tensor.shape[mu], kr[mu + 1]) for mu in range(d)] + om_shapes)
-    cores, Omega = arrs[:d], arrs[d:]
-    om = nat.ptr_array(Omega) if orth else None
-    try:
-        nat.call("ttsk_tt_orth_sketch", d, n, s, lt, rt, X, DL, DR, nat.ptr_array(cores), om, 0)
-    except nat.TtskUnsupported:
-        return None
-    return cores, Omega
-
-
-def try_orth_sketch_batch(tensors, left_drm, right_drm, method):
-    """``try_orth_sketch`` for tensor trains of ONE signature through ``ttsk_tt_orth_sketch_batch`` (the sketches run as
-    concurrent chains on the library's streams): a list of (cores, Omega) per tensor and an int32 device array of verdicts
-    (1 = repeat that tensor on the robust path), or None if the batch path does not apply."""
-    from .sketch_dispatch import SketchMethod
+def _orth_block(tensors, left_drm, right_drm, method):
+    """The argument block ``ttsk_tt_orth_sketch`` and ``ttsk_tt_orth_sketch_batch`` share, for ``B = len(tensors)`` tensor
+    trains of ONE signature: ``(args, outs, keep)`` with ``args`` the entry's arguments from ``d`` to the Omega pointers,
+    ``outs`` the (cores, Omega) arrays per tensor -- every output of the call in ONE allocation (a dozen pool round trips
+    cost the host more than the device idles for) -- and ``keep`` the operands that must outlive the call.  None if the
+    one-call paths do not apply."""
     if method not in (SketchMethod.orthogonal, SketchMethod.hmt) or not tensors:
         return None
-    if any(type(t) is not TensorTrain for t in tensors):
-        return None
     first = tensors[0]
-    if any(tuple(t.shape) != tuple(first.shape) or tuple(t.rank) != tuple(first.rank) for t in tensors):
-        return None
+    for t in tensors:
+        if type(t) is not TensorTrain or tuple(t.shape) != tuple(first.shape) or tuple(t.rank) != tuple(first.rank):
+            return None
     orth = method == SketchMethod.orthogonal
-    if type(right_drm) is not TensorTrainDRM or not right_drm.transpose:
+    # (a rank slice of a blocked sketch: the general path)
+    if not drm_pair(first.shape, left_drm, right_drm, need_left=orth, sliced_ok=False, mismatch_raises=False):
         return None
-    if orth and (type(left_drm) is not TensorTrainDRM or left_drm.transpose):
-        return None
-    d = len(first.shape)
-    drms = [right_drm] + ([left_drm] if orth else [])
-    if d < 2 or any(len(m.cores) != d - 1 or tuple(m.shape) != tuple(first.shape) for m in drms):
-        return None
-    if any(tuple(m.rank_min) != (0,) * (d - 1) or tuple(m.rank_max) != tuple(m.true_rank) for m in drms):
-        return None
-    B = len(tensors)
+    B, d = len(tensors), len(first.shape)
     arr = nat.i64_array
     n, s = arr(first.shape), arr((1,) + tuple(first.rank) + (1,))
     rt = arr((1,) + tuple(right_drm.true_rank))
@@ -244,9 +175,35 @@ def try_orth_sketch_batch(tensors, left_drm, right_drm, method):
     outs = [(arrs[b * len(per):b * len(per) + d], arrs[b * len(per) + d:(b + 1) * len(per)]) for b in range(B)]
     cores = nat.ptr_array([c for o in outs for c in o[0]])
     om = nat.ptr_array([c for o in outs for c in o[1]]) if orth else None
-    status = DevArray.zeros(((B + 1) // 2,), dtype=np.int64)         # B int32 verdicts
+    return (d, n, s, lt, rt, X, DL, DR, cores, om), outs, keep
+
+
+def try_orth_sketch(tensor, left_drm, right_drm, method) -> Optional[Tuple[list, list]]:
+    """``orthogonal`` / ``hmt`` sketch of ONE tensor train with tensor-train DRMs through ``ttsk_tt_orth_sketch``:
+    (cores, Omega) as device arrays, or None if the one-call path does not apply.  The verdicts of its fast
+    factorisations are deferred -- the caller reads ``ttsk_deferred_status`` (reference sketch_dispatch.py:160-193)."""
+    block = _orth_block([tensor], left_drm, right_drm, method)
+    if block is None:
+        return None
+    args, outs, keep = block
     try:
-        nat.call("ttsk_tt_orth_sketch_batch", B, d, n, s, lt, rt, X, DL, DR, cores, om, status, 0)
+        nat.call("ttsk_tt_orth_sketch", *args, 0)
+    except nat.TtskUnsupported:
+        return None
+    return outs[0]
+
+
+def try_orth_sketch_batch(tensors, left_drm, right_drm, method):
+    """``try_orth_sketch`` for tensor trains of ONE signature through ``ttsk_tt_orth_sketch_batch`` (the sketches run as
+    concurrent chains on the library's streams): a list of (cores, Omega) per tensor and an int32 device array of verdicts
+    (1 = repeat that tensor on the robust path), or None if the batch path does not apply."""
+    block = _orth_block(tensors, left_drm, right_drm, method)
+    if block is None:
+        return None
+    args, outs, keep = block
+    status = DevArray.zeros(((len(tensors) + 1) // 2,), dtype=np.int64)         # B int32 verdicts
+    try:
+        nat.call("ttsk_tt_orth_sketch_batch", len(tensors), *args, status, 0)
     except nat.TtskUnsupported:
         return None
     return outs, status
