@@ -442,9 +442,10 @@ int ttsk_qr_thin(double *dev_A, int64_t m, int64_t n, int stream);
  * Psi_mat (m, r2) row-major, Omega (l, r2) -- or Omega == NULL: Q = qr_thin(Psi_mat), k = r2 (hmt_sketch).  Same Q as
  * ttsk_pinv + product + ttsk_qr_thin on their fast paths (normal equations, CholeskyQR2, LAPACK's column signs) for
  * ranks up to 256.  The acceptance tests of those factorisations are NOT waited for: a rejection (Omega rank deficient
- * or kappa > 300, Psi_mat Omega^+ with kappa > 1e6) sets the stream's deferred flag and leaves Q meaningless; the caller
- * reads the flag once when the whole sketch is queued (ttsk_deferred_status) and then repeats it through ttsk_pinv /
- * ttsk_qr_thin.  TTSK_ERR_UNSUPPORTED outside the fast path (ranks > 256, TTSK_FAST_SOLVES=0). */
+ * or the diagonal of its Cholesky factor spread by more than 3e4, that of Psi_mat Omega^+ by more than 1e6 -- the spread
+ * bounds kappa from below, a matrix with kappa ten times the gate usually still passes) sets the stream's deferred flag and
+ * leaves Q meaningless; the caller reads the flag once when the whole sketch is queued (ttsk_deferred_status) and then
+ * repeats it through ttsk_pinv / ttsk_qr_thin.  TTSK_ERR_UNSUPPORTED outside the fast path (ranks > 256). */
 int ttsk_orth_step(const double *dev_psi, int64_t m, int64_t r2, const double *dev_omega, int64_t l, double *dev_q,
                    int stream);
 /* The same in two pieces for orthogonal_sketch, whose d - 1 Omega are all known before its sequential loop over the modes
@@ -468,7 +469,7 @@ int ttsk_deferred_status(int stream, int *host_flag);
  *   cores_out[d]  core mu (k_{mu-1}, n[mu], k_mu) with k_mu = lt[mu+1] (orthogonal) or rt[d-1-mu] (hmt), k_{-1} = k_{d-1} = 1
  *   omega_out     orthogonal: d - 1 matrices (lt[mu+1], rt[d-1-mu])
  * Verdicts deferred as in ttsk_orth_step (ttsk_deferred_status on `stream` afterwards).  TTSK_ERR_UNSUPPORTED: ranks
- * beyond 256, k_{mu-1} n[mu] < k_mu, TTSK_FAST_SOLVES=0.  (Omega of one shape with min(l, r) <= 128: the pseudo-inverses
+ * beyond 256, k_{mu-1} n[mu] < k_mu.  (Omega of one shape with min(l, r) <= 128: the pseudo-inverses
  * are batched launches; the sign reconstruction runs on stream + 1 and is joined back.) */
 int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t *lt, const int64_t *rt,
                         const double *const *X, const double *const *DL, const double *const *DR,

@@ -180,7 +180,14 @@ __global__ __launch_bounds__(1024) void jacobi_pinv_kernel(const double *__restr
     const double tol = fmax(4.0, sqrt((double)mW)) * DBL_EPSILON, tol2 = tol * tol;
     const int nm1 = np - 1;
     const int itc = rows <= 64 ? 4 : (rows <= 128 ? 8 : 0);   // mW >= nW
+    // Pseudo-inverse mode ends with ONE closing sweep that rotates every pair (tolerance 0).  The sweeps stop with cosines of up
+    // to tol left between the columns, and the sigma^-2 weights below turn a cosine c between a large and a small singular
+    // direction into a relative error c kappa of the result: 11 kappa eps at 150 x 128, 17 kappa eps at 200 x 64 (kappa = 3000;
+    // 37 and 11 times gelsd's error, tests/test_gpu_solve_edges.py).  Jacobi converges quadratically, so one more sweep takes the
+    // cosines from tol to rounding level: 5 and 3 kappa eps, for one sweep in about ten.
+    bool closing = false;
     for (int sweep = 0; sweep < 60; ++sweep) {
+        const double swtol2 = closing ? 0.0 : tol2;
         if (tid == 0) { s_rot = 0; s_smax = 0.0; }
         __syncthreads();
         // largest column norm^2 of this sweep (fixed reduction order: per-column sums, then one thread)
@@ -215,9 +222,9 @@ __global__ __launch_bounds__(1024) void jacobi_pinv_kernel(const double *__restr
                 double *wp = Wc + (size_t)p * mW, *wq = Wc + (size_t)q * mW;
                 double *vp = V + (size_t)p * nW, *vq = V + (size_t)q * nW;
                 if (precond) {
-                    if (itc == 4) jac_pair<4, false>(wp, wq, vp, vq, rows, nW, gl, tol2, tiny2, &s_rot);
-                    else if (itc == 8) jac_pair<8, false>(wp, wq, vp, vq, rows, nW, gl, tol2, tiny2, &s_rot);
-                    else jac_pair<0, false>(wp, wq, vp, vq, rows, nW, gl, tol2, tiny2, &s_rot);
+                    if (itc == 4) jac_pair<4, false>(wp, wq, vp, vq, rows, nW, gl, swtol2, tiny2, &s_rot);
+                    else if (itc == 8) jac_pair<8, false>(wp, wq, vp, vq, rows, nW, gl, swtol2, tiny2, &s_rot);
+                    else jac_pair<0, false>(wp, wq, vp, vq, rows, nW, gl, swtol2, tiny2, &s_rot);
                 } else if (itc == 4) jac_pair<4>(wp, wq, vp, vq, mW, nW, gl, tol2, tiny2, &s_rot);
                 else if (itc == 8) jac_pair<8>(wp, wq, vp, vq, mW, nW, gl, tol2, tiny2, &s_rot);
                 else jac_pair<0>(wp, wq, vp, vq, mW, nW, gl, tol2, tiny2, &s_rot);
@@ -226,7 +233,11 @@ __global__ __launch_bounds__(1024) void jacobi_pinv_kernel(const double *__restr
         }
         const int rot = s_rot;
         __syncthreads();
-        if (!rot) break;
+        if (closing) break;
+        if (!rot) {
+            if (!precond) break;
+            closing = true;
+        }
     }
     if (precond) {
         // V_j = column j of the converged R^T V' over its norm (zero for a column that vanished), then W V from the input

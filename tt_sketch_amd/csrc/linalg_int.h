@@ -11,8 +11,8 @@ namespace ttsk {
 constexpr int CHOL_MAX_N = 256;                       // largest n of a Cholesky factorisation (two blocks beyond CHOL_ONE_N)
 constexpr int CHOL_ONE_N = 128;                       // largest n of one workgroup's factorisation and sign reconstruction in LDS
 constexpr int QR_BATCH_MAX = 16;                      // matrices per launch of the batched QR, sign and apply-signs kernels
-constexpr double CHOL_GATE = 1.0 / 300.0;             // diag(R) spread the plain normal equations accept (kappa(Omega) <= 300)
-constexpr double CHOL_GATE_REFINED = 1.0 / 3.0e4;     // ... with a Newton-Schulz step behind them (kappa(Omega) <= 3e4)
+constexpr double CHOL_GATE = 1.0 / 300.0;             // diag(R) spread the plain normal equations accept: 1 / spread <= kappa(Omega), often by ten
+constexpr double CHOL_GATE_REFINED = 1.0 / 3.0e4;     // ... with a Newton-Schulz step behind them
 constexpr double PINV_FAST_RCOND = 1e-4;              // truncation rcond beyond which the normal equations do not apply
 
 int *deferred_flag(int stream);          // the stream's sticky rejection word (ttsk_deferred_status reads and clears it)
