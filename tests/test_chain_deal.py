@@ -1,6 +1,6 @@
 """The host-side deal of the fused chain step's work over a workgroup's waves (csrc/chain_deal.h, plain C++): a few
-lines of driver compiled with the host compiler print the table, and the table is checked here -- before any kernel
-reads it."""
+lines of driver compiled with the host compiler print the table -- for the tile structures and the k-blocks the plan
+(csrc/chain_plan.h) itself derives from the ranks -- and the table is checked here, before any kernel reads it."""
 import os
 import shutil
 import subprocess
@@ -13,12 +13,16 @@ CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
 DRIVER = r"""
 #include <cstdio>
 #include <cstdlib>
-#include "chain_deal.h"
+#include "chain_plan.h"
 int main(int argc, char **argv)
 {
-    if (argc != 9) return 2;
-    int v[8];
-    for (int i = 0; i < 8; ++i) v[i] = atoi(argv[i + 1]);
+    if (argc != 5) return 2;
+    int v[8], unr;
+    for (int i = 0; i < 3; ++i) v[i] = atoi(argv[i + 1]);           // J, A, A2; then K1
+    ttsk::chain_tile_split(v[1], v[3], v[4]);
+    ttsk::chain_tile_split(v[2], v[5], v[6]);
+    ttsk::chain_phase_a_runs(atoi(argv[4]), unr, v[7]);
+    printf("split %d %d %d %d %d\n", v[3], v[4], v[5], v[6], v[7]);
     const ttsk::ChainDeal d = ttsk::chain_deal(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
     printf("waves %d pieces %d useful %.6f cap %.6f simd %lld %lld %lld %lld h %d\n", d.waves, d.npieces, d.useful, d.cap(),
            d.simd[0], d.simd[1], d.simd[2], d.simd[3], ttsk::cd_cut(v[3]));
@@ -42,25 +46,6 @@ PARITY_SHAPES = [
 JS = (4, 16, 17, 96, 100, 112)
 
 
-def tile_split(r):
-    """chain_fused.hip: rank -> full 16-wide tiles + 4-wide strips (a remainder of 9..15 is a zero-padded full tile)"""
-    nf, rem = divmod(r, 16)
-    if rem == 0:
-        return nf, 0
-    if rem <= 4:
-        return nf, 1
-    if rem <= 8:
-        return nf, 2
-    return nf + 1, 0
-
-
-def kblocks(K1):
-    """chain_fused.hip: k-blocks of phase A, padded to whole runs of 25 or of 5"""
-    kb = (K1 + 3) // 4
-    pad25, pad5 = (kb + 24) // 25 * 25, (kb + 4) // 5 * 5
-    return pad25 if pad25 <= pad5 + 1 else pad5
-
-
 @pytest.fixture(scope="module")
 def deal(tmp_path_factory):
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
@@ -69,16 +54,16 @@ def deal(tmp_path_factory):
     d = tmp_path_factory.mktemp("chain_deal")
     src, exe = d / "driver.cpp", d / "driver"
     src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-o", str(exe), str(src)])
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
 
     def run(J, A, A2, K1):
-        (nqf, strq), (nnf, strn) = tile_split(A), tile_split(A2)
-        out = subprocess.run([str(exe)] + [str(x) for x in (J, A, A2, nqf, strq, nnf, strn, kblocks(K1))], check=True,
-                             capture_output=True, text=True).stdout.splitlines()
-        h = out[0].split()
+        out = subprocess.run([str(exe)] + [str(x) for x in (J, A, A2, K1)], check=True, capture_output=True,
+                             text=True).stdout.splitlines()
+        nqf, strq, nnf, strn, kb1 = (int(x) for x in out[0].split()[1:])
+        h = out[1].split()
         head = dict(waves=int(h[1]), npieces=int(h[3]), useful=float(h[5]), cap=float(h[7]), simd=[int(x) for x in h[9:13]],
-                    h=int(h[14]), nqf=nqf, strq=strq, nnf=nnf, strn=strn, kb1=kblocks(K1))
-        pieces = [dict(zip(("tile", "q0", "nq", "kind", "slot", "cycles"), map(int, l.split()[1:]))) for l in out[1:]]
+                    h=int(h[14]), nqf=nqf, strq=strq, nnf=nnf, strn=strn, kb1=kb1)
+        pieces = [dict(zip(("tile", "q0", "nq", "kind", "slot", "cycles"), map(int, l.split()[1:]))) for l in out[2:]]
         assert len(pieces) == head["npieces"]
         return head, pieces
     return run

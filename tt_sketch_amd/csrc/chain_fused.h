@@ -26,34 +26,10 @@
 // Partial tiles (rank 100 = 6 x 16 + 4, rank 50 = 3 x 16 + 2) are 4-wide strips computed with
 // v_mfma_f64_4x4x4 (4 blocks): 16 instead of 64 cycles of the matrix pipe.
 #pragma once
-#include "chain_deal.h"
+#include "chain_plan.h"
 #include "skinny.h"
 
 namespace ttsk {
-
-struct ChainStep {
-    const double *W[SK_MAXB];
-    const double *X[SK_MAXB];
-    double *T[SK_MAXB];          // WT: T[a][k][j] (A x n x J contiguous)
-    const double *E;
-    double *slab;                // [problem][workgroup of the problem][J][A2]
-    int nb, wpp, n;              // problems, workgroups per problem, slices (mode size)
-    int K1, A, A2, J;
-    int64_t w_c;                 // row stride of W (elements); columns contiguous
-    int64_t x_j, x_k, x_c;       // element strides of X
-    int64_t x_extent, t_extent;  // elements addressable from the bases
-    int AP, A2P;                 // padded extents of the two LDS images
-    int ebase;                   // offset (doubles) of the E image in LDS
-    int eunits;                  // 16-byte units of the E image the loader fills (multiple of 64)
-    int xcd_map;                 // 1: workgroups of the same slice range share an XCD (E_k from one L2)
-    unsigned int piece[CD_WAVES];// levelled workgroups (12 waves): wave w runs row tile | first Q << 8 | kind << 16 (chain_deal.h);
-                                 // kind CD_NONE: a loader, its index among the nload loaders << 8
-    int nload;
-    int diag;                    // timing experiments (TTSK_CF_DIAG): 1 = no X loads, 2 = no E loads, 4 = no barriers; results are then wrong
-    long long *stamps;           // diagnostics (TTSK_CF_STAMPS): s_memtime of workgroup 0, [slice][wave of CD_WAVES][8]
-};
-
-constexpr int CF_MAX_DMA = 160;  // loader instructions per slice (1 KB each)
 
 __device__ __forceinline__ void cf_barrier()
 {
@@ -532,16 +508,6 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 * OCC : 1) void chain_step_k
 }
 
 // 1 = launched (the slab reduce included), 0 = shape not covered, < 0 = error
-struct ChainStepArgs {
-    int nb, n, K1, A, A2, J;
-    const double *const *W;      // nb carried matrices (K1 x A), row stride w_c
-    int64_t w_c;
-    const double *const *X;      // nb cores
-    int64_t x_j, x_k, x_c, x_extent;
-    const double *E;             // (A, n, A2) contiguous
-    double *const *T;            // nullptr, or nb buffers (A, n, J) contiguous
-    double *const *Out;          // nb results (J x A2) contiguous
-};
 int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force = false);
 
 }  // namespace ttsk

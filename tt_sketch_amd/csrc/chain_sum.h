@@ -30,66 +30,11 @@ __device__ __forceinline__ void st8s(__amdgpu_buffer_rsrc_t r, uint32_t voff, ui
     __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<v2i_t *>(&v), r, (int)voff, (int)soff, 0);
 }
 
-constexpr int CS_NAMAX = 4;       // a-tiles of T a wave computes in phase A (W fragments in registers)
-constexpr int CS_SRMAX = 6;       // row tiles of the strip column (one wave owns all of them)
-constexpr int CS_NSMAX = 2;       // 4-wide strips behind the full column tiles
-constexpr int CS_DMAMAX = 13;     // E loader instructions per wave and slice (1 KB each)
-
-struct ChainSumRole {
-    unsigned char term, at0, na;  // phase A: local term, first a-tile, a-tiles (0 = none)
-    unsigned char body;           // phase-B body: 16 * RT + CT for a rectangle of full tiles, 128 + 16 * SR + NS for the strip column
-    unsigned char rt0, ct0;       // origin of the rectangle of full tiles
-    unsigned char pad0, pad1;
-};
-
-// everything but the pointer tables: what a wave's body reads (no dynamically indexed member -- the kernel picks the
-// wave's pointers and role from the tables itself, straight from the kernel-argument segment; handed to the body as one
-// struct WITH the tables the compiler copies all of it to scratch)
-struct ChainSumS {
-    const double *E;
-    double *T;                    // nullptr, or T[b * t_b + (a * n + k) * t_ld + j]
-    double *slab;                 // [term][slice range][J][A2]
-    int nb, n, K1, A, A2, J;
-    int tpw, ngroups, nranges;
-    int64_t w_c, x_j, x_k, x_c, x_extent;
-    int64_t t_b, t_ld, t_extent;
-    int RP;                       // row pitch of the T image (>= 16 row tiles; 2 mod 4: the stores of phase A then meet 2-way instead of 4-way bank conflicts)
-    int KB2;                      // k-blocks of phase B = ceil(A / 4)
-    int A2P;                      // row length of the E image (even, >= 16 NNF + 4 NS)
-    int NNF, NS;                  // full column tiles of Out, 4-wide strips behind them
-    int ebase, gbase;             // LDS offsets (doubles) of the E and G images; the T image sits at 0
-    int eunits;                   // 16-byte units of the E image (multiple of 64)
-    int xcd_map;                  // 1: the term groups of a slice range share an XCD (E_k from one L2)
-    int c_fast;                   // G loader: 1 = c is the contiguous index of X (right chain), 0 = j
-    // What the set-up would otherwise derive with divisions and 64-bit products: it runs once per workgroup, on a cold
-    // instruction cache, with nothing else resident on the CU -- its length in INSTRUCTIONS is what it costs (1640 of
-    // them took 13 k cycles of a 110 k-cycle launch).
-    int kbase, krem;              // slice range rr = [rr kbase + min(rr, krem), + kbase + (rr < krem))
-    int inv_ng;                   // (1 << 20) / ngroups + 1: i / ngroups == (i * inv_ng) >> 20 for i * ngroups < 2^20
-    int wpt, per, gu;             // G loader: waves per term (8 / tpw), elements per wave, loads per lane and slice
-    uint32_t w_c8, x_j8, x_c8;    // byte strides as 32-bit numbers (the host checks that every offset fits)
-    uint32_t t_b8, t_a8;          // T: bytes per term, bytes per row a (n t_ld 8)
-    uint32_t slab_t8, slab_r8;    // slab: bytes per term (nranges J A2 8) and per slice range (J A2 8)
-    uint32_t e_inv;               // ceil(2^32 / A2P): unit U of the E image is in section (U e_inv) >> 32
-#ifdef TTSK_LAB                    // timing experiments: only in a lab build (-DTTSK_LAB), never in the shipped code object
-    long long *stamps;            // s_memtime of workgroup 0, [slice][wave][8]
-    int diag;                     // (results wrong) 1 no E DMA, 2 no phase A, 4 no phase B, 8 no G loads, 16 no barriers, 32 no fragment reads in
-                                  // phase B, 64 no priorities, 128 no small rectangles
-#endif
-};
-
 #ifdef TTSK_LAB
 #define CS_DIAG(bit) (a.diag & (bit))
 #else
 #define CS_DIAG(bit) 0
 #endif
-
-struct ChainSum {
-    ChainSumS s;
-    const double *W[SK_MAXB];
-    const double *X[SK_MAXB];
-    ChainSumRole role[8];
-};
 
 // What a wave sets up once, before the slice loop -- the same code for every role, so it sits in the kernel in front of
 // the switch over the phase-B bodies: eight waves share one pass through the instruction cache (inside the bodies the
@@ -550,9 +495,6 @@ __device__ __forceinline__ void cs_wave(const ChainSumS &a, const ChainSumRole r
 }
 
 // the phase-B bodies a kernel instantiates (the host's wave table deals only these)
-#define CS_RECT_BODIES(X) X(1, 1) X(1, 2) X(1, 3) X(2, 1) X(2, 2) X(2, 3) X(3, 1) X(3, 2) X(4, 1) X(5, 1)
-#define CS_STRIP_BODIES(X) X(1, 1) X(2, 1) X(3, 1) X(4, 1) X(5, 1) X(6, 1) X(1, 2) X(2, 2) X(3, 2) X(4, 2) X(5, 2) X(6, 2)
-
 // JS: 4-row strips per term (J <= 4 JS), KB1: k-blocks of phase A (K1 <= 4 KB1), NA: a-tiles per wave in phase A,
 // WT: T is also written to memory
 template <int JS, int KB1, int NA, bool WT>
@@ -612,13 +554,7 @@ __global__ __launch_bounds__(512, 2) void chain_sum_kernel(ChainSum a)
 #endif
 }
 
-// 1 = launched (the slab reduce included), 0 = shape not covered, < 0 = error.  T of the base arguments is ignored:
-// the intermediate goes to Tint[b * t_b + (a * n + k) * t_ld + j] when Tint is given.
-struct ChainSumArgs {
-    ChainStepArgs s;
-    double *Tint;
-    int64_t t_b, t_ld, t_extent;
-};
+// 1 = launched (the slab reduce included), 0 = shape not covered, < 0 = error (the call: ChainSumArgs, chain_plan.h)
 int chain_sum_try(const ChainSumArgs &c, int stream, hipStream_t st, bool force = false);
 int launch_chain_sum_2(const ChainSum &a, bool wt, size_t lds, int grid, hipStream_t st);
 int launch_chain_sum_4(const ChainSum &a, bool wt, size_t lds, int grid, hipStream_t st);

@@ -26,31 +26,6 @@
 
 namespace ttsk {
 
-struct ChainWide {
-    const double *W[SK_MAXB];
-    const double *X[SK_MAXB];
-    double *T[SK_MAXB];          // WT: T[a][k][j] (A x n x J contiguous)
-    const double *E;
-    double *slab;                // [problem][unit = slice range x chunk][J][A2]
-    int nb, wpp, nac, n;         // problems, slice ranges per problem, chunks of A, slices (mode size)
-    int K1, A, A2, J;
-    int64_t w_c;                 // row stride of W (elements); columns contiguous
-    int64_t x_j, x_k, x_c;       // element strides of X
-    int64_t x_extent, t_extent;  // elements addressable from the bases
-    int ac;                      // columns of W / rows of E per chunk (<= 16 NQF + 4 STRQ)
-    int A2P;                     // A2 rounded up to even: 16-byte units per section of the E image
-    int ebase;                   // offset (doubles) of the E image in LDS
-    int eunits;                  // 16-byte units of one E image (multiple of 64)
-    int ebuf2;                   // 1: two E images (slice k in image k & 1)
-    int xcd_map;                 // 1: workgroups of one (slice range, chunk) share an XCD (E_k from one L2)
-    int loader;                  // the wave that only feeds E
-    signed char tile0[8], tile1[8];   // row tiles of each wave, -1 = none
-    // Few rows per tensor (J <= 64: the rank-20 terms of a sum): a workgroup serves `tpw` tensors at once -- one W image
-    // each (`wimg` doubles apart), wave w works for tensor slot[w] of the group -- and they share every E_k it loads.
-    int tpw, wimg;
-    signed char slot[8];
-};
-
 // One compute wave: MT row tiles (t[0], t[1]).
 template <int NQF, int STRQ, int NNF, int STRN, bool WT, int UNR, int MT>
 __device__ __forceinline__ void cw_compute(const ChainWide &a, const double *Wl, const double *El, const int prob, const int unit,

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <utility>
+#include "plan_common.h"
 #include "ttsk.h"
 
 namespace ttsk {
@@ -90,8 +91,6 @@ int rows_longk_try(const double *S, int64_t rows, int64_t s_row, const double *B
 
 // svd_grid.hip: one-sided Jacobi SVD over all compute units (n beyond the one-workgroup kernel)
 int svd_jacobi_grid(const double *A, int64_t m, int64_t n, double *US, double *S, double *Vt, int stream, hipStream_t st);
-
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // The one place a ttsk_gemm_desc is filled: one problem (batch = 1), C[m, n] (strides c_m, c_n) (+)= alpha sum_{ko, ki}
 // A[m, ko, ki] B[ko, ki, n] with the element strides given ...

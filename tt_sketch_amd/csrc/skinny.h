@@ -18,8 +18,6 @@
 
 namespace ttsk {
 
-constexpr int SK_MAXB = 32;  // problems of one shape per launch (one tensor of a batch each)
-
 #ifndef TTSK_S_M16
 #define TTSK_S_M16 1
 #endif
