@@ -31,11 +31,6 @@
 
 namespace ttsk {
 
-__device__ __forceinline__ void cf_barrier()
-{
-    // LDS traffic of this wave is complete, nothing moves across; vector-memory loads stay in flight
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 // Timing experiments (TTSK_CF_DIAG / TTSK_CF_STAMPS) exist in a lab build only (-DTTSK_LAB): the shipped code object carries
 // neither the run-time switches nor the stamp stores in its hot loop.
 #ifdef TTSK_LAB
@@ -45,7 +40,7 @@ __device__ __forceinline__ void cf_barrier()
 #define CF_DIAG(bit) 0
 #define CF_STAMP(i) do { } while (0)
 #endif
-#define CF_BARRIER() do { if (!CF_DIAG(4)) cf_barrier(); } while (0)
+#define CF_BARRIER() do { if (!CF_DIAG(4)) lds_barrier(); } while (0)
 
 // One piece of a row tile (chain_deal.h): rows 16 tile .. + 15, the NQF full tiles of a from tile q0 on and the STRQ
 // strips behind them -- both counts static, the origin a run-time offset into the two LDS images and into T.  KIND

@@ -360,7 +360,7 @@ __device__ __forceinline__ void cs_wave(const ChainSumS &a, const ChainSumRole r
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         CS_STAMP(2);
-        if (!(CS_DIAG(16))) cf_barrier();            // B1: T_k and E_k are in LDS, nobody reads the G image any more
+        if (!(CS_DIAG(16))) lds_barrier();            // B1: T_k and E_k are in LDS, nobody reads the G image any more
         CS_STAMP(3);
         if (k + 1 < k_end) {
             if constexpr (WT) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NST) : "memory");
@@ -455,7 +455,7 @@ __device__ __forceinline__ void cs_wave(const ChainSumS &a, const ChainSumRole r
         }
         if constexpr (SMALL) __builtin_amdgcn_s_setprio(0);
         CS_STAMP(4);
-        if (!(CS_DIAG(16))) cf_barrier();            // B2: the T and E images may be overwritten
+        if (!(CS_DIAG(16))) lds_barrier();            // B2: the T and E images may be overwritten
         CS_STAMP(5);
     }
 #undef CS_STAMP

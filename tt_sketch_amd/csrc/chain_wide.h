@@ -150,7 +150,7 @@ __device__ __forceinline__ void cw_compute(const ChainWide &a, const double *Wl,
                     st8(rt, (jok[m] && 16 * NQF + 4 * q + kq < cnt) ? tl + (uint32_t)((16 * NQF + 4 * q) * nJ * 8) : OOB_OFF, acc1s[m][q]);
             }
         }
-        cf_barrier();                                  // B1: E_k is in LDS
+        lds_barrier();                                  // B1: E_k is in LDS
         // ---- phase B: k-block kap = 4 p + t of T is register t of tile p
         {
             const double *eb = El + ((a.ebuf2 && (k & 1)) ? a.eunits * 2 : 0);
@@ -197,7 +197,7 @@ __device__ __forceinline__ void cw_compute(const ChainWide &a, const double *Wl,
                 }
             }
         }
-        cf_barrier();                                  // B2: El may be overwritten
+        lds_barrier();                                  // B2: El may be overwritten
     }
 
     // ---- partial result of this workgroup: slab[problem][unit][j][a']
@@ -310,16 +310,16 @@ __global__ __launch_bounds__(512, 2) void chain_wide_kernel(ChainWide a)
             if (k_beg < k_end) fill(k_beg);
             for (int k = k_beg; k < k_end; ++k) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                cf_barrier();                          // B1: E_k is in LDS
+                lds_barrier();                          // B1: E_k is in LDS
                 if (k + 1 < k_end) fill(k + 1);        // image (k + 1) & 1 was last read in phase B of slice k - 1
-                cf_barrier();                          // B2
+                lds_barrier();                          // B2
             }
         } else {
             for (int k = k_beg; k < k_end; ++k) {
                 fill(k);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                cf_barrier();                          // B1
-                cf_barrier();                          // B2: phase B of slice k is done, El may be overwritten
+                lds_barrier();                          // B1
+                lds_barrier();                          // B2: phase B of slice k is done, El may be overwritten
             }
         }
         return;

@@ -7,6 +7,7 @@
 #include <utility>
 #include "plan_common.h"
 #include "ttsk.h"
+#include "wave.h"
 
 namespace ttsk {
 
@@ -69,21 +70,9 @@ int launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, LaunchAt at, A
     return TTSK_ERR_HIP;
 }
 
-// Fragment reads of tiles p, p + 1 (256 bytes apart) must NOT be paired into ds_read2_b64: its 16-lane groups bank modulo
-// 32 dwords, and this layout's interleaved k-pairs (lane stride 16 bytes) then collide two by two -- 16 LDS cycles per pair of
-// fragments; two ds_read_b64 (32-lane halves, modulo 64 dwords) are conflict-free on it: 4 cycles (MI355X_MICROARCH.md, LDS
-// table).  A volatile access is what the compiler does not combine; the reads keep their place in the instruction stream, which
-// is where the look-ahead of the k-block loops wants them anyway.
-#define LDS_UNPAIRED(x) (*(const volatile __attribute__((address_space(3))) double *)(&(x)))
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-// v_mfma_f64_16x16x4_f64: A lane l holds A[m=l&15][k=l>>4], B lane l holds
-// B[k=l>>4][n=l&15]; D reg j of lane l is D[row=(l>>4)+4j][col=l&15].
-__device__ __forceinline__ v4d mfma16(double a, double b, v4d c)
-{
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
+// reduce.hip: out[j] (+)= sum_b part[b][j], b < nparts, j < W <= 4, by one workgroup in the stated order (wave.h); nparts = 0
+// writes zeros, or with `accumulate` leaves out as it is
+int sum_partials(const double *part, unsigned nparts, int W, double *out, int accumulate, LaunchAt at);
 
 // dense_right_pass.hip: C[m][n] (+)= alpha sum_k S[m][k] B[n][k], both rows contiguous along a long k, n <= 48: 1 = launched, 0 = not covered
 int rows_longk_try(const double *S, int64_t rows, int64_t s_row, const double *B, int N, int64_t b_row, int64_t K, double *C,

@@ -45,11 +45,6 @@ struct LeftPass {
     int xcd_map;
 };
 
-__device__ __forceinline__ double lp_mfma4(double a, double b, double c)
-{
-    return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
-}
-
 // STRIP: l > 16 (rows 16..19 as a 4-row strip)
 template <bool STRIP>
 __global__ __launch_bounds__(512, 2) void dense_left_pass_kernel(LeftPass a)
@@ -173,7 +168,7 @@ __global__ __launch_bounds__(512, 2) void dense_left_pass_kernel(LeftPass a)
         // are waited for with them, once per i1)
         if (kb + 1 < nkb) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        lds_barrier();
         if (kb + 2 < nkb) {
             x_fill(li1, li0, (J + 2) & 3);           // the images k-block kb - 2 was read from
             a_fill(li1, li0, (J + 2) & 3);
@@ -198,10 +193,10 @@ __global__ __launch_bounds__(512, 2) void dense_left_pass_kernel(LeftPass a)
 #pragma unroll
                 for (int s = 0; s < 3; ++s) {
                     acc[s][t] = mfma16(af[s], bf[t], acc[s][t]);
-                    if constexpr (STRIP) accs[s][t] = lp_mfma4(as[s], bf[t], accs[s][t]);
+                    if constexpr (STRIP) accs[s][t] = mfma4(as[s], bf[t], accs[s][t]);
                 }
                 acc[3][t] = mfma16(a3f, bf[t], acc[3][t]);
-                if constexpr (STRIP) accs[3][t] = lp_mfma4(a3s, bf[t], accs[3][t]);
+                if constexpr (STRIP) accs[3][t] = mfma4(a3s, bf[t], accs[3][t]);
             }
         }
         if ((kb + 1) % kpb == 0) z0_flush(kb / kpb);

@@ -49,11 +49,6 @@ __device__ __forceinline__ int64_t uniform_i64(int64_t v)
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
-__device__ __forceinline__ double mfma4s(double a, double b, double c)
-{
-    return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
-}
-
 // Timing experiments (TTSK_DP_DBG) exist in a lab build only (-DTTSK_LAB)
 #ifdef TTSK_LAB
 #define DP_DBG(bit) (a.dbg & (bit))
@@ -262,9 +257,9 @@ __global__ __launch_bounds__(512) void dense_pass_kernel(DensePass a)
 #pragma unroll
             for (int zt = 1; zt < ZT; ++zt) z[zt] = mfma16(cff[zt], xzf, z[zt]);
 #pragma unroll
-            for (int p = 0; p < SP; ++p) accs[bi][p] = mfma4s(xf, ps[p], accs[bi][p]);
+            for (int p = 0; p < SP; ++p) accs[bi][p] = mfma4(xf, ps[p], accs[bi][p]);
 #pragma unroll
-            for (int q = 0; q < ZS; ++q) zs[q] = mfma4s(csf[q], xzf, zs[q]);
+            for (int q = 0; q < ZS; ++q) zs[q] = mfma4(csf[q], xzf, zs[q]);
             xf = xf_n; xzf = xz_n;
 #pragma unroll
             for (int p = 0; p < TP; ++p) pf[p] = pf_n[p];
@@ -298,7 +293,8 @@ __global__ __launch_bounds__(512) void dense_pass_kernel(DensePass a)
         for (int zt = 0; zt < ZT; ++zt) zp[zt] = z[zt];
 #pragma unroll
         for (int q = 0; q < ZS; ++q) zps[q] = zs[q];
-        // the next tile has landed (and the stores are done); no fence: LDS traffic of this wave complete, then the barrier
+        // the next tile has landed (and the stores are done); no fence: LDS traffic of this wave complete, then the barrier.
+        // Not lds_barrier(): vmcnt(0) rides in the same s_waitcnt, a separate one in front would be one instruction more
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
     if (len > 0 && !(DP_DBG(2))) store_z(tile_of(len - 1));
@@ -333,10 +329,10 @@ __global__ __launch_bounds__(256) void dense_pass_reduce(const double *slab, int
         s += slab[id * per + f];
     }
     int p, t;
-    if (slot < 4 * TP) {                  // 16x16x4: register j of lane l is row (l >> 4) + 4 j, column l & 15
+    if (slot < 4 * TP) {                  // mfma16's accumulator layout (wave.h)
         p = 16 * (slot >> 2) + (l & 15);
         t = (l >> 4) + 4 * (slot & 3);
-    } else {                              // 4x4x4: lane (i = l >> 4, beta = (l >> 2) & 3, c = l & 3) is row 4 beta + i, column c
+    } else {                              // mfma4's (wave.h): i = l >> 4, beta = (l >> 2) & 3, j = l & 3
         p = 16 * TP + 4 * (slot - 4 * TP) + (l & 3);
         t = 4 * ((l >> 2) & 3) + (l >> 4);
     }

@@ -32,11 +32,6 @@ struct RightPass {
     int N, nrb, nkc;
 };
 
-__device__ __forceinline__ double rp_mfma4(double a, double b, double c)
-{
-    return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(512, 2) void rows_longk_kernel(RightPass a)
 {
     extern __shared__ double rp_img[];                                // [2][(64 + RP_BROWS) * 64]: 2 x 57 KB
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(512, 2) void rows_longk_kernel(RightPass a)
     for (int64_t st = s_beg; st < s_end; ++st) {
         const int buf = (int)((st - s_beg) & 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        lds_barrier();
         if (st + 1 < s_end) fill(st + 1, buf ^ 1);
         const double *I = rp_img + buf * IMG;
 #pragma unroll 4
@@ -108,7 +103,7 @@ __global__ __launch_bounds__(512, 2) void rows_longk_kernel(RightPass a)
             for (int q = 0; q < 2; ++q)
                 if (ct + 2 * q < ns) {
                     const double bs = I[rs[q] * 64 + 2 * (pair ^ (rs[q] & 31)) + lo];
-                    accs[q] = rp_mfma4(af, bs, accs[q]);
+                    accs[q] = mfma4(af, bs, accs[q]);
                 }
         }
     }

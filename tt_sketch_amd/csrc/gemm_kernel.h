@@ -30,15 +30,8 @@ struct KMap {
 };
 
 // --- fp64 matrix instruction ------------------------------------------------------------
-// Measured on MI355X (profiles/scripts/mfma_probe2.hip, mfma_mix.hip): both forms reach
-// the pipe rate -- 16x16x4 one instruction per 64 cycles and SIMD (77.7 TF/s at 2.4 GHz), 4x4x4 (4 blocks) one per
-// 16-17 cycles (75 TF/s), freely mixed.  (Round 1 read 49 vs 65 TF/s off a probe compiled with
-// __launch_bounds__(256): there hipcc keeps the accumulators in AGPRs and copies them around every
-// instruction.  The same happened to this kernel until it declared two waves per SIMD.)  The 4x4x4 form multiplies, for each of the four lane sub-groups beta
-// (lanes 16k + 4 beta + {0..3}), the 4x4 blocks A[4beta+i][k] (lane 4beta+i+16k) and
-// B[k][4beta+j] (lane 4beta+j+16k) into D[4beta+i][4beta+j] at lane 16i+4beta+j, i.e. the
-// diagonal 4x4 blocks of the 16x16 product of the SAME operand registers the 16x16x4 form
-// takes.  Rotating one operand by 4, 8, 12 lanes inside each row of 16 (DPP row_ror) and
+// mfma4 (wave.h, with its lane layout) gives the diagonal 4x4 blocks of the 16x16 product of the operand registers the
+// 16x16x4 form takes.  Rotating one operand by 4, 8, 12 lanes inside each row of 16 (DPP row_ror) and
 // issuing the instruction four times yields the full 16x16x4 product in 4 accumulators:
 //   acc[t] at lane L (i = L>>4, beta = (L>>2)&3, j = L&3)
 //     ROTB:  D[4 beta + i][4 ((beta+t)&3) + j]      ROTA:  D[4 ((beta+t)&3) + i][4 beta + j]
@@ -58,10 +51,6 @@ __device__ __forceinline__ void rot4(double v, double (&r)[4])
     r[1] = dpp_row<0x120 + 12>(v);
     r[2] = dpp_row<0x120 + 8>(v);
     r[3] = dpp_row<0x120 + 4>(v);
-}
-__device__ __forceinline__ double mfma4(double a, double b, double c)
-{
-    return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
 }
 
 // One operand tile: global -> registers -> LDS.  X = the non-contracted index (m or n).

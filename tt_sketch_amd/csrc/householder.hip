@@ -41,9 +41,10 @@ __global__ __launch_bounds__(256) void qr_tail_norm_kernel(const double *A, int6
     double acc = 0;
     for (int64_t i = r0 + threadIdx.x; i < r1; i += blockDim.x)
         if (i > j) { double x = A[i * n + j]; acc = fma(x, x, acc); }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
+    // left to right, unlike block_total; kept for bit-compatibility
     if (threadIdx.x == 0) tpart[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
@@ -97,9 +98,10 @@ __global__ __launch_bounds__(256) void qr_update_kernel(const double *A, double 
         }
     }
     if (next_tpart) {
-        for (int o = 32; o > 0; o >>= 1) nacc += __shfl_xor(nacc, o);
+        nacc = wave_sum(nacc);
         if (lane == 0) red[wave] = nacc;
         __syncthreads();
+        // left to right, unlike block_total; kept for bit-compatibility
         if (threadIdx.x == 0) next_tpart[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
     }
 }

@@ -271,7 +271,7 @@ __global__ __launch_bounds__(1024) void jacobi_pinv_kernel(const double *__restr
         double a = 0;
         const double *wj = Wc + (size_t)j * mW;
         for (int i = lane; i < mW; i += 64) a = fma(wj[i], wj[i], a);
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        a = wave_sum(a);
         if (lane == 0) s_inv2[j] = a;  // sigma^2
     }
     __syncthreads();

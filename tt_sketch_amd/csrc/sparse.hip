@@ -268,18 +268,15 @@ __global__ __launch_bounds__(256, 2) void sparse_psi_mfma_kernel(const double *_
     if (cur >= 0) flush(cur);
 }
 
-// out[t] += sum_w part[w][t]: one workgroup per output element, fixed summation order
+// out[t] += sum_w part[w][t]: one workgroup per output element; a thread sums w = tid, tid + 256, ..., then block_total
 __global__ __launch_bounds__(256) void sparse_part_reduce_kernel(const double *__restrict__ part, size_t nparts, int lr,
                                                                  double *__restrict__ out)
 {
     const int t = blockIdx.x;
-    double acc = 0.0;
-    for (size_t w = threadIdx.x; w < nparts; w += 256) acc += part[w * (size_t)lr + t];
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    __shared__ double ws[4];
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[t] += (ws[0] + ws[1]) + (ws[2] + ws[3]);
+    double acc[1] = {0.0};
+    for (size_t w = threadIdx.x; w < nparts; w += 256) acc[0] += part[w * (size_t)lr + t];
+    const double v = block_total(acc);
+    if (threadIdx.x == 0) out[t] += v;
 }
 
 __global__ void iota_kernel(int64_t *p, size_t n)

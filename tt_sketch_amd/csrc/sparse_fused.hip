@@ -54,7 +54,8 @@ __global__ __launch_bounds__(256) void sg_psi_reduce_kernel(const double *__rest
     }
 }
 
-// out[t] += sum_w part[w][t] in wave order
+// out[t] += sum_w part[w][t] in wave order.  A 256-wide LDS tree (128, 64, ..., 1), unlike block_total; kept for
+// bit-compatibility
 __global__ __launch_bounds__(256) void sg_om_reduce_kernel(const double *__restrict__ part, int waves, int cells, double *__restrict__ out)
 {
     const int t = blockIdx.x;

@@ -51,8 +51,6 @@ __device__ __forceinline__ uint64_t sg_flat(const SgF &f, uint64_t fl, uint64_t 
     return (f.src & 2) ? base + (uint64_t)(int64_t)j * f.mul : base;
 }
 
-__device__ __forceinline__ double sg_mfma4(double a, double b, double c) { return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0); }
-
 // ---- The accumulators of one product, in two forms with one interface.  Ops: a factor's operands of one k-block (the lane's
 // nonzero 4 b + kq, whose row is r); load (`one`: the ones factor), scaled, zero, mac, and store: the cells set to
 // dst[row * stride + col] where row < wa and col < wb.  No masks in load or mac: a column beyond a factor's width only reaches
@@ -142,11 +140,11 @@ template <int NS> struct SgEdge {
     {
         t = mfma16(A.t, B.t, t);
 #pragma unroll
-        for (int q = 0; q < NS; ++q) sb[q] = sg_mfma4(A.t, B.s[q], sb[q]);
+        for (int q = 0; q < NS; ++q) sb[q] = mfma4(A.t, B.s[q], sb[q]);
 #pragma unroll
-        for (int q = 0; q < NS; ++q) sa[q] = sg_mfma4(A.s[q], B.t, sa[q]);
+        for (int q = 0; q < NS; ++q) sa[q] = mfma4(A.s[q], B.t, sa[q]);
 #pragma unroll
-        for (int q = 0; q < NS; ++q) c[q] = sg_mfma4(A.s[q], B.b1, c[q]);
+        for (int q = 0; q < NS; ++q) c[q] = mfma4(A.s[q], B.b1, c[q]);
     }
     __device__ __forceinline__ void store(double *dst, int64_t stride, int wa, int wb, int x16, int kq) const
     {

@@ -56,13 +56,6 @@ __device__ __forceinline__ bool grid_sync(GridCtl *c, unsigned nblocks, int *s_o
     return *s_ok != 0;
 }
 
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-
 // One pair step by a wavefront.  IT > 0: columns of <= 64 IT rows stay in registers between the inner
 // products and the rotation.
 template <int IT>

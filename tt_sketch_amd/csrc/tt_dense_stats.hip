@@ -26,7 +26,7 @@
 // Order of the sums.  The grid is min(tiles rounded up to 8, 4096) workgroups, a function of M and N alone; workgroup b
 // walks the tiles (b % 8) (grid / 8) + b / 8 + i grid -- the workgroups of one XCD (b % 8) take neighbouring tiles,
 // row blocks fastest, so that they share the R chunk in their L2.  A lane sums its tiles in that order, the lanes of a
-// wave by a butterfly, the four waves and then the workgroups' quadruples by one workgroup in index order: no atomics,
+// wave and the four waves by block_total (wave.h), then the workgroups' quadruples by sum_partials (reduce.hip): no atomics,
 // the same bits on every call, with or without the output array.
 #include "common.h"
 #include "prof.h"
@@ -47,29 +47,6 @@ struct DenseStats {
     int64_t M, N, rho, ldx, ldo;                    // ldx / ldo: row strides of X / out (R and the tile grid use N)
     int64_t nrb, tiles;                             // row blocks, tiles = nrb x column tiles
 };
-
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// part[block][W]: the workgroup's sums, waves added in a fixed order
-template <int W>
-__device__ __forceinline__ void store_block_sums(double (&s)[W], double *__restrict__ part)
-{
-    __shared__ double ws[4][W];
-#pragma unroll
-    for (int j = 0; j < W; ++j)
-        for (int o = 32; o > 0; o >>= 1) s[j] += __shfl_xor(s[j], o);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int j = 0; j < W; ++j) ws[threadIdx.x >> 6][j] = s[j];
-    __syncthreads();
-    if (threadIdx.x < W) {
-        const int j = threadIdx.x;
-        part[(size_t)blockIdx.x * W + j] = (ws[0][j] + ws[1][j]) + (ws[2][j] + ws[3][j]);
-    }
-}
 
 __global__ __launch_bounds__(256, 2) void tt_dense_stats_kernel(DenseStats a)
 {
@@ -185,7 +162,10 @@ __global__ __launch_bounds__(256, 2) void tt_dense_stats_kernel(DenseStats a)
                 }
             }
     }
-    if (has_sums) store_block_sums<4>(s, a.part);
+    if (has_sums) {                                 // part[block][4]
+        const double v = block_total(s);
+        if (tid < 4) a.part[(size_t)blockIdx.x * 4 + tid] = v;
+    }
 }
 
 // part[block][0] = sum of squares of the workgroup's share (grid-stride, so the share depends on n alone)
@@ -193,27 +173,8 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const double *__restrict__ x
 {
     double s[1] = {0.0};
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) s[0] = fma(x[i], x[i], s[0]);
-    store_block_sums<1>(s, part);
-}
-
-// stats[j] (+)= sum_b part[b][j], j < W <= 4: one workgroup, fixed order (nparts = 0: zeros)
-__global__ __launch_bounds__(256) void dense_sums_reduce_kernel(const double *__restrict__ part, unsigned nparts, int W,
-                                                                double *__restrict__ stats, int accumulate)
-{
-    __shared__ double ws[4][4];
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (unsigned b = threadIdx.x; b < nparts; b += 256)
-        for (int j = 0; j < W; ++j) acc[j] += part[(size_t)b * W + j];
-    for (int o = 32; o > 0; o >>= 1)
-        for (int j = 0; j < 4; ++j) acc[j] += __shfl_xor(acc[j], o);
-    if ((threadIdx.x & 63) == 0)
-        for (int j = 0; j < 4; ++j) ws[threadIdx.x >> 6][j] = acc[j];
-    __syncthreads();
-    if ((int)threadIdx.x < W) {
-        const int j = threadIdx.x;
-        const double v = (ws[0][j] + ws[1][j]) + (ws[2][j] + ws[3][j]);
-        stats[j] = accumulate ? stats[j] + v : v;
-    }
+    const double v = block_total(s);
+    if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
 
 }  // namespace
@@ -256,7 +217,7 @@ int ttsk_tt_dense_stats_ld(const double *dev_L, int64_t M, const double *dev_R, 
     ProfBracket prof(st, PROF_EVAL, 2.0 * (double)rho * (double)M * (double)N, "tt_dense_stats_kernel");
     int rc = launch(tt_dense_stats_kernel, dim3(blocks), dim3(256), (size_t)DS_LDS_BYTES, st, a);
     if (rc == TTSK_OK && dev_stats)
-        rc = launch(dense_sums_reduce_kernel, dim3(1), dim3(256), 0, st, a.part, blocks, 4, dev_stats, accumulate);
+        rc = sum_partials(a.part, blocks, 4, dev_stats, accumulate, st);
     return rc;
 }
 
@@ -280,7 +241,7 @@ int ttsk_sumsq(const double *dev_x, size_t n, double *dev_out, int stream)
         ProfBracket prof(st, PROF_EVAL, 2.0 * (double)n, "sumsq_kernel");      // closed before the reduce below
         if (int rc = launch(sumsq_kernel, dim3(blocks), dim3(256), 0, st, dev_x, n, part)) return rc;
     }
-    return launch(dense_sums_reduce_kernel, dim3(1), dim3(256), 0, st, part, blocks, 1, dev_out, 0);
+    return sum_partials(part, blocks, 1, dev_out, 0, st);
 }
 
 }  // extern "C"

@@ -67,25 +67,11 @@ __device__ __forceinline__ void emit(double t, size_t e, bool own, size_t N, con
     }
 }
 
-// part[block][3]: the workgroup's sums, waves added in a fixed order
-__device__ __forceinline__ void store_block_stats(double s_xt, double s_tt, double s_rr, double *__restrict__ part)
+// part[block][3]: the workgroup's sums (block_total: the stated order)
+__device__ __forceinline__ void store_block_stats(double (&s)[3], double *__restrict__ part)
 {
-    __shared__ double ws[4][3];
-    for (int o = 32; o > 0; o >>= 1) {
-        s_xt += __shfl_xor(s_xt, o);
-        s_tt += __shfl_xor(s_tt, o);
-        s_rr += __shfl_xor(s_rr, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        ws[threadIdx.x >> 6][0] = s_xt;
-        ws[threadIdx.x >> 6][1] = s_tt;
-        ws[threadIdx.x >> 6][2] = s_rr;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int j = threadIdx.x;
-        part[(size_t)blockIdx.x * 3 + j] = (ws[0][j] + ws[1][j]) + (ws[2][j] + ws[3][j]);
-    }
+    const double v = block_total(s);
+    if (threadIdx.x < 3) part[(size_t)blockIdx.x * 3 + threadIdx.x] = v;
 }
 
 template <int G>
@@ -98,7 +84,7 @@ __global__ __launch_bounds__(256) void tt_gather_kernel(TTCores tc, GatherIdx ix
     double *const va = sm + (size_t)((wave * GPW + grp) * 2) * rv, *const vb = va + rv;
     const int d = ix.d;
     int *const sidx = (int *)(sm + (size_t)4 * GPW * 2 * rv) + wave * d * 64;
-    double s_xt = 0.0, s_tt = 0.0, s_rr = 0.0;
+    double sums[3] = {0.0, 0.0, 0.0};           // x.t, t.t, |t - x|^2
     const size_t tb = (size_t)GPW * S, nbatch = (N + tb - 1) / tb;      // S tuples per group and batch
     const bool own = lg < S;
     for (size_t bt = (size_t)blockIdx.x * 4 + wave; bt < nbatch; bt += (size_t)gridDim.x * 4) {
@@ -144,9 +130,9 @@ __global__ __launch_bounds__(256) void tt_gather_kernel(TTCores tc, GatherIdx ix
             if (lg == s) mine = p;
             wave_lds_sync();
         }
-        emit(mine, e_own, own, N, val, out, part != nullptr, s_xt, s_tt, s_rr);
+        emit(mine, e_own, own, N, val, out, part != nullptr, sums[0], sums[1], sums[2]);
     }
-    if (part) store_block_stats(s_xt, s_tt, s_rr, part);
+    if (part) store_block_stats(sums, part);
 }
 
 // t_e = sum_rho prod_k A_k[i_k(e), rho]: lane rho of the group (strided by G) forms the product over the modes
@@ -158,7 +144,7 @@ __global__ __launch_bounds__(256) void cp_gather_kernel(CPFactors cf, GatherIdx 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lg = lane & (G - 1), grp = lane / G;
     const int d = ix.d, R = cf.rank;
     int *const sidx = (int *)sm + wave * d * 64;
-    double s_xt = 0.0, s_tt = 0.0, s_rr = 0.0;
+    double sums[3] = {0.0, 0.0, 0.0};           // x.t, t.t, |t - x|^2
     const size_t tb = (size_t)(64 / G) * S, nbatch = (N + tb - 1) / tb;
     const bool own = lg < S;
     for (size_t bt = (size_t)blockIdx.x * 4 + wave; bt < nbatch; bt += (size_t)gridDim.x * 4) {
@@ -179,28 +165,9 @@ __global__ __launch_bounds__(256) void cp_gather_kernel(CPFactors cf, GatherIdx 
             for (int o = G / 2; o > 0; o >>= 1) p += __shfl_xor(p, o, G);
             if (lg == s) mine = p;
         }
-        emit(mine, e_own, own, N, val, out, part != nullptr, s_xt, s_tt, s_rr);
+        emit(mine, e_own, own, N, val, out, part != nullptr, sums[0], sums[1], sums[2]);
     }
-    if (part) store_block_stats(s_xt, s_tt, s_rr, part);
-}
-
-// stats[j] = sum_w part[w][j], one workgroup, fixed order (nparts = 0: zeros)
-__global__ __launch_bounds__(256) void gather_stats_sum_kernel(const double *__restrict__ part, unsigned nparts,
-                                                               double *__restrict__ stats)
-{
-    __shared__ double ws[4][3];
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (unsigned w = threadIdx.x; w < nparts; w += 256)
-        for (int j = 0; j < 3; ++j) acc[j] += part[(size_t)w * 3 + j];
-    for (int o = 32; o > 0; o >>= 1)
-        for (int j = 0; j < 3; ++j) acc[j] += __shfl_xor(acc[j], o);
-    if ((threadIdx.x & 63) == 0)
-        for (int j = 0; j < 3; ++j) ws[threadIdx.x >> 6][j] = acc[j];
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int j = threadIdx.x;
-        stats[j] = (ws[0][j] + ws[1][j]) + (ws[2][j] + ws[3][j]);
-    }
+    if (part) store_block_stats(sums, part);
 }
 
 // what both entries check and set up alike; TTSK_OK with `ix` filled
@@ -248,6 +215,21 @@ static unsigned gather_blocks(size_t N, int G, int S)
     return (unsigned)(b > GATHER_MAX_BLOCKS ? GATHER_MAX_BLOCKS : b);
 }
 
+// What both entries end in: room for the workgroups' partial sums in SCRATCH_MISC (only if statistics are wanted), the
+// gather kernel through `run(part)` (no launch for an empty list), the closing sum of the partials.
+template <typename Run>
+static int gather_run(unsigned blocks, double *dev_stats, int stream, hipStream_t st, Run &&run)
+{
+    double *part = nullptr;
+    if (dev_stats && blocks) {
+        part = (double *)scratch(stream, SCRATCH_MISC, (size_t)blocks * 3 * 8);
+        if (!part) return TTSK_ERR_HIP;
+    }
+    if (blocks)
+        if (int rc = run(part)) return rc;
+    return dev_stats ? sum_partials(part, blocks, 3, dev_stats, 0, st) : TTSK_OK;
+}
+
 }  // namespace ttsk
 
 using namespace ttsk;
@@ -283,19 +265,12 @@ int ttsk_tt_gather(const double *const *dev_cores, const int64_t *ranks, const i
     tc.rank[d] = 1;
     const int G = widest <= 16 ? 16 : widest <= 32 ? 32 : 64, S = gather_steps(N, G);
     const unsigned blocks = gather_blocks(N, G, S);
-    double *part = nullptr;
-    if (dev_stats && blocks) {
-        part = (double *)scratch(stream, SCRATCH_MISC, (size_t)blocks * 3 * 8);
-        if (!part) return TTSK_ERR_HIP;
-    }
-    if (blocks) {
-        const int rv = (int)widest;
-        const size_t lds = (size_t)4 * (64 / G) * 2 * rv * 8 + (size_t)4 * d * 64 * 4;
-        auto kern = G == 16 ? tt_gather_kernel<16> : G == 32 ? tt_gather_kernel<32> : tt_gather_kernel<64>;
-        if (int rc = launch(kern, dim3(blocks), dim3(256), lds, st, tc, ix, N, dev_val, dev_out, part, rv, S)) return rc;
-    }
-    if (dev_stats) return launch(gather_stats_sum_kernel, dim3(1), dim3(256), 0, st, part, blocks, dev_stats);
-    return TTSK_OK;
+    const int rv = (int)widest;
+    const size_t lds = (size_t)4 * (64 / G) * 2 * rv * 8 + (size_t)4 * d * 64 * 4;
+    auto kern = G == 16 ? tt_gather_kernel<16> : G == 32 ? tt_gather_kernel<32> : tt_gather_kernel<64>;
+    return gather_run(blocks, dev_stats, stream, st, [&](double *part) {
+        return launch(kern, dim3(blocks), dim3(256), lds, st, tc, ix, N, dev_val, dev_out, part, rv, S);
+    });
 }
 
 int ttsk_cp_gather(const double *const *dev_factors, int64_t rank, const int64_t *shape, int d, const int64_t *dev_idx,
@@ -316,18 +291,11 @@ int ttsk_cp_gather(const double *const *dev_factors, int64_t rank, const int64_t
     cf.rank = (int)rank;
     const int G = rank <= 16 ? 16 : rank <= 32 ? 32 : 64, S = gather_steps(N, G);
     const unsigned blocks = gather_blocks(N, G, S);
-    double *part = nullptr;
-    if (dev_stats && blocks) {
-        part = (double *)scratch(stream, SCRATCH_MISC, (size_t)blocks * 3 * 8);
-        if (!part) return TTSK_ERR_HIP;
-    }
-    if (blocks) {
-        const size_t lds = (size_t)4 * d * 64 * 4;
-        auto kern = G == 16 ? cp_gather_kernel<16> : G == 32 ? cp_gather_kernel<32> : cp_gather_kernel<64>;
-        if (int rc = launch(kern, dim3(blocks), dim3(256), lds, st, cf, ix, N, dev_val, dev_out, part, S)) return rc;
-    }
-    if (dev_stats) return launch(gather_stats_sum_kernel, dim3(1), dim3(256), 0, st, part, blocks, dev_stats);
-    return TTSK_OK;
+    const size_t lds = (size_t)4 * d * 64 * 4;
+    auto kern = G == 16 ? cp_gather_kernel<16> : G == 32 ? cp_gather_kernel<32> : cp_gather_kernel<64>;
+    return gather_run(blocks, dev_stats, stream, st, [&](double *part) {
+        return launch(kern, dim3(blocks), dim3(256), lds, st, cf, ix, N, dev_val, dev_out, part, S);
+    });
 }
 
 }  // extern "C"
