@@ -317,6 +317,24 @@ int ttsk_tt_gram(const double *const *dev_cores_a, const int64_t *ranks_a, int K
 int ttsk_op_apply(int K, const double *const *L, const double *const *M, const double *const *C, const int64_t *dims,
                   const int64_t *strides, int64_t l, double *W, int64_t w_cols, int stream);
 
+/* ---- entrywise (Hadamard) products of two tensor trains, never formed (csrc/hadamard_apply.hip, plan in
+ * csrc/hadamard_plan.h) ----
+ * One step of sketching x o y, whose core is P[(beta a), i, (beta' a')] = X[beta, i, beta'] Y[a, i, a'], without that core:
+ * with the chain so far L (R, r, l),
+ *   W[l, i, w_off + beta' r' + a'] = sum_beta X[beta, i, beta'] sum_a L[beta, a, l] Y[a, i, a'];
+ * the inner sum stays on the chip.  The chain step, Psi and Omega are one ttsk_gemm each on W.  One term per call.
+ *   L         contiguous (R, r, l)
+ *   X, Y      strided: (R, n, R') and (r, n, r')
+ *   dims      R, R', r, r', n, l
+ *   strides   in elements: X over (beta, i, beta'), then Y over (a, i, a')
+ *   W         contiguous (l, n, w_cols); the call writes the columns w_off .. w_off + R' r' and nothing else
+ * One workgroup forms each element in a fixed order, no atomics: the same bits on every call.  TTSK_ERR_ARG: a NULL
+ * pointer, an extent below 1, w_off < 0, w_off + R' r' > w_cols.  TTSK_ERR_UNSUPPORTED before anything is launched: an
+ * extent or the number of workgroups (n x ceil(l / 16) x ceil(r' / 16) x ceil(R' / 64)) of 2^31 or more.  Inside those
+ * bounds every shape runs. */
+int ttsk_hadamard_apply(const double *L, const double *X, const double *Y, const int64_t *dims, const int64_t *strides,
+                        double *W, int64_t w_cols, int64_t w_off, int stream);
+
 /* ---- CP tensors against tensor-train DRMs, no panels (csrc/cp_pass.hip, plan in csrc/cp_pass_plan.h) ----
  * A CP tensor of rank N has factor matrices V_mu (n x N).  The step of TensorTrainDRM.sketch_cp (tensor_train_drm.py:90-107)
  * and the Psi / Omega of cp_sketch.py:6-36 are one GEMM each whose Khatri-Rao operand is formed in registers; the N x n x

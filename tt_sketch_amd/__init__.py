@@ -6,6 +6,7 @@ Python host code with the reference's module layout and API (``sketch``, ``sketc
 There is no CPU fallback: compute entry points raise if the library or a GPU is missing.
 """
 from .drm import ALL_DRM, DenseGaussianDRM, SparseGaussianDRM, SparseSignDRM, TensorTrainDRM
+from .hadamard_product import HadamardProduct, hadamard_round
 from .operator_product import OperatorProduct
 from .sketch import (SketchedTensorTrain, assemble_sketched_tt, blocked_stream_sketch, hmt_sketch,
                      orthogonal_sketch, orthogonal_sketch_batch, hmt_sketch_batch, stream_sketch, stream_sketch_batch,
@@ -21,5 +22,5 @@ __all__ = [
     "SketchedTensorTrain", "assemble_sketched_tt", "blocked_stream_sketch", "hmt_sketch",
     "orthogonal_sketch", "orthogonal_sketch_batch", "hmt_sketch_batch", "stream_sketch", "stream_sketch_batch", "to_tt_batch", "SketchContainer", "SketchMethod", "general_sketch",
     "CPTensor", "DenseTensor", "SparseTensor", "Tensor", "TensorSum", "TensorTrain", "TuckerTensor",
-    "tt_svd", "tt_gram", "OperatorProduct",
+    "tt_svd", "tt_gram", "OperatorProduct", "HadamardProduct", "hadamard_round",
 ]

@@ -15,13 +15,13 @@ import numpy as np
 from .. import _native as nat
 from ..device import DevArray, as_dev, contract
 from ..drm_base import CanSlice, handle_transpose
-from ..sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchOperatorProduct,
-                                                  CansketchSparse, CansketchTT, CanSketchTucker)
+from ..sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchHadamardProduct,
+                                                  CansketchOperatorProduct, CansketchSparse, CansketchTT, CanSketchTucker)
 from ..utils import random_normal_dev_many
 
 
 class TensorTrainDRM(CansketchSparse, CansketchTT, CansketchCP, CanSlice, CansketchDense,
-                     CanSketchTucker, CansketchOperatorProduct):
+                     CanSketchTucker, CansketchOperatorProduct, CansketchHadamardProduct):
     cores: list
 
     def __init__(self, rank: Union[Tuple[int, ...], int], shape: Tuple[int, ...], transpose: bool,
@@ -92,6 +92,23 @@ class TensorTrainDRM(CansketchSparse, CansketchTT, CansketchCP, CanSlice, Canske
             Lm = contract("lic,lim->cm", W, self._core(mu))
             yield self._cut(mu, Lm)
             L = Lm.reshape(M.shape[3], C.shape[2], Lm.shape[1])
+
+    # ------------------------------------------------------------------ entrywise product of two trains
+    @handle_transpose
+    def sketch_hadamard_product(self, tensor):
+        """L_mu[(b' a'), m] = sum_{l,i} W_mu[l, i, (b' a')] D_mu[l, i, m] with W_mu = L_{mu-1} o (X_mu, Y_mu) from
+        ``hadamard_apply`` -- one ``ttsk_hadamard_apply`` call, or W composed from ``contract`` calls where its routing rule
+        has it: the Kronecker core of the product is never formed either way."""
+        from ..hadamard_product import hadamard_apply
+        from ..operator_product import chain_start
+        Xs, Ys = tensor.dev_parts()
+        L = chain_start()
+        for mu in range(len(self.shape) - 1):
+            X, Y = Xs[mu], Ys[mu]
+            W = hadamard_apply(L, X, Y)
+            Lm = contract("lic,lim->cm", W, self._core(mu))
+            yield self._cut(mu, Lm)
+            L = Lm.reshape(X.shape[2], Y.shape[2], Lm.shape[1])
 
     # ------------------------------------------------------------------ CP input
     @handle_transpose

@@ -17,17 +17,19 @@ from typing import Callable, List, Optional, Tuple
 import numpy as np
 
 from . import _native as nat
-from . import cp_fused, operator_fused, sparse_fused, tt_fused
+from . import cp_fused, hadamard_fused, operator_fused, sparse_fused, tt_fused
 from .device import DevArray, as_dev, axpby, contract
 from .drm import TensorTrainDRM
 from .drm_base import DRM
 from .sketch_container import SketchContainer
+from .hadamard_product import HadamardProduct
 from .operator_product import OperatorProduct
 from .paths import SketchMethod
-from .sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchOperatorProduct, CansketchSparse,
-                                                 CansketchTT, CanSketchTucker)
+from .sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchHadamardProduct,
+                                                 CansketchOperatorProduct, CansketchSparse, CansketchTT, CanSketchTucker)
 from .sketching_methods.cp_sketch import sketch_omega_cp, sketch_psi_cp
 from .sketching_methods.dense_sketch import sketch_omega_dense, sketch_psi_dense
+from .sketching_methods.hadamard_product_sketch import sketch_omega_hadamard_product, sketch_psi_hadamard_product
 from .sketching_methods.operator_product_sketch import sketch_omega_operator_product, sketch_psi_operator_product
 from .sketching_methods.sparse_sketch import sketch_omega_sparse, sketch_psi_sparse
 from .sketching_methods.tensor_train_sketch import sketch_omega_tt, sketch_psi_tt
@@ -39,18 +41,22 @@ from .utils import pinv_dev
 ABSTRACT_TENSOR_SKETCH_DISPATCH = {
     SparseTensor: CansketchSparse, TensorTrain: CansketchTT, DenseTensor: CansketchDense,
     CPTensor: CansketchCP, TuckerTensor: CanSketchTucker, OperatorProduct: CansketchOperatorProduct,
+    HadamardProduct: CansketchHadamardProduct,
 }
 DRM_SKETCH_METHOD_DISPATCH = {
     SparseTensor: "sketch_sparse", TensorTrain: "sketch_tt", DenseTensor: "sketch_dense",
     CPTensor: "sketch_cp", TuckerTensor: "sketch_tucker", OperatorProduct: "sketch_operator_product",
+    HadamardProduct: "sketch_hadamard_product",
 }
 OMEGA_METHODS = {
     SparseTensor: sketch_omega_sparse, TensorTrain: sketch_omega_tt, DenseTensor: sketch_omega_dense,
     CPTensor: sketch_omega_cp, TuckerTensor: sketch_omega_tucker, OperatorProduct: sketch_omega_operator_product,
+    HadamardProduct: sketch_omega_hadamard_product,
 }
 PSI_METHODS = {
     SparseTensor: sketch_psi_sparse, TensorTrain: sketch_psi_tt, DenseTensor: sketch_psi_dense,
     CPTensor: sketch_psi_cp, TuckerTensor: sketch_psi_tucker, OperatorProduct: sketch_psi_operator_product,
+    HadamardProduct: sketch_psi_hadamard_product,
 }
 
 
@@ -286,12 +292,14 @@ def _sketch_pass(tensor: Tensor, left_drm: Optional[DRM], right_drm: DRM, method
 # arrays (Psi, Omega), or None where it does not apply (what each accepts of a DRM pair: ``paths.drm_pair``).
 FUSED_PATHS = (tt_fused.try_stream_sketch, sparse_fused.try_sparse_gauss_sketch, operator_fused.try_operator_sketch,
                cp_fused.try_cp_sketch)
+# asked after those, in the same way: the paths added since tests/test_cp_pass_host.py fixed the four above and their order
+PRODUCT_PATHS = (hadamard_fused.try_hadamard_sketch,)
 
 
 def general_sketch(tensor: Tensor, left_drm: Optional[DRM], right_drm: DRM,
                    method: SketchMethod) -> SketchContainer:
     """Sketch on the device, result copied to a host ``SketchContainer``."""
-    for path in FUSED_PATHS:
+    for path in FUSED_PATHS + PRODUCT_PATHS:
         fused = path(tensor, left_drm, right_drm, method)
         if fused is not None:
             return SketchContainer(*fused)

@@ -20,6 +20,13 @@ class CansketchOperatorProduct(DRM, ABC):
         are never formed; rows in (operator rank, train rank) order."""
 
 
+class CansketchHadamardProduct(DRM, ABC):
+    @abstractmethod
+    def sketch_hadamard_product(self, tensor):
+        """yields (x.rank[mu] * y.rank[mu], drm.rank[mu]): DRM_mu^T contracted with the Kronecker cores 0..mu of the
+        entrywise product, which are never formed; rows in (rank of x, rank of y) order."""
+
+
 class CansketchSparse(DRM, ABC):
     @abstractmethod
     def sketch_sparse(self, tensor):

@@ -800,6 +800,12 @@ class TensorTrain(_GatherOnDevice, Tensor):
 
     __rmul__ = __mul__
 
+    def hadamard(self, other: "TensorTrain"):
+        """The entrywise product ``self o other`` as a tensor that keeps its two factors (``HadamardProduct``, ``self``
+        the outer one): the sketches take it without forming its Kronecker cores."""
+        from .hadamard_product import HadamardProduct
+        return HadamardProduct(self, other)
+
     @property
     def size(self) -> int:
         return int(sum(c.size for c in self.cores))

@@ -22,6 +22,7 @@ import numpy.typing as npt
 import scipy.linalg
 
 from .device import DevArray, as_dev, axpby, contract
+from .hadamard_product import HadamardProduct
 from .operator_product import OperatorProduct
 from .sketch import orthogonal_sketch, stream_sketch
 from .tensor import Tensor, TensorSum, TensorTrain, _host, tt_gram
@@ -221,9 +222,10 @@ def round_tt_sum(tt_sum: TensorSum, max_rank: TTRank, eps: Optional[float] = Non
     sum then TT-SVD, ``"pairwise"`` = add and round term by term, ``"sketch"`` = streaming sketch
     with right rank ``ceil(oversample_factor * left)``, ``"orth_sketch"`` = orthogonal sketch,
     ``None`` = no rounding.  The two SVD variants run ``add`` / ``round_dev`` on the device.  Only the two sketches take
-    an ``OperatorProduct`` term as it is; the other methods form it first."""
-    if method in ("exact", "pairwise", None) and any(isinstance(t, OperatorProduct) for t in tt_sum.tensors):
-        tt_sum = TensorSum([t.to_tt() if isinstance(t, OperatorProduct) else t for t in tt_sum.tensors])
+    an ``OperatorProduct`` or ``HadamardProduct`` term as it is; the other methods form it first."""
+    lazy = (OperatorProduct, HadamardProduct)
+    if method in ("exact", "pairwise", None) and any(isinstance(t, lazy) for t in tt_sum.tensors):
+        tt_sum = TensorSum([t.to_tt() if isinstance(t, lazy) else t for t in tt_sum.tensors])
     if method == "exact":
         terms = [t.to_device() for t in tt_sum.tensors]
         tt = terms[0]
