@@ -366,6 +366,29 @@ int ttsk_cp_psi_omega(const double *L, int64_t ldl, const double *R, int64_t ldr
                       double *psi, const double *R_om, int64_t ld_om, int64_t r_om, double *omega, int64_t N, int64_t l, int64_t n,
                       int64_t r, int stream);
 
+/* ---- inner product of two CP tensors (csrc/cp_gram.hip, plan in csrc/cp_gram_plan.h) ----
+ * Tensor.dot / norm / error(fast=True) with a CPTensor on either side (tensor.py:53-88 densifies both operands):
+ *   dev_out[0] = sum_{j < N, j' < M} prod_k sum_i A_k[i, j] B_k[i, j']
+ * for factor matrices A_k (shape[k] x N) and B_k (shape[k] x M): 2 N M sum_k shape[k] flops, and no array of size N x M --
+ * a workgroup keeps the product over the modes of its 64 x 64 tile of (j, j') in registers.
+ *   dev_a[k]   A_k, element (i, j) at dev_a[k] + i lda[k] + j: columns contiguous, lda[k] >= N (a column slice of a wider
+ *              matrix is taken as it is); dev_a itself is a host array of d device pointers
+ *   dev_b, ldb the same for B_k, ldb[k] >= M
+ *   sym        != 0: b IS a (dev_b[k] == dev_a[k] and ldb[k] == lda[k] for every k, M == N); only the tiles with
+ *              tile(j) <= tile(j') are formed and those strictly above the diagonal count twice
+ *   dev_out    1 double
+ * Workgroup g of G = min(tiles, 3 x compute units) owns the tiles g, g + G, ... in ascending order and writes one partial;
+ * one workgroup adds the partials.  No atomics; the split depends on the shapes, sym and the CU count alone: the same
+ * bits on every call.  TTSK_ERR_ARG: a NULL pointer, d < 1, an extent below 1, a leading dimension below its width, sym
+ * with differing factors or M != N.  TTSK_ERR_UNSUPPORTED before anything is launched: d > 32, N, M or a mode of 2^31 or
+ * more.  Inside those bounds every shape runs. */
+int ttsk_cp_gram(const double *const *dev_a, const int64_t *lda, int64_t N, const double *const *dev_b, const int64_t *ldb,
+                 int64_t M, const int64_t *shape, int d, int sym, double *dev_out /* 1 double */, int stream);
+/* dev_out[0] = sum_i x_i by one workgroup in the library's fixed order (thread t adds x_t, x_{t + 256}, ... in ascending
+ * order, then the workgroup total): the same bits on every call; closes <tt, cp> after its chain of ttsk_cp_chain_step.
+ * n = 0 gives 0.  TTSK_ERR_UNSUPPORTED: n of 2^32 or more. */
+int ttsk_sum(const double *dev_x, size_t n, double *dev_out, int stream);
+
 /* ---- a tensor train against a dense tensor (csrc/tt_dense_stats.hip) ----------
  * Tensor.error / dot / norm for a DenseTensor argument (tensor.py:53-88) and TensorTrain.dense in one pass over the
  * tensor.  The train is cut at a bond: T^{<k>} = L R, dev_L (M x rho) and dev_R (rho x N) row-major and contiguous.

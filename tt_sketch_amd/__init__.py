@@ -14,7 +14,7 @@ from .sketch import (SketchedTensorTrain, assemble_sketched_tt, blocked_stream_s
 from .sketch_container import SketchContainer
 from .sketch_dispatch import SketchMethod, general_sketch
 from .tensor import (CPTensor, DenseTensor, SparseTensor, Tensor, TensorSum, TensorTrain,
-                     TuckerTensor, tt_gram)
+                     TuckerTensor, cp_gram, tt_gram)
 from .tt_svd import tt_svd
 
 __all__ = [
@@ -22,5 +22,5 @@ __all__ = [
     "SketchedTensorTrain", "assemble_sketched_tt", "blocked_stream_sketch", "hmt_sketch",
     "orthogonal_sketch", "orthogonal_sketch_batch", "hmt_sketch_batch", "stream_sketch", "stream_sketch_batch", "to_tt_batch", "SketchContainer", "SketchMethod", "general_sketch",
     "CPTensor", "DenseTensor", "SparseTensor", "Tensor", "TensorSum", "TensorTrain", "TuckerTensor",
-    "tt_svd", "tt_gram", "OperatorProduct", "HadamardProduct", "hadamard_round",
+    "tt_svd", "tt_gram", "cp_gram", "OperatorProduct", "HadamardProduct", "hadamard_round",
 ]

@@ -121,6 +121,8 @@ ENTRY_POINTS = {
     "ttsk_hadamard_apply": Entry([P, P, P, POINTER(I64), POINTER(I64), P, I64, I64, I], QUEUE),
     "ttsk_cp_chain_step": Entry([P, I64, P, I64, I64, P, P, I64, I64, I64, I64, I64, I], QUEUE),
     "ttsk_cp_psi_omega": Entry([P, I64, P, I64, P, I64, I64, P, P, I64, I64, P, I64, I64, I64, I64, I], QUEUE),
+    "ttsk_cp_gram": Entry([POINTER(P), POINTER(I64), I64, POINTER(P), POINTER(I64), I64, POINTER(I64), I, I, P, I], QUEUE),
+    "ttsk_sum": Entry([P, S, P, I], QUEUE),
     "ttsk_tt_dense_stats": Entry([P, I64, P, I64, I64, P, P, P, I], QUEUE),
     "ttsk_tt_dense_stats_ld": Entry([P, I64, P, I64, I64, P, I64, P, I64, P, I, I], QUEUE),
     "ttsk_sumsq": Entry([P, S, P, I], QUEUE),

@@ -1,5 +1,6 @@
 // The closing sum of the one-pass kernels that leave per-workgroup partial sums (the gather kernels, the dense statistics,
-// ttsk_sumsq): one workgroup adds them in the library's stated order (block_total, wave.h).
+// ttsk_sumsq, ttsk_cp_gram): one workgroup adds them in the library's stated order (block_total, wave.h).  ttsk_sum is that
+// sum of a caller's own vector.
 #include "common.h"
 
 namespace ttsk {
@@ -26,3 +27,14 @@ int sum_partials(const double *part, unsigned nparts, int W, double *out, int ac
 }
 
 }  // namespace ttsk
+
+extern "C" int ttsk_sum(const double *dev_x, size_t n, double *dev_out, int stream)
+{
+    TTSK_STREAM(st, stream);
+    TTSK_ARG(dev_out && (dev_x || n == 0), "ttsk_sum: NULL argument");
+    if (n > 0xffffffffu) {
+        ttsk::set_error("ttsk_sum: %zu values, below 2^32 is covered", n);
+        return TTSK_ERR_UNSUPPORTED;
+    }
+    return ttsk::sum_partials(dev_x, (unsigned)n, 1, dev_out, 0, st);
+}

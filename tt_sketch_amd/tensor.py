@@ -12,7 +12,8 @@ The arithmetic helpers (``error``, ``norm``, ``dot``, ``round``, ...) are off th
 path and stay plain NumPy on the host; the steps that follow
 ``to_tt()`` have device forms beside them (``round_dev``, ``orthogonalize_dev``, resident ``dot`` /
 ``norm``, the evaluation at index lists: ``gather_dev``, ``support_error``, ``SparseTensor.dot``, and the pass over a
-dense tensor: ``dense_stats``, ``to_dense_dev`` and with them ``error`` / ``dot`` against a ``DenseTensor``).
+dense tensor: ``dense_stats``, ``to_dense_dev`` and with them ``error`` / ``dot`` against a ``DenseTensor``; inner products
+with a ``CPTensor``: ``cp_gram``, ``CPTensor.dot`` / ``norm`` and ``TensorTrain.dot`` against it).
 
 Residency contract: payload arrays are treated as immutable once a tensor has been
 sketched; replace a core (``tt[i] = new``) rather than writing into it, or call
@@ -835,9 +836,13 @@ class TensorTrain(_GatherOnDevice, Tensor):
         out.append(np.concatenate((A[-1], B[-1]), axis=0))
         return TensorTrain(out)
 
-    def dot(self, other, reverse=False) -> float:
+    def dot(self, other, reverse=False, route: Optional[str] = None) -> float:
+        """``<self, other>``.  ``route`` is the switch of ``paths.py`` for the one path here that has a kernel and a
+        composition per step, the chain against a ``CPTensor`` (``_tt_cp_dot``)."""
         if isinstance(other, TensorTrain) and self.resident() and other.resident():
             return float(tt_gram([self], [other])[0, 0])        # one device call, or the chain where tt_gram routes it
+        if isinstance(other, CPTensor) and (_on_device(self) or _on_device(other)):
+            return _tt_cp_dot(self, other, route)
         if isinstance(other, TensorTrain):
             acc = np.ones((1, 1))
             for a, b in zip(self.cores, other.cores):
@@ -851,7 +856,12 @@ class TensorTrain(_GatherOnDevice, Tensor):
         """``||self - other||`` (reference tensor.py:53-88).  Against a dense tensor with either side on the device all
         of it comes from the four sums of one pass (``dense_stats``): the residual is ``sqrt(sum (t - x)^2)``, the
         reference norm ``sqrt(sum x^2)``, and ``fast`` puts ``sum x t``, ``sum t^2`` and ``sum x^2`` into the reference's
-        formula.  A host train with a host array keeps the NumPy path."""
+        formula.  A host train with a host array keeps the NumPy path.
+
+        Against a ``CPTensor`` (or a ``TensorSum`` that holds one) ``fast=True`` is the reference's formula on
+        ``self.norm()``, ``other.norm()`` and ``self.dot(other)``, which stay on the device when either side is there
+        (``cp_gram``, ``_tt_cp_dot``) and form no dense array; that formula has the reference's floor of about 1e-8
+        relative.  ``fast=False`` against CP keeps the reference's dense formula."""
         if hasattr(other, "to_tt"):
             other = other.to_tt()
         dense = DenseTensor(other) if isinstance(other, np.ndarray) else other
@@ -1065,9 +1075,66 @@ class TensorSum(Tensor):
         return f"<Sum of {self.num_summands} tensors of shape {self.shape} at {hex(id(self))}>"
 
 
+# ------------------------------------------------------------------ inner products with a CP tensor (csrc/cp_gram.hip)
+def _on_device(t) -> bool:
+    """The condition of ``SparseTensor.dot`` for a device path: the payload lives in HBM only, or is uploaded already."""
+    return t.resident() or t._dev is not None
+
+
+def _cp_factor(F: DevArray) -> Tuple[DevArray, int]:
+    """A factor matrix ``(n, N)`` as ``ttsk_cp_gram`` takes it -- columns contiguous, rows a leading dimension >= N
+    apart, so a column slice goes as it is -- and that leading dimension."""
+    n, N = F.shape
+    if not ((N == 1 or F.strides[1] == 1) and (n == 1 or F.strides[0] >= N)):
+        F = F.contiguous()
+    return F, (F.strides[0] if n > 1 else N)
+
+
+def cp_gram(a: "CPTensor", b: Optional["CPTensor"] = None) -> float:
+    """``<a, b> = sum_{j, j'} prod_k (A_k^T B_k)[j, j']`` of two CP tensors of one shape (``b=None``: ``<a, a>``, of which
+    only the tiles on and above the diagonal are formed).  Host factors are uploaded once (``dev_cores``); one call of
+    ``ttsk_cp_gram``, which keeps the product over the modes in registers: no dense tensor and no ``N x M`` array, and
+    the same bits on every call."""
+    from . import _native as nat
+    sym = b is None or b is a
+    for t in (a,) if sym else (a, b):
+        if not isinstance(t, CPTensor):
+            raise TypeError(f"cp_gram: {type(t).__name__} is not a CPTensor")
+    if not sym and tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"cp_gram: CP tensors of shapes {a.shape} and {b.shape}")
+    fa = [_cp_factor(F) for F in a.dev_cores()]
+    fb = fa if sym else [_cp_factor(F) for F in b.dev_cores()]
+    out = DevArray.empty((1,))
+    nat.call("ttsk_cp_gram", nat.ptr_array([F for F, _ in fa]), nat.i64_array([ld for _, ld in fa]), a.rank,
+             nat.ptr_array([F for F, _ in fb]), nat.i64_array([ld for _, ld in fb]), a.rank if sym else b.rank,
+             nat.i64_array(a.shape), a.ndim, int(sym), out, 0)
+    return float(out.get()[0])
+
+
+def _tt_cp_dot(tt: "TensorTrain", cp: "CPTensor", route: Optional[str] = None) -> float:
+    """``<tt, cp>`` by the left-to-right chain ``L_k[j, a'] = sum_{a, i} L_{k-1}[j, a] V_k[i, j] C_k[a, i, a']``: the
+    recurrence of ``TensorTrainDRM.sketch_cp`` with the train's cores in place of the DRM's, so each mode is one
+    ``ttsk_cp_chain_step`` -- or, beyond that entry's cover (a train rank above 128) and where ``cp_fused.chain_route_ms``
+    gives the step to it, the two ``contract`` calls of ``sketch_cp``.  The last mode leaves ``(N, 1)``, which
+    ``ttsk_sum`` adds in the library's fixed order.  ``route``: the switch of ``paths.py``."""
+    from . import _native as nat
+    from .cp_fused import _chain
+    if tuple(tt.shape) != tuple(cp.shape):
+        raise ValueError(f"dot: a train of shape {tt.shape} against a CP tensor of shape {cp.shape}")
+    L = _chain(cp.dev_cores(), tt, resolve(route), 0)[-1].contiguous()
+    out = DevArray.empty((1,))
+    nat.call("ttsk_sum", L, L.size, out, 0)
+    return float(out.get()[0])
+
+
 # --------------------------------------------------------------------------- CP
 class CPTensor(_GatherOnDevice, Tensor):
-    """CP format, factor matrices ``(n_k, R)`` (reference tensor.py:674-743)."""
+    """CP format, factor matrices ``(n_k, R)`` (reference tensor.py:674-743).
+
+    ``dot`` / ``norm`` against another ``CPTensor`` or a ``TensorTrain`` run on the device when either operand is there
+    (``resident()`` or uploaded already) and form no dense array; with them ``error(fast=True)`` -- the reference's
+    formula, whose floor is a relative error of about 1e-8 -- does not either.  Two host objects keep the NumPy path,
+    and ``fast=False`` keeps the reference's dense formula."""
 
     def __init__(self, cores: ArrayList, _dev=None) -> None:
         self.cores = cores
@@ -1127,6 +1194,19 @@ class CPTensor(_GatherOnDevice, Tensor):
         for C, rows in zip(self.cores, idx):
             acc = acc * _host(C)[rows]
         return np.sum(acc, axis=1)
+
+    def norm(self) -> float:
+        if _on_device(self):
+            return float(np.sqrt(abs(cp_gram(self))))
+        return super().norm()
+
+    def dot(self, other, reverse=False, route: Optional[str] = None) -> float:
+        """``route``: the switch of ``paths.py`` for the chain against a ``TensorTrain`` (``_tt_cp_dot``)."""
+        if isinstance(other, CPTensor) and (_on_device(self) or _on_device(other)):
+            return cp_gram(self, other)
+        if isinstance(other, TensorTrain) and (_on_device(self) or _on_device(other)):
+            return _tt_cp_dot(other, self, route)
+        return super().dot(other, reverse=reverse)
 
     def __mul__(self, other: float) -> "CPTensor":
         cores = list(self.cores)
