@@ -162,6 +162,17 @@ int ttsk_chain_step_sum(int nb, int n, int K1, int A, int A2, int J, const doubl
                         const double *const *X, int64_t x_j, int64_t x_k, int64_t x_c, int64_t x_extent,
                         const double *E, double *T, int64_t t_b, int64_t t_ld, int64_t t_extent,
                         double *const *Out, int stream);
+/* A DRM core E (A, n, A2) is the same for every sketch it takes part in; ttsk_chain_step's kernel reads each slice
+ * E[:, k, :] into LDS in one fixed permutation.  ttsk_drm_pack stores that permutation once (csrc/chain_pack.hip): an
+ * image of n * eunits * 16 bytes -- at rank 100 as large as the core, so a packed core takes about twice the device
+ * memory -- allocated by the library and registered under (core, A, n, A2).  Every later fused chain step whose E is
+ * `core` with these extents loads its slices from the image, 1 KB per instruction; results are bit-identical.  Returns
+ * after `stream` has drained.  TTSK_ERR_UNSUPPORTED for ranks the fused kernel does not cover (nothing is registered).
+ * THE CORE MUST NOT BE WRITTEN WHILE IT IS REGISTERED, and must be unregistered before its memory is freed or reused:
+ * ttsk_drm_unpack drops and frees the image (no-op for an unregistered core; waits for the device).  ttsk_shutdown
+ * empties the registry. */
+int ttsk_drm_pack(const double *core, int A, int n, int A2, int stream);
+int ttsk_drm_unpack(const double *core);
 /* Dense tensor x DRM MATRICES (dense_gaussian_drm.py:77-80, dense_sketch.py:7-52): the first four left products
  * Z_mu = A_mu X^{<mu+1>}, mu = 0..3, from ONE read of X viewed as (n0, n1, n2, C = n3 * n4) (csrc/dense_left_pass.hip).
  * A0 (l, n0) and A3 (l, n0 n1 n2 n3) as the DRM holds them, A1t (l, n1, n0) / A2t (l, n2, n1, n0) the transposed copies of

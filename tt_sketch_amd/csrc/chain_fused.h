@@ -86,9 +86,9 @@ __device__ __forceinline__ void cf_piece(const ChainStep &a, const double *Wl, c
     // LDS addresses of this lane's fragment elements inside a k-block's two sections
     const int wl_lane = (kq >> 1) * 2 * AP + 2 * (16 * q0 + x16) + (kq & 1);
     const int ws_lane = (kq >> 1) * 2 * AP + 2 * (16 * (q0 + NQF) + (x16 & 3)) + (kq & 1);
-    const int el_lane = (kq >> 1) * 2 * A2P + 4 * (x16 >> 1) + 2 * (kq & 1) + (x16 & 1);
+    const int el_lane = e_frag_lane(x16, kq, A2P);
     const int es_col = 16 * NNF + (x16 & 3);
-    const int es_lane = (kq >> 1) * 2 * A2P + 2 * (kq & 1);
+    const int es_lane = e_strip_lane(kq, A2P);
 
     __amdgpu_buffer_rsrc_t rt;
     if constexpr (WT) rt = make_rsrc(uniform_ptr(a.T[prob]), a.t_extent * 8);
@@ -172,7 +172,7 @@ __device__ __forceinline__ void cf_piece(const ChainStep &a, const double *Wl, c
             // per-slice copies of the lane offsets the compiler cannot see through: it then forms each k-block's
             // address with one add where it is used, instead of keeping 2 x 25 precomputed addresses alive across
             // the slice loop (and spilling them into the phase)
-            int el0 = el_lane, es0 = es_lane + 4 * (es_col >> 1) + (es_col & 1);
+            int el0 = el_lane, es0 = es_lane + e_image_at(0, es_col, A2P);
             asm volatile("" : "+v"(el0), "+v"(es0));
             auto efetch = [&](int kap, double (&f)[NNF ? NNF : 1], double (&g)[STRN ? STRN : 1]) {
 #pragma unroll
@@ -284,10 +284,10 @@ __device__ __forceinline__ void cf_rows4(const ChainStep &a, const double *Wl, c
 
     const int wl_lane = (kq >> 1) * 2 * AP + 2 * x16 + (kq & 1);
     const int ws_lane = (kq >> 1) * 2 * AP + 2 * (16 * NQF + n4) + (kq & 1);
-    // E[row][col] sits at (row >> 1) 2 A2P + 4 (col >> 1) + 2 (row & 1) + (col & 1); row = 16 p + 4 beta + kq (a strip:
-    // 16 NQF + 4 q + kq in every block), col = 4 c + n
-    const int el_lane = (2 * beta + (kq >> 1)) * 2 * A2P + 4 * (n4 >> 1) + 2 * (kq & 1) + (n4 & 1);
-    const int es_lane = (kq >> 1) * 2 * A2P + 4 * (n4 >> 1) + 2 * (kq & 1) + (n4 & 1);
+    // E[row][col] sits at e_image_at(row, col); row = 16 p + 4 beta + kq (a strip: 16 NQF + 4 q + kq in every block),
+    // col = 4 c + n
+    const int el_lane = e_image_at(4 * beta + kq, n4, A2P);
+    const int es_lane = e_image_at(kq, n4, A2P);
 
     __amdgpu_buffer_rsrc_t rt;
     if constexpr (WT) rt = make_rsrc(uniform_ptr(a.T[prob]), a.t_extent * 8);
@@ -416,8 +416,8 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 * OCC : 1) void chain_step_k
     }
 
     // the wave's piece (levelled workgroups): wave-uniform, fetched once.  Every wave the deal left without a piece is a
-    // loader: loader li of nl brings every nl-th KB of E_k (one wave's address arithmetic for all of E_k at rank 100
-    // takes longer than a levelled phase A)
+    // loader: loader li of nl brings every nl-th KB of E_k (one wave alone needs longer for all of E_k at rank 100 than a
+    // levelled phase A takes, gathered or packed)
     unsigned pc = 0;
     int li = 0, nl = 1;
     if constexpr (NWV != 8) {
@@ -434,24 +434,44 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 * OCC : 1) void chain_step_k
         // levelled workgroups: the loader is the youngest of three waves on its SIMD and the arbiter serves the oldest
         // first -- left at that it issues one load per ~300 cycles and E_k lands after phase A is over
         if constexpr (NWV != 8) __builtin_amdgcn_s_setprio(3);
+#ifdef TTSK_LAB
+        if (CF_DIAG(8)) {                              // one loader, the other spare waves leave
+            if (li > 0) { __syncthreads(); return; }
+            nl = 1;
+        }
+#endif
         const int NI = CF_DIAG(2) ? 0 : a.eunits >> 6;
-        const uint32_t inv = (uint32_t)(((1ull << 32) + (uint32_t)A2P - 1) / (uint32_t)A2P);   // U / A2P for U < 2^16
+        const uint32_t inv = e_image_inv(A2P);
         const int64_t rowstride = (int64_t)a.n * a.A2;
         const int ebuf = a.eunits * 2;                 // doubles per E image
-        auto fill = [&](int k) {
+        auto fill_gather = [&](int k) {
             const double *Ek = a.E + (int64_t)k * a.A2;
             double *dst = El + (EBUF == 2 ? (k & 1) * ebuf : 0);
 #pragma unroll 2
             for (int m = li; m < NI; m += nl) {
-                const uint32_t U = 64u * (uint32_t)m + (uint32_t)lane;
-                const uint32_t sec = (uint32_t)(((uint64_t)U * inv) >> 32), u = U - sec * (uint32_t)A2P;
-                int row = (int)(2 * sec + (u & 1));
-                row = row < a.A ? row : a.A - 1;
-                int col = (int)(2 * (u >> 1));
-                col = col + 1 < a.A2 ? col : 0;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(Ek + row * rowstride + col),
+                const EUnit un = e_image_unit(64u * (uint32_t)m + (uint32_t)lane, inv, a.A, a.A2, A2P);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(Ek + un.row * rowstride + un.col),
                                                  (__attribute__((address_space(3))) void *)(dst + m * 128), 16, 0, 0);
             }
+        };
+        // A packed core (chain_pack.hip) holds the image itself: piece m of slice k is 1 KB at Epk + (k eunits + 64 m) units,
+        // a wave-uniform base that moves by a constant per instruction under the lane's fixed 16 bytes -- no division,
+        // no clamp, no 64-bit product, and every instruction reads 1 KB of consecutive memory instead of 2 x 16 pieces
+        // of 16 bytes from two rows 160 KB apart.  (Stamps: a loader wave still needs ~650 cycles per instruction -- the
+        // arithmetic was not what bounds it -- so all spare waves stay loaders: one alone lands E_k 3.6 k cycles late.)
+        const uint32_t lane16 = 16u * (uint32_t)lane;
+        auto fill_packed = [&](int k) {
+            const char *src = (const char *)(a.Epk + ((int64_t)k * a.eunits + 64 * li) * 2);
+            double *dst = El + (EBUF == 2 ? (k & 1) * ebuf : 0);
+#pragma unroll 2
+            for (int m = li; m < NI; m += nl, src += 1024 * nl)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + lane16),
+                                                 (__attribute__((address_space(3))) void *)(dst + m * 128), 16, 0, 0);
+        };
+        const bool packed = a.Epk != nullptr;          // wave-uniform (a kernel argument)
+        auto fill = [&](int k) {
+            if (packed) fill_packed(k);
+            else fill_gather(k);
         };
         __syncthreads();                               // W staged (all waves)
         if constexpr (EBUF == 2) {
@@ -504,5 +524,8 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 * OCC : 1) void chain_step_k
 
 // 1 = launched (the slab reduce included), 0 = shape not covered, < 0 = error
 int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force = false);
+
+// chain_pack.hip: the packed image registered for core E with exactly these extents and image layout, or nullptr
+const double *drm_packed_lookup(const double *E, int A, int n, int A2, int A2P, int eunits);
 
 }  // namespace ttsk

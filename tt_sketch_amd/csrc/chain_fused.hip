@@ -31,6 +31,7 @@ int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool for
     ChainStep &a = p.a;
     a.slab = (double *)scratch(stream, SCRATCH_GEMM, (size_t)p.l.slab * 8 + 64);
     if (!a.slab) return TTSK_ERR_HIP;
+    a.Epk = drm_packed_lookup(c.E, c.A, c.n, c.A2, a.A2P, a.eunits);
     // flops of BOTH products of the step (the pair this kernel replaces), reduce launch inside the bracket; the name as
     // profiles/*_traffic.json is keyed by it: the nine parameters from before the deal (no NWV), NN / SN given as NQ / SQ
     ProfBracket prof(st, PROF_CURRENT, p.l.flops,
@@ -56,7 +57,7 @@ int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool for
         long long t0 = 0;
         for (int i = 0; i < 8 * CD_WAVES * 8; ++i) if (h[i] && (!t0 || h[i] < t0)) t0 = h[i];
         fprintf(stderr, "[cf stamps] workgroup 0: cycles since its first stamp; per slice, wave: start | endA | afterB1 | endB | afterB2\n");
-        for (int sl = 0; sl < 4; ++sl)
+        for (int sl = 0; sl < 8; ++sl)
             for (int w = 0; w < CD_WAVES; ++w) {
                 const long long *r = h + (sl * CD_WAVES + w) * 8;
                 if (!r[1] && !r[4]) continue;

@@ -1,6 +1,6 @@
 // What the three chain-step kernels (chain_fused.h, chain_wide.h, chain_sum.h) are launched with, decided on the host:
 // the cover tests, the LDS plan, the wave tables, the grid rule, the proofs that every 32-bit byte offset fits, the slab
-// of partial results and its closing reduce.  A plan holds the filled kernel-argument struct (all but `slab` and the
+// of partial results and its closing reduce.  A plan holds the filled kernel-argument struct (all but `slab`, `Epk` and the
 // lab-only `diag` / `stamps`), the instantiation the launcher picks and the launch figures; the launchers
 // (chain_fused.hip, chain_wide.hip, chain_sum.hip) only carry it out.
 //
@@ -45,6 +45,7 @@ struct ChainStep {
     const double *X[SK_MAXB];
     double *T[SK_MAXB];          // WT: T[a][k][j] (A x n x J contiguous)
     const double *E;
+    const double *Epk;           // nullptr, or E packed (chain_pack.hip): slice k is the LDS image of E_k, eunits units; set by the launcher
     double *slab;                // [problem][workgroup of the problem][J][A2]
     int nb, wpp, n;              // problems, workgroups per problem, slices (mode size)
     int K1, A, A2, J;
@@ -58,11 +59,46 @@ struct ChainStep {
     unsigned int piece[CD_WAVES];// levelled workgroups (12 waves): wave w runs row tile | first Q << 8 | kind << 16 (chain_deal.h);
                                  // kind CD_NONE: a loader, its index among the nload loaders << 8
     int nload;
-    int diag;                    // timing experiments (TTSK_CF_DIAG): 1 = no X loads, 2 = no E loads, 4 = no barriers; results are then wrong
+    int diag;                    // timing experiments (TTSK_CF_DIAG): 1 = no X loads, 2 = no E loads, 4 = no barriers (results are then wrong); 8 = one loader wave
     long long *stamps;           // diagnostics (TTSK_CF_STAMPS): s_memtime of workgroup 0, [slice][wave of CD_WAVES][8]
 };
 
 constexpr int CF_MAX_DMA = 160;  // loader instructions per slice (1 KB each)
+
+// ---- the E image of chain_step_kernel --------------------------------------------------------------------------------
+// One slice E_k[a][a'] (A x A2) sits in LDS pair-interleaved, in 16-byte units (two doubles): section sec holds rows
+// 2 sec and 2 sec + 1, A2P units long; unit u of a section is columns (2 (u >> 1), + 1) of row 2 sec + (u & 1).  The 32
+// lanes (kq in {0, 1}, x) of a phase-B fragment then read 32 consecutive doubles.  Defined here once, for the loader that
+// gathers the image from E, for the kernel that packs it (chain_pack.hip) and for the host test of both
+// (tests/test_chain_pack_host.py).  constexpr: the device code calls them as they stand.
+struct EUnit { int row, col; };
+
+// ceil(2^32 / A2P): U / A2P == (U * inv) >> 32 for U < 2^16
+constexpr uint32_t e_image_inv(int A2P) { return (uint32_t)(((1ull << 32) + (uint32_t)A2P - 1) / (uint32_t)A2P); }
+
+// Which two elements E[row][col], E[row][col + 1] unit U of the image holds.  Rows beyond A repeat row A - 1 (they meet
+// exact zeros of T), a last unit whose second column would lie beyond A2 holds columns 0, 1 (never read).
+constexpr EUnit e_image_unit(uint32_t U, uint32_t inv, int A, int A2, int A2P)
+{
+    const uint32_t sec = (uint32_t)(((uint64_t)U * inv) >> 32), u = U - sec * (uint32_t)A2P;
+    int row = (int)(2 * sec + (u & 1));
+    row = row < A ? row : A - 1;
+    int col = (int)(2 * (u >> 1));
+    col = col + 1 < A2 ? col : 0;
+    return EUnit{row, col};
+}
+
+// The inverse view: the offset (doubles) of E[a][a2] in the image ...
+constexpr int e_image_at(int a, int a2, int A2P) { return (a >> 1) * 2 * A2P + 4 * (a2 >> 1) + 2 * (a & 1) + (a2 & 1); }
+// ... and phase B's fragment reads.  Lane (x16 = lane & 15, kq = lane >> 4) reads E[4 kap + kq][16 nn + x16] of k-block kap,
+// column tile nn, at e_frag_lane + kap 4 A2P + 32 nn; of strip q behind NNF full tiles E[4 kap + kq][16 NNF + 4 q + (x16 & 3)]
+// at e_strip_lane + e_image_at(0, 16 NNF + (x16 & 3)) + kap 4 A2P + 8 q.
+constexpr int e_frag_lane(int x16, int kq, int A2P) { return (kq >> 1) * 2 * A2P + 4 * (x16 >> 1) + 2 * (kq & 1) + (x16 & 1); }
+constexpr int e_strip_lane(int kq, int A2P) { return (kq >> 1) * 2 * A2P + 2 * (kq & 1); }
+
+// A packed DRM core (chain_pack.hip): Epk[k][eunits] units, slice k the image of E_k byte for byte.  Its size in bytes --
+// at rank 100 as large as the core itself: a packed DRM takes about twice the device memory.
+constexpr int64_t e_pack_bytes(int n, int eunits) { return (int64_t)n * eunits * 16; }
 
 struct ChainWide {
     const double *W[SK_MAXB];
@@ -199,6 +235,18 @@ inline void chain_tile_split(int r, int &nf, int &str)
     else { nf += 1; str = 0; }
 }
 
+// The E image of a DRM core of ranks (A, A2) as chain_fused_plan lays it out: row length A2P, and the 16-byte units of a
+// slice padded to whole 64-unit (1 KB) loader pieces.  false: chain_step_kernel has no image for these ranks.
+inline bool chain_e_image(int A, int A2, int &A2P, int &eunits)
+{
+    if (A < 4 || A2 < 4 || (A2 & 1)) return false;
+    int nq, sq;
+    chain_tile_split(A, nq, sq);
+    A2P = A2;
+    eunits = (int)cdiv((int64_t)2 * (nq * 4 + sq) * A2P, 64) * 64;     // 2 KB2 A2P units
+    return eunits / 64 <= CF_MAX_DMA;
+}
+
 // k-blocks of phase A are issued in straight-line runs of 25 or of 5 and padded to whole runs (the padded ones
 // meet zero rows of the W image): 25 when that pads at most one k-block more than 5 does
 inline void chain_phase_a_runs(int K1, int &unr, int &KB1)
@@ -232,13 +280,10 @@ inline int chain_fused_plan(const ChainStepArgs &c, int n_cu, bool force, ChainF
     // there is little T to keep on chip anyway (the two-launch form is then the faster one: measured on C5)
     if (!force && 2 * c.K1 < c.A) return 0;
     a.AP = 16 * nq + 4 * sq;
-    a.A2P = c.A2;
     if (a.AP < 4 * KB2) return 0;
     const int64_t wl = (int64_t)4 * KB1 * a.AP;                          // doubles
     a.ebase = (int)((wl + 1) & ~(int64_t)1);
-    const int64_t units = (int64_t)2 * KB2 * a.A2P;                      // 16-byte units of the E image
-    a.eunits = (int)cdiv(units, 64) * 64;
-    if (a.eunits / 64 > CF_MAX_DMA) return 0;
+    if (!chain_e_image(c.A, c.A2, a.A2P, a.eunits)) return 0;
     // two E images for the small structures (the load of E_{k+1} then has a whole slice to land: their
     // phases are too short to hide it), one for the large ones (no LDS room; their phases are long)
     const int ebuf = nq <= 4 ? 2 : 1;

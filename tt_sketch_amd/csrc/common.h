@@ -22,6 +22,8 @@ void *scratch(int stream, int slot, size_t bytes);
 // another device gets fresh ones.  nullptr on failure.
 enum { PA_PINV_HOST = 0, PA_PINV_DEV, PA_DEFERRED, PA_PINV_BATCH_VD, PA_DEFERRED_PINNED, PA_SLOTS };
 void *persistent_alloc(int key, size_t bytes, bool host, bool zero);
+// chain_pack.hip: frees every packed DRM image and empties the registry (ttsk_shutdown: a re-init starts without any)
+void drm_packed_clear();
 
 #define TTSK_HIP(call)                                                          \
     do {                                                                        \

@@ -173,8 +173,9 @@ int ttsk_shutdown(void)
 {
     std::lock_guard<std::mutex> lk(g_mu);
     if (!g_init) return TTSK_OK;
+    for (int i = 0; i < TTSK_NUM_STREAMS; ++i) (void)hipStreamSynchronize(g_streams[i]);
+    drm_packed_clear();
     for (int i = 0; i < TTSK_NUM_STREAMS; ++i) {
-        (void)hipStreamSynchronize(g_streams[i]);
         (void)hipStreamDestroy(g_streams[i]);
         (void)hipEventDestroy(g_ev_start[i]);
         (void)hipEventDestroy(g_ev_stop[i]);

@@ -236,7 +236,8 @@ static int right_step(const Ctx &c, int j)
     return TTSK_OK;
 }
 
-// left chain: L_mu and the shared products T_mu = L_{mu-1}^T X_mu (the last step only makes T_{d-1}, for Psi_{d-1})
+// left chain: L_mu and the shared products T_mu = L_{mu-1}^T X_mu (the last step only makes T_{d-1} = Psi_{d-1}: of a sketch
+// per tensor straight into the sketch, of a sum into the workspace)
 static int left_step(Ctx &c, int mu)
 {
     const int nb = c.nb, d = c.d;
@@ -281,6 +282,15 @@ static int left_step(Ctx &c, int mu)
         q.A[0] = T0; q.B[0] = c.DL[mu]; q.C[0] = c.Lp(0, mu);
         CK(gemm_batch(3, 1, gemm_desc2((int64_t)nb * sp, lt[mu + 1], lfull, nn, 1, nn * ldt, ldt, nn * lt[mu + 1], lt[mu + 1], 1,
                                   lt[mu + 1], 1, 0), q, c.aux, c.st_aux));
+        return TTSK_OK;
+    }
+    if (mu == d - 1 && !c.sum) {
+        // last mode, a sketch per tensor: Psi_{d-1}[q,k,0] = T[q,k,0] for q in [l_lo, l_hi) -- the same product on those
+        // columns of L_{d-2}, written (or accumulated) straight into the sketch: no T_{d-1}, no copy per tensor behind it
+        if (c.lw(mu - 1) == 0) return TTSK_OK;
+        for (int b = 0; b < nb; ++b) { p.A[b] = c.Lslice(b, mu - 1); p.B[b] = c.Xc(b, mu); p.C[b] = c.outb(b) + c.psi_at[mu]; }
+        CK(gemm_batch(5, nb, gemm_desc2(c.lw(mu - 1), nn * sp, 1, sn, 1, 0, lfull, 0, nn * sp, 1, nn * sp, 1, c.accumulate), p, c.aux,
+                      c.st_aux));
         return TTSK_OK;
     }
     // T[q,k,p'] = sum_p Lc[p,q] X[p,k,p']      (M=q (all lfull columns), N=(k,p'), K=p)
@@ -377,15 +387,8 @@ static int psi_omega(const Ctx &c, int mu, int q, bool do_psi, bool do_omega)
         CK(gemm_batch(5, nb, gemm_desc2(nn, r, 1, sp, sp, 0, 1, 0, ldr, 1, r, 1, c.sum ? 0 : c.accumulate), p, q, stq));
         if (c.sum) CK(ttsk_sum_slices(c.out + c.psi_at[0], c.P0(0), nb, c.szP0, (size_t)(nn * r), c.accumulate, q));
     } else if (mu == d - 1) {
-        // last mode: Psi_{d-1}[q,k,0] = T[q,k,0], of a sum sum_b T_b[q,k,0]
-        const size_t len = (size_t)(c.lw(mu - 1) * nn);
-        if (c.sum)
-            CK(ttsk_sum_slices(c.out + c.psi_at[mu], c.Tslice(0, mu), nb, c.szT[mu], len, c.accumulate, q));
-        else
-            for (int b = 0; b < nb; ++b) {
-                if (c.accumulate) CK(ttsk_axpby(c.outb(b) + c.psi_at[mu], c.Tslice(b, mu), 1.0, 1.0, len, q));
-                else TTSK_HIP(hipMemcpyAsync(c.outb(b) + c.psi_at[mu], c.Tslice(b, mu), len * 8, hipMemcpyDeviceToDevice, stq));
-            }
+        // last mode: Psi_{d-1}[q,k,0] = T[q,k,0].  A sketch per tensor: left_step wrote it in place.  Of a sum: sum_b T_b[q,k,0]
+        if (c.sum) CK(ttsk_sum_slices(c.out + c.psi_at[mu], c.Tslice(0, mu), nb, c.szT[mu], (size_t)(c.lw(mu - 1) * nn), c.accumulate, q));
     } else if (c.sum && sp <= sum_psi_split) {
         CK(psi_sum_one_product(c, mu, q));
     } else {
@@ -570,8 +573,8 @@ static int tt_sketch_core(int nb, int d, const int64_t *n, const int64_t *s, con
     // both chains are needed from here on, on both streams.
     // Psi_0 = X_0 R_0 needs the right chain only (this stream): queued BEFORE the join, it runs while this stream would wait for the
     // left chain (the join costs ~16 us of cross-queue latency) instead of standing behind the Omega launch at the very end
-    // (one C3 tensor: 0.254 -> 0.239 ms).  (Psi_{d-1}, a copy of the left chain's last T, stays behind the join: on the helper
-    // stream in front of it, it would lengthen the chain the join waits for.)
+    // (one C3 tensor: 0.254 -> 0.239 ms).  (Psi_{d-1} of a sketch per tensor is the left chain's last product itself, written
+    // into the sketch on the helper stream; of a sum it is summed from the T_b behind the join.)
     const bool ends_early = !sum && d >= 3;
     if (ends_early) CK(psi_omega(c, 0, stream, true, false));
     CK(ttsk_stream_wait(stream, c.aux));

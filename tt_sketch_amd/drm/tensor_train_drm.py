@@ -8,6 +8,8 @@ last core never materialised) and every chain step is an MFMA contraction in HBM
 """
 from __future__ import annotations
 
+import ctypes
+import sys
 from typing import List, Optional, Tuple, Union
 
 import numpy as np
@@ -18,6 +20,38 @@ from ..drm_base import CanSlice, handle_transpose
 from ..sketching_methods.abstract_methods import (CansketchCP, CansketchDense, CansketchHadamardProduct,
                                                   CansketchOperatorProduct, CansketchSparse, CansketchTT, CanSketchTucker)
 from ..utils import random_normal_dev_many
+
+
+class _PackedCores:
+    """The chain images of a DRM's interior cores (``ttsk_drm_pack``) and the device cores they were made from.  Holding
+    the cores keeps their buffers out of the pool until the images are dropped: a registration never outlives its core.
+    Shared by a DRM and its copies (``.T``, ``copy.copy``); the images go when the last of them does, or on ``release``."""
+
+    def __init__(self):
+        self.cores: List[DevArray] = []
+
+    def add(self, core: DevArray) -> None:
+        if any(c is core for c in self.cores):
+            return
+        A, n, A2 = (int(x) for x in core.shape)
+        try:
+            nat.call("ttsk_drm_pack", ctypes.c_void_p(core.ptr), A, n, A2, 0)
+        except nat.TtskUnsupported:
+            return                       # ranks outside the fused chain step: nothing would read an image
+        self.cores.append(core)
+
+    def release(self) -> None:
+        cores, self.cores = self.cores, []
+        for c in cores:                  # before the buffers go back to the pool (``cores`` still holds them here)
+            nat.call("ttsk_drm_unpack", ctypes.c_void_p(c.ptr))
+
+    def __del__(self):
+        if sys.is_finalizing():          # the process ends: its device memory goes with it
+            return
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 class TensorTrainDRM(CansketchSparse, CansketchTT, CansketchCP, CanSlice, CansketchDense,
@@ -38,6 +72,24 @@ class TensorTrainDRM(CansketchSparse, CansketchTT, CansketchCP, CanSlice, Canske
                                                 [1.0 / np.sqrt(rk[mu]) for mu in range(k)])
         self._dev: List[DevArray] = []
         self._dev_src: list = []          # the host objects the device copies were made from
+        self._packed = _PackedCores()
+
+    def pack_for_chain(self) -> None:
+        """Stores the interior cores a second time in the layout the fused chain step loads them in (``ttsk_drm_pack``):
+        its loader then copies each slice instead of gathering it.  Worth it where the DRM sketches many tensors -- the
+        batched and summed one-call paths call this on first use; one sketch of a fresh DRM gains less than the pass over
+        the cores costs and does not pack.  Idempotent.  A packed core takes about twice its device memory; ``close``
+        (or the DRM's end) gives the images back, before the cores' buffers.
+
+        Invariant: device cores are never written after they are made (every method here only reads them).  Code that
+        does write one must call ``ttsk_drm_unpack`` on it first."""
+        for k, c in enumerate(self.dev_cores()):
+            if k >= 1 and c.ndim == 3 and c.is_contiguous():
+                self._packed.add(c)
+
+    def close(self) -> None:
+        """Drops the packed chain images (the DRM stays usable; it packs again on the next batched use)."""
+        self._packed.release()
 
     def dev_cores(self) -> List[DevArray]:
         """Device copies of ``self.cores`` (the list may grow: OrthogTTDRM appends)."""

@@ -39,6 +39,7 @@ class TTSketchPlan:
         self.l_lo, self.l_hi = arr(left_drm.rank_min), arr(left_drm.rank_max)
         self.r_lo, self.r_hi = arr(right_drm.rank_min), arr(right_drm.rank_max)
         self._keep = (left_drm.dev_cores(), right_drm.dev_cores())
+        self._drms = (left_drm, right_drm)
         for k, c in enumerate(self._keep[0]):
             want = (self.lt[k], self.shape[k], self.lt[k + 1])
             if tuple(c.shape) != want:
@@ -70,7 +71,11 @@ class TTSketchPlan:
 
     def run_batch(self, X_ptrs, nb: int, out: DevArray, out_stride: int, accumulate: bool = False, stream: int = 0):
         """``nb`` tensors of the plan's signature in one pass: ``X_ptrs`` holds nb * d core pointers
-        (tensor-major), sketch ``b`` lands at ``out[b * out_stride:]``."""
+        (tensor-major), sketch ``b`` lands at ``out[b * out_stride:]``.  From two tensors on the DRMs are packed for the
+        chain steps first (``TensorTrainDRM.pack_for_chain``, once per DRM: it allocates and waits for the stream, so
+        call it yourself before capturing this call into a graph)."""
+        if nb >= 2:
+            self._pack()
         nat.call("ttsk_tt_sketch_batch", nb, self.d, self.n, self.s, self.lt, self.l_lo, self.l_hi, self.rt,
                  self.r_lo, self.r_hi, X_ptrs, self.DL, self.DR, out, out_stride,
                  1 if accumulate else 0, stream)
@@ -78,8 +83,16 @@ class TTSketchPlan:
     def run_sum(self, X_ptrs, nb: int, out: DevArray, accumulate: bool = False, stream: int = 0):
         """The sketch of the SUM of ``nb`` tensors of the plan's signature as one packed sketch at ``out``
         (``ttsk_tt_sketch_sum``: chains per tensor, Psi / Omega contracted over (tensor, rank) at once)."""
+        if nb >= 2:
+            self._pack()
         nat.call("ttsk_tt_sketch_sum", nb, self.d, self.n, self.s, self.lt, self.l_lo, self.l_hi, self.rt,
                  self.r_lo, self.r_hi, X_ptrs, self.DL, self.DR, out, 1 if accumulate else 0, stream)
+
+    def _pack(self):
+        if self._drms is not None:
+            for drm in self._drms:
+                drm.pack_for_chain()
+            self._drms = None
 
     def views(self, out: DevArray) -> Tuple[List[DevArray], List[DevArray]]:
         """Psi / Omega arrays as views into the packed (contiguous) buffer."""
