@@ -24,7 +24,7 @@ import numpy as np
 from tt_sketch_amd import TensorTrain, _native as nat
 from tt_sketch_amd import device as dev
 from tt_sketch_amd.device import DevArray, axpby, contract
-from tt_sketch_amd.tensor import _dense_split, _tt_dense_pass
+from tt_sketch_amd.tensor_dense import _dense_split, _tt_dense_pass
 
 WARM, REPS = 3, 21
 

@@ -32,10 +32,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import numpy as np
 
 from tt_sketch_amd import TensorTrain, tt_gram, _native as nat
-from tt_sketch_amd import tensor as tmod
+from tt_sketch_amd import tensor_gram as tmod
 from tt_sketch_amd.device import DevArray
 from tt_sketch_amd.paths import forced
-from tt_sketch_amd.tensor import _tt_dot_composed
+from tt_sketch_amd.tensor_gram import _tt_dot_composed
 
 WARM = 2
 

@@ -426,7 +426,7 @@ def test_route_switch_through_op_apply(monkeypatch):
 
 
 def test_route_switch_through_tt_gram(monkeypatch):
-    from tt_sketch_amd import TensorTrain, _native as nat, paths, tensor as tmod, tt_gram
+    from tt_sketch_amd import TensorTrain, _native as nat, paths, tensor_gram as tmod, tt_gram
     tts = [TensorTrain([np.ones((1, 3, 2)), np.ones((2, 4, 1))]) for _ in range(2)]
     monkeypatch.setattr(tmod, "_gram_composed", _reach("composed"))
     monkeypatch.setattr(nat, "call", lambda name, *a: _reach(name)())

@@ -91,7 +91,7 @@ def _random_plans(n, seed):
 
 
 def test_split_minimises_the_panels():
-    from tt_sketch_amd.tensor import _dense_split
+    from tt_sketch_amd.tensor_dense import _dense_split
     for shape, rank in _random_plans(300, 1):
         plan = _dense_split(shape, rank, 1 << 62)
         cost, k = _brute(shape, rank)
@@ -105,7 +105,7 @@ def test_split_minimises_the_panels():
 
 
 def test_split_stays_under_the_budget_and_tiles_the_mode():
-    from tt_sketch_amd.tensor import _dense_split
+    from tt_sketch_amd.tensor_dense import _dense_split
     slabbed = 0
     for shape, rank in _random_plans(400, 2):
         rk = (1,) + rank + (1,)
@@ -133,7 +133,7 @@ def test_split_stays_under_the_budget_and_tiles_the_mode():
 
 
 def test_split_refuses_what_cannot_fit():
-    from tt_sketch_amd.tensor import _dense_split
+    from tt_sketch_amd.tensor_dense import _dense_split
     with pytest.raises(ValueError, match=r"1000.*budget|budget"):
         _dense_split((1000, 1000, 1000), (50, 50), 1 << 20)
     for shape, rank in itertools.islice(_random_plans(50, 3), 50):

@@ -85,7 +85,7 @@ def check(L, R, x, T, s4, what, quiet=False):
 
 def _matricise(case):
     """L, R, x of a fixture case at the bond ``_dense_split`` picks, on the buffer the device would see."""
-    from tt_sketch_amd.tensor import _dense_split
+    from tt_sketch_amd.tensor_dense import _dense_split
     cores, x = case["cores"], case["x_buffer"]
     if case["transposed"]:
         cores = [np.transpose(c, (2, 1, 0)) for c in cores[::-1]]
@@ -181,20 +181,20 @@ def test_same_bits_every_call_with_and_without_out(tsa, monkeypatch):
         assert np.array_equal(r[2], runs[0][2])
     assert runs[1][1].tobytes() == runs[3][1].tobytes()
     # a slabbed run through the public API, repeated
-    from tt_sketch_amd import tensor as tmod
+    from tt_sketch_amd import tensor_dense as tmod
     from tt_sketch_amd.device import DevArray
     shape, rank = (30, 50, 40), (9, 30)
     tt = tsa.TensorTrain.random(shape, rank, seed=5).to_device()
     X = tsa.DenseTensor(DevArray.from_host(rng.standard_normal(shape)))
-    monkeypatch.setattr(tmod, "_GATHER_PANEL_BYTES", 8 * (30 * 9 + 7 * 40 * 9 + 30 * 40))
-    assert len(tmod._dense_split(shape, rank, tmod._GATHER_PANEL_BYTES)["slabs"]) == 8       # 7 x 7 + 1
+    monkeypatch.setattr(tmod, "_PANEL_BYTES", 8 * (30 * 9 + 7 * 40 * 9 + 30 * 40))
+    assert len(tmod._dense_split(shape, rank, tmod._PANEL_BYTES)["slabs"]) == 8       # 7 x 7 + 1
     a, b = tt.dense_stats(X), tt.dense_stats(X)
     assert np.array_equal(a, b)
 
 
 # ---- 3. slabs
 def test_slabbed_runs_agree_with_the_plain_run(tsa, monkeypatch):
-    from tt_sketch_amd import tensor as tmod
+    from tt_sketch_amd import tensor_dense as tmod
     from tt_sketch_amd.device import DevArray
     rng = np.random.default_rng(8)
     shape, rank = (12, 7, 33, 9, 5), (6, 14, 10, 4)
@@ -212,8 +212,8 @@ def test_slabbed_runs_agree_with_the_plain_run(tsa, monkeypatch):
     seen = set()
     for width in (None, shape[k], 5, 4, 1):                       # 5 and 4 do not divide 33
         if width is not None:
-            monkeypatch.setattr(tmod, "_GATHER_PANEL_BYTES", 8 * (M * rho + width * Np * rho + rk[k + 1] * Np))
-        plan = tmod._dense_split(shape, rank, tmod._GATHER_PANEL_BYTES)
+            monkeypatch.setattr(tmod, "_PANEL_BYTES", 8 * (M * rho + width * Np * rho + rk[k + 1] * Np))
+        plan = tmod._dense_split(shape, rank, tmod._PANEL_BYTES)
         assert plan["k"] == k
         seen.add(len(plan["slabs"]))
         s4 = tt.dense_stats(X)

@@ -151,17 +151,17 @@ def test_rank_out_of_cover_is_refused_by_c_and_composed_by_python(tsa):
     ref, scale = gr.tt_gather(cores, idx), gr.tt_gather(cores, idx, absolute=True)
     tt = tsa.TensorTrain(cores).to_device()
     check_values(tt.gather_dev(idx).get(), ref, scale, "composed gather_dev")
-    from tt_sketch_amd import tensor as tmod
+    from tt_sketch_amd import tensor_gather as tmod
     sp = tsa.SparseTensor(shape, idx, val)
-    old = tmod._GATHER_PANEL_BYTES
+    old = tmod._PANEL_BYTES
     try:
-        tmod._GATHER_PANEL_BYTES = 16 * (MAX_RANK + 44) * 1000          # three chunks and a remainder
+        tmod._PANEL_BYTES = 16 * (MAX_RANK + 44) * 1000          # three chunks and a remainder
         check_values(tt.gather(sp), ref, scale, "composed, chunked")
         rs, terms = gr.stats(ref, val)
         assert abs(sp.dot(tt) - rs[0]) <= 1e-12 * terms[0]
         assert abs(tt.support_error(sp) ** 2 - rs[2]) <= 1e-12 * terms[2]
     finally:
-        tmod._GATHER_PANEL_BYTES = old
+        tmod._PANEL_BYTES = old
 
 
 def test_argument_errors(tsa):

@@ -176,7 +176,7 @@ def test_rank_past_the_cover_is_refused_by_c_and_composed_by_python(tsa, n_cu):
 def test_route_keyword_and_forced_context(tsa, n_cu):
     """``route=`` of tt_gram: the pass itself under "kernel" (ranks on both sides of 16: the FMA and the matrix-instruction
     body), the chain under "composed" and under ``forced("composed")``, and past the cover a refusal instead of the chain."""
-    from tt_sketch_amd import _native as nat, paths, tensor as tmod
+    from tt_sketch_amd import _native as nat, paths, tensor_gram as tmod
     rng = np.random.default_rng(21)
     shape = (3, 4, 3)
     A = [gr.random_cores(rng, shape, rk) for rk in ((1, 15), (16, 17))]

@@ -14,7 +14,8 @@ from .sketch import (SketchedTensorTrain, assemble_sketched_tt, blocked_stream_s
 from .sketch_container import SketchContainer
 from .sketch_dispatch import SketchMethod, general_sketch
 from .tensor import (CPTensor, DenseTensor, SparseTensor, Tensor, TensorSum, TensorTrain,
-                     TuckerTensor, cp_gram, tt_gram)
+                     TuckerTensor)
+from .tensor_gram import cp_gram, tt_gram
 from .tt_svd import tt_svd
 
 __all__ = [

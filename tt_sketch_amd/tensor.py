@@ -1,4 +1,4 @@
-"""Tensor types of the sketch API (host-side data model + HBM residency).
+"""Tensor types of the sketch API: the data model, its host arithmetic and HBM residency.
 
 Mirrors the public surface of the reference's ``tt_sketch/tensor.py`` (classes,
 constructor signatures, ``.T``, ``shape``/``rank``/``cores``...), because these are
@@ -8,12 +8,14 @@ payload to HBM once (``dev_*`` accessors) and ``.T`` re-uses that upload through
 strided views, so a right sketch (drm_base.py:122-145 in the reference transposes
 the tensor on every call) costs no copy and no PCIe traffic.
 
-The arithmetic helpers (``error``, ``norm``, ``dot``, ``round``, ...) are off the hot
-path and stay plain NumPy on the host; the steps that follow
-``to_tt()`` have device forms beside them (``round_dev``, ``orthogonalize_dev``, resident ``dot`` /
-``norm``, the evaluation at index lists: ``gather_dev``, ``support_error``, ``SparseTensor.dot``, and the pass over a
-dense tensor: ``dense_stats``, ``to_dense_dev`` and with them ``error`` / ``dot`` against a ``DenseTensor``; inner products
-with a ``CPTensor``: ``cp_gram``, ``CPTensor.dot`` / ``norm`` and ``TensorTrain.dot`` against it).
+The arithmetic of the classes (``error``, ``norm``, ``dot``, ``round``, ...) is plain NumPy on the host.  Where a method
+has a device form it decides here whether to take it, and the pass itself lives beside the name of its kernel, reached
+by an import inside the method: ``tensor_gather`` (evaluation at index lists: ``gather_dev``, ``support_error``,
+``SparseTensor.dot``), ``tensor_dense`` (the pass over a dense tensor: ``dense_stats``, ``to_dense_dev`` and with them
+``error`` / ``dot`` against a ``DenseTensor``) and ``tensor_gram`` (``tt_gram``, ``cp_gram`` and the chain of a train against a
+``CPTensor``: resident ``dot`` / ``norm`` / ``error(fast=True)``).  Those modules import the classes from this one and
+never ``_host``, so a device pass has no way to a host copy.  The TT sweeps ``orthogonalize_dev`` / ``round_dev`` are
+methods without a helper layer and stay with ``TensorTrain``.
 
 Residency contract: payload arrays are treated as immutable once a tensor has been
 sketched; replace a core (``tt[i] = new``) rather than writing into it, or call
@@ -23,13 +25,12 @@ from __future__ import annotations
 
 import abc
 from functools import cached_property
-from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
+from typing import Dict, Iterable, List, Optional, Tuple, Union
 
 import numpy as np
 import numpy.typing as npt
 
 from .device import DevArray, as_dev, axpby, contract, copy_into
-from .paths import resolve, taken
 from .utils import ArrayList, TTRank, process_tt_rank, random_normal
 
 
@@ -41,118 +42,6 @@ def _same_objects(key, items) -> bool:
     """The cached device copies belong to exactly these payload objects (identity, not id(): the id of
     a collected array can be handed to a new one)."""
     return key is not None and len(key) == len(items) and all(a is b for a, b in zip(key, items))
-
-
-# ------------------------------------------------------------------ evaluation at index lists (csrc/tt_gather.hip)
-_GATHER_PANEL_BYTES = 256 << 20      # composed fallback: the two (chunk x rank) panels of a step stay below this
-
-
-def _gather_indices(idx, shape):
-    """The index argument of ``gather_dev`` as (device index matrix, row stride, row order, N, device entries or None).
-    A ``SparseTensor`` is read in place (``.T`` views through their row order); host arrays are checked against
-    ``shape`` here, before anything is uploaded."""
-    d = len(shape)
-    if isinstance(idx, SparseTensor):
-        if tuple(idx.shape) != tuple(shape):
-            raise ValueError(f"gather: index tensor of shape {idx.shape}, tensor of shape {tuple(shape)}")
-        return idx.dev_indices(), idx.nnz, tuple(idx.dev_row_order), idx.nnz, idx.dev_entries()
-    arr = np.stack(idx) if isinstance(idx, (tuple, list)) else np.asarray(idx)
-    if arr.ndim != 2 or arr.shape[0] != d:
-        raise ValueError(f"gather: {d} index rows expected, got an array of shape {arr.shape}")
-    arr = np.ascontiguousarray(arr, dtype=np.int64)
-    if arr.size and (arr.min() < 0 or (arr.max(axis=1) >= np.asarray(shape, dtype=np.int64)).any()):
-        raise IndexError(f"gather: an index lies outside the shape {tuple(shape)}")
-    return DevArray.from_host(arr, dtype=np.int64), arr.shape[1], tuple(range(d)), arr.shape[1], None
-
-
-def _tt_gather_composed(cores, dev_idx, stride, order, N, val, want_out, want_stats):
-    """The chain from ``ttsk_sparse_ttdrm_step``, mode by mode, for ranks beyond the fused kernel's cover: chunks of the
-    list small enough for the panel budget, the statistics from device products summed over the chunks in order."""
-    from . import _native as nat
-    widest = max(max(c.shape[0], c.shape[2]) for c in cores)
-    chunk = max(1, _GATHER_PANEL_BYTES // (16 * widest))
-    out = DevArray.empty((N,)) if want_out else None
-    stats = np.zeros(3) if want_stats else None
-    for lo in range(0, N, chunk):
-        m = min(chunk, N - lo)
-        v = None
-        for k, c in enumerate(cores):
-            rho, n, rhop = c.shape
-            nxt = DevArray.empty((m, rhop))
-            nat.call("ttsk_sparse_ttdrm_step", v, rho, c, n, rhop, dev_idx[order[k], lo:lo + m], m, nxt, 0)
-            v = nxt
-        if want_out:
-            copy_into(out[lo:lo + m], v.reshape(m))
-        if want_stats:
-            x = val[lo:lo + m].reshape(m, 1)
-            res = v.copy()
-            axpby(res, x, -1.0, 1.0)                                   # t - x
-            for j, (a, b) in enumerate(((x, v), (v, v), (res, res))):
-                stats[j] += float(contract("ka,kb->ab", a, b).get()[0, 0])
-    return out, stats
-
-
-def _gather_device(tensor, idx, want_out: bool, want_stats: bool):
-    """One pass of ``ttsk_tt_gather`` / ``ttsk_cp_gather`` over an index list: (DevArray (N,) or None, the three sums
-    (x . t, t . t, |t - x|^2) as a host array or None).  Nothing of the tensor or the list is downloaded."""
-    import ctypes
-    from . import _native as nat
-    dev_idx, stride, order, N, val = _gather_indices(idx, tensor.shape)
-    if want_stats and val is None:
-        raise ValueError("gather: the sums need the entries of a SparseTensor")
-    d = tensor.ndim
-    cores = [c.contiguous() for c in tensor.dev_cores()]
-    out = DevArray.empty((N,)) if want_out else None
-    stats = DevArray.empty((3,)) if want_stats else None
-    tail = (dev_idx, stride, (ctypes.c_int * d)(*order), N, val if want_stats else None, out, stats, 0)
-    cptr = nat.ptr_array(cores)
-    shape = nat.i64_array(tensor.shape)
-    if isinstance(tensor, TensorTrain):
-        ranks = nat.i64_array([c.shape[0] for c in cores] + [cores[-1].shape[2]])
-        try:
-            nat.call("ttsk_tt_gather", cptr, ranks, shape, d, *tail)
-        except nat.TtskUnsupported:
-            return _tt_gather_composed(cores, dev_idx, stride, order, N, val, want_out, want_stats)
-    else:
-        nat.call("ttsk_cp_gather", cptr, tensor.rank, shape, d, *tail)
-    return out, (stats.get() if want_stats else None)
-
-
-# ------------------------------------------------------------------ a train against a dense tensor (csrc/tt_dense_stats.hip)
-def _dense_split(shape, ranks, budget_bytes: int = _GATHER_PANEL_BYTES) -> dict:
-    """Where to cut a train of the given ``shape`` and bond ``ranks`` (d - 1 of them) for the pass over a dense tensor:
-    ``T^{<k>} = L R`` with L (M x rho) the modes before bond ``k`` and R (rho x N) the rest, ``k`` minimising
-    ``(M + N) rho`` (the numbers that must exist beside the tensor; the first such bond on a tie).  If the two panels
-    exceed ``budget_bytes`` the right group is cut into slabs of its leading mode k: for the values ``[j0, j1)`` of that
-    mode ``R_J = G_k[:, j0:j1, :] R'`` with ``R' = G_{k+1} ... G_{d-1}``, and the plan keeps
-    ``8 (M rho + (j1 - j0) N' rho + rho' N')`` under the budget (``N' = N / n_k``).  Pure arithmetic, no device call.
-    Returns ``dict(k, M, N, rho, slabs)``, ``slabs`` the list of ``(j0, j1)`` (one entry covering the mode: no slabbing)."""
-    shape = tuple(int(n) for n in shape)
-    d = len(shape)
-    rk = (1,) + tuple(int(r) for r in ranks) + (1,)
-    if d < 1 or len(rk) != d + 1 or min(shape) < 1 or min(rk) < 1:
-        raise ValueError(f"_dense_split: shape {shape} with bond ranks {tuple(ranks)}")
-    best = None
-    for k in (range(1, d) if d > 1 else (0,)):
-        M, N = _prod(shape[:k]), _prod(shape[k:])
-        cost = (M + N) * rk[k]
-        if best is None or cost < best[0]:
-            best = (cost, k, M, N)
-    cost, k, M, N = best
-    rho, n_k = rk[k], shape[k]
-    plan = dict(k=k, M=M, N=N, rho=rho, slabs=[(0, n_k)])
-    if 8 * cost <= budget_bytes:
-        return plan
-    Np = N // n_k
-    fixed, per = 8 * (M * rho + rk[k + 1] * Np), 8 * Np * rho
-    width = (budget_bytes - fixed) // per if budget_bytes > fixed else 0
-    if width < 1:
-        raise ValueError(f"_dense_split: a train of shape {shape} and ranks {rk[1:-1]} cut at bond {k} needs "
-                         f"{fixed + per} bytes of panels (L {M} x {rho}, one slice of R {rho} x {Np}, R' {rk[k + 1]} x {Np}) "
-                         f"for a single value of mode {k}: above the budget of {budget_bytes} bytes")
-    width = min(width, n_k)
-    plan["slabs"] = [(j, min(j + width, n_k)) for j in range(0, n_k, width)]
-    return plan
 
 
 def _prod(xs) -> int:
@@ -167,84 +56,76 @@ def _dense_current(dense: "DenseTensor") -> bool:
     return isinstance(dense.data, DevArray) or (dense._dev is not None and dense._dev_src is dense.data)
 
 
-def _dense_operand(X, shape):
-    """The dense argument of ``dense_stats`` as (C-contiguous DevArray, transposed): checked against ``shape`` before
-    anything touches the device.  A ``.T`` view of a contiguous buffer is returned as that buffer with ``transposed``
-    set (the caller runs its own ``.T`` against it: no copy); any other layout is copied once."""
-    if isinstance(X, np.ndarray):
-        X = DenseTensor(X)
-    if not isinstance(X, DenseTensor):
-        raise TypeError(f"dense_stats: a DenseTensor or an ndarray expected, got {type(X).__name__}")
-    if tuple(X.shape) != tuple(shape):
-        raise ValueError(f"dense_stats: dense tensor of shape {tuple(X.shape)}, tensor train of shape {tuple(shape)}")
-    if np.dtype(X.data.dtype) != np.float64:
-        raise TypeError(f"dense_stats: float64 data expected, got {X.data.dtype}")
-    arr = X.dev_data()
-    if arr.is_contiguous():
-        return arr, False
-    if arr.T.is_contiguous():
-        return arr.T, True
-    return arr.contiguous(), False
+def _on_device(t) -> bool:
+    """The condition of ``SparseTensor.dot`` for a device path: the payload lives in HBM only, or is uploaded already."""
+    return t.resident() or t._dev is not None
 
 
-def _core_chain(cores, from_right: bool) -> DevArray:
-    """The product of consecutive cores as one (r_first, n ... n, r_last) array, built from the cheap end."""
-    if from_right:
-        acc = cores[-1]
-        for c in cores[-2::-1]:
-            acc = contract("ajb,bm->ajm", c, acc.reshape(acc.shape[0], -1)).reshape(c.shape[0], -1, acc.shape[2])
-        return acc
-    acc = cores[0]
-    for c in cores[1:]:
-        acc = contract("mb,bjc->mjc", acc.reshape(-1, acc.shape[2]), c).reshape(acc.shape[0], -1, c.shape[2])
-    return acc
+def _fast_error(aa, ab, bb):
+    """``||a - b||`` from ``<a, a>``, ``<a, b>`` and ``<b, b>`` by the reference's fast formula (tensor.py:68-72), whose
+    floor is a relative error of about 1e-8.  No guard for ``aa + bb == 0``: a caller that has one keeps it."""
+    tot = aa + bb
+    return np.sqrt(tot) * np.sqrt(abs(1 - 2 * ab / tot))
 
 
-def _tt_dense_pass(tt: "TensorTrain", X: Optional[DevArray], want_out: bool, want_stats: bool):
-    """``ttsk_tt_dense_stats`` over the whole tensor: (DevArray of ``tt.shape`` or None, the four sums ``x . t``,
-    ``t . t``, ``|t - x|^2``, ``x . x`` as a host array or None).  ``X``: C-contiguous device array of ``tt.shape``, or
-    None.  Slabs (``_dense_split``) are passed in order and their sums added on the device."""
-    from . import _native as nat
-    plan = _dense_split(tt.shape, tt.rank, _GATHER_PANEL_BYTES)
-    k, M, N, rho, slabs = plan["k"], plan["M"], plan["N"], plan["rho"], plan["slabs"]
-    cores = [c.contiguous() for c in tt.dev_cores()]                # a .T train holds transposed views
-    one = lambda: DevArray.from_host(np.ones((1, 1)))
-    L = _core_chain(cores[:k], False).contiguous().reshape(M, rho) if k else one()
-    out = DevArray.empty(tt.shape) if want_out else None
-    stats = DevArray.empty((4,)) if want_stats else None
-    if len(slabs) == 1:
-        R = _core_chain(cores[k:], True).contiguous().reshape(rho, N)
-        nat.call("ttsk_tt_dense_stats", L, M, R, N, rho, X, out, stats, 0)
-    else:
-        Np = N // tt.shape[k]
-        Rp = _core_chain(cores[k + 1:], True).contiguous().reshape(-1, Np) if k + 1 < tt.ndim else one()
-        slab = lambda a: None if a is None else a.reshape(M, N)[:, j0 * Np:j1 * Np]       # its columns, rows N apart
-        for i, (j0, j1) in enumerate(slabs):
-            RJ = contract("ajb,bn->ajn", cores[k][:, j0:j1, :], Rp)
-            nat.call("ttsk_tt_dense_stats_ld", L, M, RJ, (j1 - j0) * Np, rho, slab(X), N, slab(out), N, stats,
-                     1 if i else 0, 0)
-    return out, (stats.get() if want_stats else None)
+def _error_tail(err, ref_norm, shape, relative: bool, rmse: bool):
+    """The tail of every ``error``: ``relative`` divides by ``ref_norm`` (read only then; ``inf`` against a zero
+    reference), ``rmse`` by ``sqrt(prod(shape))``."""
+    if relative:
+        if ref_norm == 0:
+            return np.inf
+        err /= ref_norm
+    if rmse:
+        err /= np.sqrt(np.prod(shape))
+    return err
 
 
-class _GatherOnDevice:
-    """``gather_dev`` / ``support_error`` of the formats with a gather kernel (TensorTrain, CPTensor)."""
+class _CoreList:
+    """What ``TensorTrain`` and ``CPTensor`` share: a list ``cores`` of payload arrays, its cached upload ``_dev`` with
+    the objects it was made from (``_dev_key``), and the gather kernels' ``gather_dev`` / ``support_error``."""
+
+    def _set_cores(self, cores: ArrayList, _dev) -> None:
+        self.cores = cores
+        self._dev = _dev
+        self._dev_key = None if _dev is None else tuple(cores)      # the objects, compared with `is`
+
+    def _dev_current(self) -> Optional[List[DevArray]]:
+        """The cached device copies if they still belong to the current core objects, None otherwise."""
+        return self._dev if self._dev is not None and _same_objects(self._dev_key, self.cores) else None
+
+    def dev_cores(self) -> List[DevArray]:
+        if self._dev_current() is None:
+            self._dev = [as_dev(c) for c in self.cores]
+            self._dev_key = tuple(self.cores)
+        return self._dev
+
+    prepare_device = dev_cores
+
+    def resident(self) -> bool:
+        """True if the cores (factor matrices) live in HBM only (as ``to_tt`` / ``round_dev`` / an MPO product leave
+        them); arithmetic on such a tensor stays on the device."""
+        return all(isinstance(c, DevArray) for c in self.cores)
+
+    def __getitem__(self, k: int):
+        return self.cores[k]
+
+    def __setitem__(self, k: int, data) -> None:
+        self.cores[k] = data
+        self.invalidate_device()
 
     def gather_dev(self, idx) -> DevArray:
         """Entries at the given multi-indices as a device array (N,): ``idx`` is a ``SparseTensor`` of this shape (its
         resident index matrix is used in place), a ``(d, N)`` array or a tuple of ``d`` arrays."""
+        from .tensor_gather import _gather_device
         return _gather_device(self, idx, True, False)[0]
 
     def support_error(self, sparse: "SparseTensor", relative: bool = False) -> float:
         """``|| self[indices] - entries ||`` over ALL nonzeros of ``sparse`` in one device pass (the figure the
         reference's scripts/frostt.py:112-116 forms on a sample of 10^4); exact where ``error(fast=True)`` has lost
         everything below 1e-8.  ``relative``: divided by ``||entries||``."""
+        from .tensor_gather import _gather_device
         err = float(np.sqrt(_gather_device(self, sparse, False, True)[1][2]))
-        if relative:
-            ref = sparse.norm()
-            if ref == 0:
-                return np.inf
-            err /= ref
-        return err
+        return _error_tail(err, sparse.norm() if relative else None, None, relative, False)
 
 
 class Tensor(abc.ABC):
@@ -287,18 +168,10 @@ class Tensor(abc.ABC):
             other = DenseTensor(other)
         ref_norm = other.norm()
         if fast:
-            mine = self.norm()
-            tot = mine**2 + ref_norm**2
-            err = np.sqrt(tot) * np.sqrt(abs(1 - 2 * self.dot(other) / tot))
+            err = _fast_error(self.norm()**2, self.dot(other), ref_norm**2)
         else:
             err = np.linalg.norm(self.to_numpy() - other.to_numpy())
-        if relative:
-            if ref_norm == 0:
-                return np.inf
-            err /= ref_norm
-        if rmse:
-            err /= np.sqrt(np.prod(self.shape))
-        return err
+        return _error_tail(err, ref_norm, self.shape, relative, rmse)
 
     def dot(self, other, reverse: bool = False) -> float:
         if isinstance(other, TensorSum):
@@ -492,7 +365,8 @@ class SparseTensor(Tensor):
         return float(np.linalg.norm(self.entries))
 
     def dot(self, other, reverse=False) -> float:
-        if isinstance(other, _GatherOnDevice) and (other.resident() or self._dev is not None):
+        if isinstance(other, _CoreList) and (other.resident() or self._dev is not None):
+            from .tensor_gather import _gather_device
             return float(_gather_device(other, self, False, True)[1][0])      # one pass, no (N,) vector
         if hasattr(other, "gather"):
             return float(np.dot(other.gather(self.indices), self.entries))
@@ -523,33 +397,21 @@ class SparseTensor(Tensor):
 
 
 # --------------------------------------------------------------------------- TT
-class TensorTrain(_GatherOnDevice, Tensor):
+class TensorTrain(_CoreList, Tensor):
     """Tensor train with cores ``(r_{k-1}, n_k, r_k)`` (reference tensor.py:294-609)."""
 
     def __init__(self, cores: ArrayList, _dev=None) -> None:
-        self.cores = cores
+        self._set_cores(cores, _dev)
         self.shape = tuple(int(C.shape[1]) for C in cores)
         self.rank = tuple(int(C.shape[0]) for C in cores[1:])
-        self._dev = _dev
-        self._dev_key = None if _dev is None else tuple(cores)      # the objects, compared with `is`
-
-    def dev_cores(self) -> List[DevArray]:
-        if self._dev is None or not _same_objects(self._dev_key, self.cores):
-            self._dev = [as_dev(c) for c in self.cores]
-            self._dev_key = tuple(self.cores)
-        return self._dev
-
-    prepare_device = dev_cores
 
     @property
     def T(self) -> "TensorTrain":
         flip = (2, 1, 0)
         cores = [c.transpose(flip) if isinstance(c, DevArray) else np.transpose(c, flip)
                  for c in self.cores[::-1]]
-        dev = None
-        if self._dev is not None and _same_objects(self._dev_key, self.cores):
-            dev = [c.transpose(flip) for c in self._dev[::-1]]
-        return TensorTrain(cores, dev)
+        dev = self._dev_current()
+        return TensorTrain(cores, None if dev is None else [c.transpose(flip) for c in dev[::-1]])
 
     def to_numpy(self):
         acc = _host(self.cores[0])
@@ -606,13 +468,6 @@ class TensorTrain(_GatherOnDevice, Tensor):
             raise ValueError(dir)
         return out
 
-    def __getitem__(self, k: int):
-        return self.cores[k]
-
-    def __setitem__(self, k: int, data) -> None:
-        self.cores[k] = data
-        self.invalidate_device()
-
     def gather(self, idx) -> npt.NDArray:
         """Entries at the given multi-indices (rows of ``idx`` are modes).  On the device (``gather_dev``) for a
         resident train or a ``SparseTensor`` of indices; host NumPy otherwise."""
@@ -630,11 +485,13 @@ class TensorTrain(_GatherOnDevice, Tensor):
         """``[sum x t, sum t^2, sum (t - x)^2, sum x^2]`` over all entries of the dense tensor ``X`` (a ``DenseTensor`` or
         an ndarray of this shape) in one device pass that reconstructs the train tile by tile and stores nothing
         (``ttsk_tt_dense_stats``).  The same bits on every call."""
+        from .tensor_dense import _dense_operand, _tt_dense_pass
         arr, transposed = _dense_operand(X, self.shape)
         return _tt_dense_pass(self.T if transposed else self, arr, False, True)[1]
 
     def to_dense_dev(self) -> "DenseTensor":
         """The full tensor as a ``DenseTensor`` whose data stay on the device (the same kernel, storing its tiles)."""
+        from .tensor_dense import _tt_dense_pass
         return DenseTensor(_tt_dense_pass(self, None, True, False)[0])
 
     def dense(self) -> "DenseTensor":
@@ -666,11 +523,6 @@ class TensorTrain(_GatherOnDevice, Tensor):
         tensor.py:442-444) has no such limit.  That is why ``error(fast=False)`` keeps the QR sweep of the direct
         sum, and only ``fast=True`` -- whose formula has that floor by definition -- takes the Gram pass."""
         return float(np.sqrt(max(self.dot(self), 0.0)))
-
-    def resident(self) -> bool:
-        """True if the cores live in HBM only (as ``to_tt`` / ``round_dev`` / an MPO product leave
-        them); arithmetic on such a train stays on the device."""
-        return all(isinstance(c, DevArray) for c in self.cores)
 
     def to_device(self) -> "TensorTrain":
         """The same train with device-resident cores (uploads host cores once)."""
@@ -840,8 +692,10 @@ class TensorTrain(_GatherOnDevice, Tensor):
         """``<self, other>``.  ``route`` is the switch of ``paths.py`` for the one path here that has a kernel and a
         composition per step, the chain against a ``CPTensor`` (``_tt_cp_dot``)."""
         if isinstance(other, TensorTrain) and self.resident() and other.resident():
+            from .tensor_gram import tt_gram
             return float(tt_gram([self], [other])[0, 0])        # one device call, or the chain where tt_gram routes it
         if isinstance(other, CPTensor) and (_on_device(self) or _on_device(other)):
+            from .tensor_gram import _tt_cp_dot
             return _tt_cp_dot(self, other, route)
         if isinstance(other, TensorTrain):
             acc = np.ones((1, 1))
@@ -868,154 +722,22 @@ class TensorTrain(_GatherOnDevice, Tensor):
         if isinstance(dense, DenseTensor) and (self.resident() or _dense_current(dense)):
             s = self.dense_stats(dense)
             ref_norm = float(np.sqrt(s[3]))
-            if fast:
-                tot = s[1] + s[3]
-                err = np.sqrt(tot) * np.sqrt(abs(1 - 2 * s[0] / tot))
-            else:
-                err = np.sqrt(s[2])
-            if relative:
-                if ref_norm == 0:
-                    return np.inf
-                err /= ref_norm
-            if rmse:
-                err /= np.sqrt(np.prod(self.shape))
-            return float(err)
+            err = _fast_error(s[1], s[0], s[3]) if fast else np.sqrt(s[2])
+            return float(_error_tail(err, ref_norm, self.shape, relative, rmse))
         if isinstance(other, TensorTrain) and fast and self.resident() and other.resident():
-            # <a, a>, <a, b>, <b, b> from one 2 x 2 Gram in the reference's formula (tensor.py:68-72; its floor is a
-            # relative error of about 1e-8)
+            # <a, a>, <a, b>, <b, b> from one 2 x 2 Gram in the reference's formula
+            from .tensor_gram import tt_gram
             G = tt_gram([self, other])
-            tot = G[0, 0] + G[1, 1]
-            err = float(np.sqrt(tot) * np.sqrt(abs(1 - 2 * G[0, 1] / tot))) if tot > 0 else 0.0
-            if relative:
-                ref_norm = float(np.sqrt(abs(G[1, 1])))
-                if ref_norm == 0:
-                    return np.inf
-                err /= ref_norm
-            if rmse:
-                err /= np.sqrt(np.prod(self.shape))
-            return float(err)
+            err = float(_fast_error(G[0, 0], G[0, 1], G[1, 1])) if G[0, 0] + G[1, 1] > 0 else 0.0
+            ref_norm = float(np.sqrt(abs(G[1, 1])))
+            return float(_error_tail(err, ref_norm, self.shape, relative, rmse))
         if isinstance(other, TensorTrain):
             err = self.add(-other).norm()
-            if relative:
-                ref = other.norm()
-                if ref == 0:
-                    return np.inf
-                err /= ref
-            if rmse:
-                err /= np.sqrt(np.prod(self.shape))
-            return err
+            return _error_tail(err, other.norm() if relative else None, self.shape, relative, rmse)   # the sweep only if asked
         return super().error(other, relative=relative, rmse=rmse, fast=fast)
 
     def __repr__(self) -> str:
         return f"<Tensor train of shape {self.shape} with rank {self.rank} at {hex(id(self))}>"
-
-
-# ------------------------------------------------------------------ Gram matrix of trains (csrc/tt_gram.hip)
-_GRAM_MAX_TRAINS = 128       # K + M of one ttsk_tt_gram call
-# The routing rule of DESIGN section 12, its constants measured on one MI355X (profiles/tt_gram_bench.json): the work
-# of the pass beyond its launches against the time of the composed chain.
-_GRAM_CUS = 256              # the chip the constants were measured on; the plan's chunks per pair follow the CU count
-_GRAM_MAX_CHUNKS = 64        # GRAM_MAX_CHUNKS of tt_gram_plan.h
-_GRAM_REDUCE_MS = 0.9e-6     # per partial a workgroup adds while it forms acc (chunks x ra x rb of them per mode)
-_GRAM_WG_FLOPS_MS = 3e7      # flops per ms of one workgroup on its run of slices
-_GRAM_CHAIN_MODE_MS = 0.045  # the chain per pair and mode: two launch-bound ``contract`` calls
-
-
-def _gram_route_ms(ra: np.ndarray, rb: np.ndarray, shape) -> Tuple[float, float]:
-    """(work of the Gram pass, time of the composed chain) in ms for the rank tables ``(K, d + 1)`` and ``(M, d + 1)``.
-    The d + 1 launches and the one read-back of the pass never cost more than the 2 d launches and the read-back of
-    one pair's chain, so only what a workgroup does in a launch can make the pass the slower path: the fused reduce
-    of the previous mode's chunk partials and the two products over its run of slices, as many rounds of either as
-    the grid (pairs x chunks) has workgroups per CU."""
-    pairs = ra.shape[0] * rb.shape[0]
-    a, b = ra.max(0).astype(np.float64), rb.max(0).astype(np.float64)
-    work, prev = 0.0, 1
-    for k, n in enumerate(shape):
-        chunks = max(1, min(-(-_GRAM_CUS // pairs), _GRAM_MAX_CHUNKS, int(n)))
-        slices = -(-int(n) // chunks)
-        flops = slices * 2.0 * (a[k] * b[k] * a[k + 1] + a[k + 1] * b[k] * b[k + 1])
-        rounds = -(-pairs * chunks // _GRAM_CUS)
-        work += rounds * (_GRAM_REDUCE_MS * prev * a[k] * b[k] + flops / _GRAM_WG_FLOPS_MS)
-        prev = chunks
-    return work, pairs * len(shape) * _GRAM_CHAIN_MODE_MS
-
-
-def _tt_dot_composed(x: TensorTrain, y: TensorTrain) -> float:
-    """<x, y> of two resident trains as a chain of 2 d ``contract`` launches: what ``tt_gram`` falls back to beyond the
-    cover of ``ttsk_tt_gram`` (a rank above 128) and where its routing rule expects the chain to be faster."""
-    acc = None
-    for a, b in zip(x.dev_cores(), y.dev_cores()):
-        t = a.reshape(a.shape[1], a.shape[2]) if acc is None else contract("ij,ika->jka", acc, a)
-        b = b.reshape(b.shape[1], b.shape[2]) if acc is None else b
-        acc = contract("ka,kb->ab", t, b) if acc is None else contract("jka,jkb->ab", t, b)
-    return float(acc.get().sum())
-
-
-def _gram_composed(As, Bs, sym: bool) -> np.ndarray:
-    G = np.empty((len(As), len(Bs)))
-    for p, a in enumerate(As):
-        for q, b in enumerate(Bs):
-            G[p, q] = G[q, p] if sym and q < p else _tt_dot_composed(a, b)
-    return G
-
-
-def _gram_block(As: Sequence[TensorTrain], Bs: Sequence[TensorTrain], sym: bool = False, route: Optional[str] = None) -> np.ndarray:
-    from . import _native as nat
-    route = resolve(route)
-    if route == "composed":
-        return _gram_composed(As, Bs, sym)
-    d = As[0].ndim
-    cores = [[c.contiguous() for c in t.dev_cores()] for t in list(As) + list(Bs)]
-    ranks = [[c.shape[0] for c in cs] + [cs[-1].shape[2]] for cs in cores]
-    K, M = len(As), len(Bs)
-    if route is None:
-        work, chain = _gram_route_ms(np.array(ranks[:K]), np.array(ranks[K:]), As[0].shape)
-        if taken(route, work, chain * (K + 1) / (2 * M) if sym else chain) == "composed":   # of a symmetric block the chain forms the upper triangle
-            return _gram_composed(As, Bs, sym)
-    out = DevArray.empty((K, M))
-    try:
-        nat.call("ttsk_tt_gram", nat.ptr_array([c for cs in cores[:K] for c in cs]), nat.i64_array([r for rk in ranks[:K] for r in rk]), K,
-                 nat.ptr_array([c for cs in cores[K:] for c in cs]), nat.i64_array([r for rk in ranks[K:] for r in rk]), M,
-                 nat.i64_array(As[0].shape), d, out, 0)
-    except nat.TtskUnsupported:
-        if route == "kernel":
-            raise
-        return _gram_composed(As, Bs, sym)
-    return out.get()
-
-
-def tt_gram(As: Sequence[TensorTrain], Bs: Optional[Sequence[TensorTrain]] = None, route: Optional[str] = None) -> np.ndarray:
-    """``G[p, q] = <As[p], Bs[q]>`` as a ``(K, M)`` array (``Bs=None``: ``As``).  The trains share one shape and have each
-    their own ranks; a host train is uploaded once (``dev_cores``).
-
-    On the device pass, ``ttsk_tt_gram``, that is one call (one launch per mode over all pairs) per block of at most
-    ``_GRAM_MAX_TRAINS`` trains, and the same bits on every call.  Both hold on that pass only: beyond the cover of the
-    entry (a rank above 128), and where the routing rule of DESIGN section 12 (``_gram_route_ms``: few pairs of large
-    ranks) expects the chain to be faster, a block is composed pair by pair from ``contract``, 2 d launches and a
-    read-back each.  With ``Bs=None`` a single block computes only its upper triangle on the composed path; lists cut
-    into several blocks (``K + M > _GRAM_MAX_TRAINS``) compute every block in full, the lower ones too.
-
-    ``route`` is the switch of ``paths.py``: None is the rule above with its fallback, ``"composed"`` the chain for every
-    block, ``"kernel"`` the pass for every block, with the entry's ``TtskUnsupported`` where it refuses."""
-    route = resolve(route)
-    As = list(As)
-    sym = Bs is None
-    Bs = As if sym else list(Bs)
-    if not As or not Bs:
-        raise ValueError("tt_gram: an empty list of trains")
-    for t in As + Bs:
-        if not isinstance(t, TensorTrain):
-            raise TypeError(f"tt_gram: {type(t).__name__} is not a TensorTrain")
-        if t.shape != As[0].shape:
-            raise ValueError(f"tt_gram: trains of shapes {As[0].shape} and {t.shape}")
-    K, M, half = len(As), len(Bs), _GRAM_MAX_TRAINS // 2
-    if K + M <= _GRAM_MAX_TRAINS:
-        return _gram_block(As, Bs, sym, route)
-    out = np.empty((K, M))
-    for p in range(0, K, half):
-        for q in range(0, M, half):
-            out[p:p + half, q:q + half] = _gram_block(As[p:p + half], Bs[q:q + half], route=route)
-    return out
 
 
 # --------------------------------------------------------------------------- sums
@@ -1075,60 +797,8 @@ class TensorSum(Tensor):
         return f"<Sum of {self.num_summands} tensors of shape {self.shape} at {hex(id(self))}>"
 
 
-# ------------------------------------------------------------------ inner products with a CP tensor (csrc/cp_gram.hip)
-def _on_device(t) -> bool:
-    """The condition of ``SparseTensor.dot`` for a device path: the payload lives in HBM only, or is uploaded already."""
-    return t.resident() or t._dev is not None
-
-
-def _cp_factor(F: DevArray) -> Tuple[DevArray, int]:
-    """A factor matrix ``(n, N)`` as ``ttsk_cp_gram`` takes it -- columns contiguous, rows a leading dimension >= N
-    apart, so a column slice goes as it is -- and that leading dimension."""
-    n, N = F.shape
-    if not ((N == 1 or F.strides[1] == 1) and (n == 1 or F.strides[0] >= N)):
-        F = F.contiguous()
-    return F, (F.strides[0] if n > 1 else N)
-
-
-def cp_gram(a: "CPTensor", b: Optional["CPTensor"] = None) -> float:
-    """``<a, b> = sum_{j, j'} prod_k (A_k^T B_k)[j, j']`` of two CP tensors of one shape (``b=None``: ``<a, a>``, of which
-    only the tiles on and above the diagonal are formed).  Host factors are uploaded once (``dev_cores``); one call of
-    ``ttsk_cp_gram``, which keeps the product over the modes in registers: no dense tensor and no ``N x M`` array, and
-    the same bits on every call."""
-    from . import _native as nat
-    sym = b is None or b is a
-    for t in (a,) if sym else (a, b):
-        if not isinstance(t, CPTensor):
-            raise TypeError(f"cp_gram: {type(t).__name__} is not a CPTensor")
-    if not sym and tuple(a.shape) != tuple(b.shape):
-        raise ValueError(f"cp_gram: CP tensors of shapes {a.shape} and {b.shape}")
-    fa = [_cp_factor(F) for F in a.dev_cores()]
-    fb = fa if sym else [_cp_factor(F) for F in b.dev_cores()]
-    out = DevArray.empty((1,))
-    nat.call("ttsk_cp_gram", nat.ptr_array([F for F, _ in fa]), nat.i64_array([ld for _, ld in fa]), a.rank,
-             nat.ptr_array([F for F, _ in fb]), nat.i64_array([ld for _, ld in fb]), a.rank if sym else b.rank,
-             nat.i64_array(a.shape), a.ndim, int(sym), out, 0)
-    return float(out.get()[0])
-
-
-def _tt_cp_dot(tt: "TensorTrain", cp: "CPTensor", route: Optional[str] = None) -> float:
-    """``<tt, cp>`` by the left-to-right chain ``L_k[j, a'] = sum_{a, i} L_{k-1}[j, a] V_k[i, j] C_k[a, i, a']``: the
-    recurrence of ``TensorTrainDRM.sketch_cp`` with the train's cores in place of the DRM's, so each mode is one
-    ``ttsk_cp_chain_step`` -- or, beyond that entry's cover (a train rank above 128) and where ``cp_fused.chain_route_ms``
-    gives the step to it, the two ``contract`` calls of ``sketch_cp``.  The last mode leaves ``(N, 1)``, which
-    ``ttsk_sum`` adds in the library's fixed order.  ``route``: the switch of ``paths.py``."""
-    from . import _native as nat
-    from .cp_fused import _chain
-    if tuple(tt.shape) != tuple(cp.shape):
-        raise ValueError(f"dot: a train of shape {tt.shape} against a CP tensor of shape {cp.shape}")
-    L = _chain(cp.dev_cores(), tt, resolve(route), 0)[-1].contiguous()
-    out = DevArray.empty((1,))
-    nat.call("ttsk_sum", L, L.size, out, 0)
-    return float(out.get()[0])
-
-
 # --------------------------------------------------------------------------- CP
-class CPTensor(_GatherOnDevice, Tensor):
+class CPTensor(_CoreList, Tensor):
     """CP format, factor matrices ``(n_k, R)`` (reference tensor.py:674-743).
 
     ``dot`` / ``norm`` against another ``CPTensor`` or a ``TensorTrain`` run on the device when either operand is there
@@ -1137,19 +807,9 @@ class CPTensor(_GatherOnDevice, Tensor):
     and ``fast=False`` keeps the reference's dense formula."""
 
     def __init__(self, cores: ArrayList, _dev=None) -> None:
-        self.cores = cores
+        self._set_cores(cores, _dev)
         self.rank = int(cores[0].shape[1])
         self.shape = tuple(int(C.shape[0]) for C in cores)
-        self._dev = _dev
-        self._dev_key = None if _dev is None else tuple(cores)      # the objects, compared with `is`
-
-    def dev_cores(self) -> List[DevArray]:
-        if self._dev is None or not _same_objects(self._dev_key, self.cores):
-            self._dev = [as_dev(c) for c in self.cores]
-            self._dev_key = tuple(self.cores)
-        return self._dev
-
-    prepare_device = dev_cores
 
     @property
     def size(self) -> int:
@@ -1157,10 +817,8 @@ class CPTensor(_GatherOnDevice, Tensor):
 
     @property
     def T(self) -> "CPTensor":
-        dev = None
-        if self._dev is not None and _same_objects(self._dev_key, self.cores):
-            dev = self._dev[::-1]
-        return CPTensor(self.cores[::-1], dev)
+        dev = self._dev_current()
+        return CPTensor(self.cores[::-1], None if dev is None else dev[::-1])
 
     def to_numpy(self):
         acc = _host(self.cores[0])
@@ -1174,17 +832,6 @@ class CPTensor(_GatherOnDevice, Tensor):
         return cls([np.random.default_rng(s).standard_normal((n, rank)) / np.sqrt(n)
                     for s, n in zip(seeds, shape)])
 
-    def __getitem__(self, k: int):
-        return self.cores[k]
-
-    def __setitem__(self, k: int, data) -> None:
-        self.cores[k] = data
-        self.invalidate_device()
-
-    def resident(self) -> bool:
-        """True if the factor matrices live in HBM only."""
-        return all(isinstance(c, DevArray) for c in self.cores)
-
     def gather(self, idx) -> npt.NDArray:
         """Entries at the given multi-indices; on the device (``gather_dev``) for device factors or a ``SparseTensor``
         of indices, host NumPy otherwise."""
@@ -1197,14 +844,17 @@ class CPTensor(_GatherOnDevice, Tensor):
 
     def norm(self) -> float:
         if _on_device(self):
+            from .tensor_gram import cp_gram
             return float(np.sqrt(abs(cp_gram(self))))
         return super().norm()
 
     def dot(self, other, reverse=False, route: Optional[str] = None) -> float:
         """``route``: the switch of ``paths.py`` for the chain against a ``TensorTrain`` (``_tt_cp_dot``)."""
         if isinstance(other, CPTensor) and (_on_device(self) or _on_device(other)):
+            from .tensor_gram import cp_gram
             return cp_gram(self, other)
         if isinstance(other, TensorTrain) and (_on_device(self) or _on_device(other)):
+            from .tensor_gram import _tt_cp_dot
             return _tt_cp_dot(other, self, route)
         return super().dot(other, reverse=reverse)
 

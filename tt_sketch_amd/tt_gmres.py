@@ -25,7 +25,8 @@ from .device import DevArray, as_dev, axpby, contract
 from .hadamard_product import HadamardProduct
 from .operator_product import OperatorProduct
 from .sketch import orthogonal_sketch, stream_sketch
-from .tensor import Tensor, TensorSum, TensorTrain, _host, tt_gram
+from .tensor import Tensor, TensorSum, TensorTrain, _host
+from .tensor_gram import tt_gram
 from .utils import ArrayList, TTRank, process_tt_rank
 
 
