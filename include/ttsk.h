@@ -441,12 +441,32 @@ int ttsk_sparse_mode_stream_u32(const int64_t *dev_idx, int64_t row_stride, cons
 /* one DRM factor of a pass: kind 0 = ones (width 1), 1 = table[flat][w] (every possible prefix sampled once:
  * ttsk_sparse_normal_table / ttsk_sparse_sign_table; allocated with one spare row: rows are fetched in 16-byte units), 2 = normals sampled in the pass: ndtri(u(hash(flat + hash(rank_min + c)
  * + seed))), 3 = sparse-sign rows sampled in the pass (fast_lazy_gaussian.pyx:121-180; whole row <= 32 entries);
- * flat = src 0: prefix, 1: suffix, 2: prefix + j * mul, 3: suffix + j * mul (the prefix / suffix one mode longer) */
+ * flat = src 0: prefix, 1: suffix, 2: prefix + j * mul, 3: suffix + j * mul (the prefix / suffix one mode longer)
+ *
+ * kind 4 = a row of a tensor-train DRM, formed in the pass: a running vector times `steps` slices of the DRM's cores,
+ *     row(e) = t(e) core[0][:, i_0(e), :] ... core[steps - 1][:, i_{steps-1}(e), rank_min : rank_min + w]
+ * with core[s] a contiguous (rank[s], n[s], rank[s + 1]) device array.  The digits: the record's flat prefix (src 0, 2) or
+ * suffix (src 1, 3) index, the first mode the fastest digit, is split into (row, i_0, i_1, ...) -- `rows` first where there
+ * is a table, then n[0], n[1], ...; with src 2 or 3 the last digit is the record's mode index j and is not part of the flat
+ * index (mul is not read).  The start: t(e) = table[row(e)][0 : rank[0]], the DRM's partial products up to the level in
+ * front of core[0] (`rows` rows of rank[0] doubles and one spare row), or, with table == NULL, the vector (1): rank[0] = 1,
+ * core[0] is the DRM's first core.  steps = 0 with a table copies columns [rank_min, rank_min + w) of the start row.  Ranks
+ * <= 32, steps <= TTSK_SG_CHAIN_MAX, rows and every n[s] below 2^31; the 32-bit entry point only (the digits of a flat index
+ * that wrapped are not those of the record).  seed, full and nnz are not read. */
+#define TTSK_SG_CHAIN_MAX 8
+typedef struct {
+    int steps;
+    uint64_t rows;                               /* rows of the start table; 0 without one */
+    const double *core[TTSK_SG_CHAIN_MAX];
+    int64_t n[TTSK_SG_CHAIN_MAX];
+    int rank[TTSK_SG_CHAIN_MAX + 1];
+} ttsk_sg_chain;
 typedef struct {
     int kind, w, rank_min, src;
     uint64_t mul, seed;
     const double *table;
     int full, nnz;          /* kind 3 only: length of the whole sign row, its +-1 entries (sparse_sign_drm.py:34-51) */
+    const ttsk_sg_chain *chain;      /* kind 4 only (host memory, read during the call); not read for any other kind */
 } ttsk_sg_factor;
 /* Psi[a, j, c] (+)= sum_{e: j_e = j} val_e A[e, a] B[e, c]   (dev_psi (wA, n, wB), zero-initialised by the caller)
  * and, with C != NULL, Omega += sum_e val_e C[e, a] B[e, c] (c_left) or sum_e val_e A[e, a] C[e, c]  (dev_omega,

@@ -211,11 +211,12 @@ static int sg_gauss_pass(const void *dev_fl, const void *dev_fr, int w32, const 
         return (size_t)v;
     }();
     SgPlan p;
-    int rc = sg_plan(A, B, C, c_left, N, n_cu, &p);
+    int rc = sg_plan(A, B, C, c_left, N, n_cu, &p, w32);
     if (rc) { set_error("%s", p.msg); return rc; }
     SgPass a{};
     a.fl = (const uint64_t *)dev_fl; a.fr = (const uint64_t *)dev_fr; a.w32 = w32; a.jj = dev_j; a.val = dev_val; a.N = N; a.n = n;
     a.chunk = p.chunk; a.c_left = c_left; a.has_om = C != nullptr; a.tcols = p.tcols; a.tab = p.tab; a.qcols = p.qcols; a.psi = dev_psi;
+    a.chain = p.chain;
     const ttsk_sg_factor *fs[3] = {A, B, C};
     for (int i = 0; i < 3; ++i) {
         SgF &F = a.f[i];
@@ -224,6 +225,11 @@ static int sg_gauss_pass(const void *dev_fl, const void *dev_fr, int w32, const 
         F.rank_min = fs[i]->rank_min; F.src = fs[i]->src; F.mul = fs[i]->mul; F.seed = fs[i]->seed; F.table = fs[i]->table;
         F.full = fs[i]->full; F.nnz = fs[i]->nnz;
         TTSK_ARG(F.kind != 1 || F.table, "ttsk_sparse_gauss_pass: table factor without a table");
+        if (F.kind == 4) {
+            a.ch[i] = p.ch[i];
+            for (int s = 0; s < p.ch[i].steps; ++s) a.core[i][s] = fs[i]->chain->core[s];
+            TTSK_ARG(!p.ch[i].has_table == !F.table, "ttsk_sparse_gauss_pass: factor %d: a chain starts at a table exactly when it states its rows", i);
+        }
         TTSK_ARG(!((F.src & 1) ? !dev_fr : !dev_fl) || F.kind == 0, "ttsk_sparse_gauss_pass: factor %d needs a flat index stream", i);
     }
 #ifdef TTSK_LAB
@@ -239,6 +245,11 @@ static int sg_gauss_pass(const void *dev_fl, const void *dev_fr, int w32, const 
     auto kern = p.NT == 1    ? sg_pass_kernel<1, 0, 32>
                 : p.T == 32  ? (p.NS == 1 ? sg_pass_kernel<2, 1, 32> : p.NS == 2 ? sg_pass_kernel<2, 2, 32> : sg_pass_kernel<2, 0, 32>)
                              : (p.NS == 1 ? sg_pass_kernel<2, 1, 16> : p.NS == 2 ? sg_pass_kernel<2, 2, 16> : sg_pass_kernel<2, 0, 16>);
+    // the same seven with the chain stage, for a pass with a chain factor
+    if (p.has_chain)
+        kern = p.NT == 1    ? sg_pass_kernel<1, 0, 32, true>
+               : p.T == 32  ? (p.NS == 1 ? sg_pass_kernel<2, 1, 32, true> : p.NS == 2 ? sg_pass_kernel<2, 2, 32, true> : sg_pass_kernel<2, 0, 32, true>)
+                            : (p.NS == 1 ? sg_pass_kernel<2, 1, 16, true> : p.NS == 2 ? sg_pass_kernel<2, 2, 16, true> : sg_pass_kernel<2, 0, 16, true>);
     if ((rc = launch(kern, dim3((unsigned)p.blocks), dim3(256), p.lds, st, a))) return rc;
     const int64_t rb = n < 4096 ? n : 4096;
     if ((rc = launch(sg_psi_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, st, a.part_psi, a.part_j, wtot, a.f[0].w, a.f[1].w, n, dev_psi))) return rc;

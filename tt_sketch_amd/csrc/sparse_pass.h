@@ -1,5 +1,6 @@
 // The pass kernel of sparse_fused.hip: one wave walks its stretch of a mode's stream tile by tile -- (1) records, (2a) table
-// rows by LDS-DMA, (2b) sampled factors, (3) tail samples, (4) products on the matrix cores -- and stores the slices of Psi
+// rows by LDS-DMA, (2b) sampled factors, (3) tail samples, (2b') rows of tensor-train DRMs by a few chain steps from a table
+// row (only in the instantiations with CH), (4) products on the matrix cores -- and stores the slices of Psi
 // inside its stretch; its first and last (shared) slices and its Omega go to per-wave partial blocks.  The launch is planned
 // by sparse_plan.h, which also owns the wave's LDS layout.
 #pragma once
@@ -10,7 +11,8 @@
 namespace ttsk {
 
 struct SgF {
-    int kind;            // 0: ones (width 1), 1: table gathered by flat index, 2: normals sampled in the pass, 3: sign rows sampled in the pass
+    int kind;            // 0: ones (width 1), 1: table gathered by flat index, 2: normals sampled in the pass, 3: sign rows sampled in the pass,
+                         // 4: rows of a tensor-train DRM formed in the pass (SgPass::ch; `table`, `units`, `rcp`: its start rows)
     int w;               // columns of the factor (<= 16 NT)
     int rank_min;
     int src;             // flat index: 0 = prefix, 1 = suffix, 2 = prefix + j * mul, 3 = suffix + j * mul
@@ -36,6 +38,9 @@ struct SgPass {
     double *part_psi;    // [wave][2][wA * wB]
     int *part_j;         // [wave][3]: first slice, last slice (= first if none), 1 if the last partial exists
     double *part_om;     // [wave][wOl * wOr]
+    int chain;           // SgPlan::chain, ch; the cores of the chain factors (read by the CH instantiations only)
+    SgPlanCh ch[3];
+    const double *core[3][SG_CHAIN_MAX];
 #ifdef TTSK_LAB
     int lab;             // TTSK_SG_LAB: 1 = no table DMA, 2 = no products, 4 = no sampling (timing experiments; results are wrong)
 #endif
@@ -168,8 +173,9 @@ struct SgSrc { const double *p; int se; bool one; };
 
 // ---- One wave's walk.  NT: 16-column matrix tiles per factor (NT = 1: every factor <= 16 columns, C4; NT = 2: up to 32, two
 // waves per SIMD).  NS: edge strips, above.  T: nonzeros per staged tile; 16 where three wide factors would leave room for ONE
-// workgroup per CU (sg_plan): the sampling stage then deals CP = 4 columns of a nonzero over the wave instead of 2.
-template <int NT, int NS, int T> struct SgWave {
+// workgroup per CU (sg_plan): the sampling stage then deals CP = 4 columns of a nonzero over the wave instead of 2.  CH: the
+// pass has a chain factor (stage 2b'); without, none of that stage's code is in the kernel.
+template <int NT, int NS, int T, bool CH> struct SgWave {
     static constexpr int CP = 64 / T;
     using Acc = std::conditional_t<(NS > 0), SgEdge<(NS > 0 ? NS : 1)>, SgTiles<NT>>;
     using Ops = typename Acc::Ops;
@@ -180,6 +186,8 @@ template <int NT, int NS, int T> struct SgWave {
     uint64_t *ro;
     int *rj, *pj;
     unsigned short *q;
+    double *cv;                                        // CH: the running vectors of the chains, the digits of the tile's nonzeros
+    uint32_t *cd;
     size_t w_id, beg, end;
     int wA, wB, wOl, wOr;
     int jfirst, cur;
@@ -194,10 +202,11 @@ template <int NT, int NS, int T> struct SgWave {
     __device__ __forceinline__ bool setup(double *lds)
     {
         lane = threadIdx.x & 63, x16 = lane & 15, kq = lane >> 4, t32 = lane & (T - 1), half = lane / T;
-        const SgLds L = sg_lds_layout(a.tcols, a.tab, a.qcols, T);
+        const SgLds L = sg_lds_layout(a.tcols, a.tab, a.qcols, T, CH ? a.chain : 0);
         double *base = lds + (size_t)(threadIdx.x >> 6) * L.total;
         tile = base + L.tile; tabs = base + L.tabs; ro = (uint64_t *)(base + L.ro); rv = base + L.rv;
         rj = (int *)(base + L.rj); q = (unsigned short *)(base + L.q);
+        if constexpr (CH) { cv = base + L.cv; cd = (uint32_t *)(base + L.cd); }
         // (finite values everywhere a product may read: the rows of nonzeros beyond the stretch are multiplied by val = 0)
         for (int i = lane; i < T * a.tcols + a.tab; i += 64) tile[i] = 0.0;
         w_id = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -236,6 +245,20 @@ template <int NT, int NS, int T> struct SgWave {
         nx_v = in ? a.val[pos] : 0.0;
     }
 
+    // (1) of the chain factors, by the lane of the nonzero: its digits (sg_chain_digits) and where its start row begins (a
+    // missing nonzero: row 0 and digits 0, as for the tables)
+    __device__ __forceinline__ void chain_records()
+    {
+#pragma unroll 1
+        for (int f = 0; f < 3; ++f) {
+            if (a.f[f].kind != 4) continue;
+            const SgPlanCh &c = a.ch[f];
+            const uint32_t flat = valid ? (uint32_t)((a.f[f].src & 1) ? my_fr : my_fl) : 0u;
+            const uint32_t row = sg_chain_digits(c, flat, (a.f[f].src & 2) != 0, valid ? (uint32_t)my_j : 0u, cd + c.doff * T + lane, T);
+            if (c.has_table) ro[f * T + lane] = (uint64_t)row * (uint64_t)(8 * c.rank[0]);
+        }
+    }
+
     // (1) the records of the tile at t0 into LDS, those of the next one on their way; true: the whole tile belongs to the
     // running slice
     __device__ __forceinline__ bool records(size_t t0)
@@ -248,6 +271,7 @@ template <int NT, int NS, int T> struct SgWave {
                 if (a.f[f].kind == 1) ro[f * T + lane] = valid ? sg_flat(a.f[f], my_fl, my_fr, my_j) * (uint64_t)(8 * a.f[f].w) : 0;
             rv[lane] = nx_v;
             rj[lane] = my_j;
+            if constexpr (CH) chain_records();
         }
         const bool one_slice = __ballot(valid && my_j != cur) == 0ull;
         rec_load(t0 + T);
@@ -266,11 +290,12 @@ template <int NT, int NS, int T> struct SgWave {
 #pragma unroll 1
         for (int f = 0; f < 3; ++f) {
             const SgF &F = a.f[f];
-            if (F.kind != 1) continue;
+            const bool start = CH && F.kind == 4 && a.ch[f].has_table;       // the start rows of a chain factor, as a table of rank[0] columns
+            if (F.kind != 1 && !start) continue;
 #ifdef TTSK_LAB
             if (a.lab & 1) continue;
 #endif
-            double *blk = tabs + a.off[f];
+            double *blk = tabs + (start ? a.ch[f].toff : a.off[f]);
 #pragma unroll 1
             for (int i0 = 0; i0 < T * F.units; i0 += 64) {
                 const int i = i0 + lane;
@@ -352,6 +377,61 @@ template <int NT, int NS, int T> struct SgWave {
                 const int slot = q[i + lane];
                 tile[slot] = sg_ndtri(tile[slot]);
             }
+    }
+
+    // (2b') the rows of a chain factor, as tt_gather_kernel walks a train: the wave in groups of G = 16 lanes (32 beyond rank
+    // 16), a group takes the tile's nonzeros grp, grp + 64 / G, ... one after the other.  The running vector of a nonzero
+    // starts as its row of the start table (landed with the table blocks; without a table: the vector (1)) and alternates
+    // between the group's two LDS vectors; in a step lane b forms out[b] = sum_a v[a] D[a, i, b], a ascending, every a one
+    // contiguous row of the core through L2.  The last step keeps the columns [lo, lo + w) and writes them where the products
+    // read the factor.
+    __device__ __forceinline__ void chain_factor(int f)
+    {
+        const SgF &F = a.f[f];
+        const SgPlanCh &c = a.ch[f];
+        const int G = 1 << c.gsh, lg = lane & (G - 1), grp = lane >> c.gsh, groups = 64 >> c.gsh;
+        double *const va = cv + grp * 2 * SG_CHAIN_RANK, *const vb = va + SG_CHAIN_RANK;
+        const uint32_t *dg = cd + c.doff * T;
+#pragma unroll 1
+        for (int e = grp; e < T; e += groups) {                 // T / groups trips in every group
+            double *row = tile + e * a.tcols + a.off[f];
+            if (c.has_table) {
+                const double *src = tabs + c.toff + e * 2 * F.units;
+                for (int b = lg; b < c.rank[0]; b += G) va[b] = src[b];
+            } else if (lg == 0) {
+                va[0] = 1.0;
+            }
+            double *cur = va, *nxt = vb;
+#pragma unroll 1
+            for (int s = 0; s < c.steps; ++s) {
+                wave_lds_sync();
+                const int r = c.rank[s], rn = c.rank[s + 1];
+                const bool last = s == c.steps - 1;
+                const int64_t as = (int64_t)c.n[s] * rn;
+                const double *cp = a.core[f][s] + (int64_t)dg[s * T + e] * rn + (last ? c.lo : 0);
+                const int wn = last ? F.w : rn;
+                double *out = last ? row : nxt;
+                for (int b = lg; b < wn; b += G) {
+                    const double *cb = cp + b;
+                    double acc = 0.0;
+#pragma unroll 4
+                    for (int k = 0; k < r; ++k) acc = fma(cur[k], cb[k * as], acc);
+                    out[b] = acc;
+                }
+                double *sw = cur; cur = nxt; nxt = sw;
+            }
+            wave_lds_sync();
+            if (c.steps == 0)
+                for (int b = lg; b < F.w; b += G) row[b] = va[c.lo + b];
+            wave_lds_sync();                                    // the next nonzero of the group overwrites the vectors
+        }
+    }
+
+    __device__ __forceinline__ void chain()
+    {
+#pragma unroll 1
+        for (int f = 0; f < 3; ++f)
+            if (a.f[f].kind == 4) chain_factor(f);
     }
 
     // store the finished slice k: the wave's first slice and (final) its last one go to the partial blocks
@@ -470,7 +550,7 @@ template <int NT, int NS, int T> struct SgWave {
     }
 };
 
-template <int NT, int NS, int T>
+template <int NT, int NS, int T, bool CH = false>
 __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void sg_pass_kernel(SgPass a)
 {
     static_assert(NS == 0 || NT == 2, "edge strips belong to the wide instantiation");
@@ -484,7 +564,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void sg_pass_kernel(SgPass a)
         salt[f][c] = mix64((uint64_t)((a.f[f].kind == 3 ? 0 : a.f[f].rank_min) + c)) + a.f[f].seed;
     }
     __syncthreads();                                   // the only workgroup barrier: waves run free from here
-    SgWave<NT, NS, T> w{a, salt};
+    SgWave<NT, NS, T, CH> w{a, salt};
     if (!w.setup(sg_lds)) return;
     for (size_t t0 = w.beg; t0 < w.end; t0 += T) {
         const bool one_slice = w.records(t0);          // (1)
@@ -493,6 +573,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void sg_pass_kernel(SgPass a)
         w.drain_tails(qn);                             // (3)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the table blocks have landed
         __builtin_amdgcn_wave_barrier();
+        if constexpr (CH) w.chain();                   // (2b'): the start rows are among the table blocks
 #ifdef TTSK_LAB
         if (a.lab & 2) continue;
 #endif

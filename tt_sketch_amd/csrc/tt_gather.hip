@@ -36,15 +36,6 @@ struct CPFactors {
     int rank;
 };
 
-// Lanes of one wave hand data to each other through LDS: the hardware runs a wave's LDS accesses in order, this keeps the
-// compiler from reordering them.
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // indices of the lanes' own tuples (e: the lane's tuple, `own`: it has one): sidx[k * 64 + lane]; no tuple, or one beyond
 // N, reads as index 0 (valid in every mode), its value is never stored
 __device__ __forceinline__ void stage_indices(const GatherIdx &ix, size_t e, bool own, size_t N, int lane, int *sidx)

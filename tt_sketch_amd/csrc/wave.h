@@ -42,6 +42,15 @@ __device__ __forceinline__ double wave_sum(double x)
     return x;
 }
 
+// Lanes of one wave hand data to each other through LDS: the hardware runs a wave's LDS accesses in order, this keeps the
+// compiler from reordering them.
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // Workgroup barrier for data handed over through LDS.
 __device__ __forceinline__ void lds_barrier()
 {

@@ -44,11 +44,12 @@ def drm_pair(shape, left_drm, right_drm, *, kinds=(TensorTrainDRM,), need_left: 
     ``tt_fused.try_orth_sketch``              TensorTrainDRM  orthogonal  yes    no         no
     ``tt_fused.try_orth_sketch_batch``        TensorTrainDRM  orthogonal  yes    no         no
     ``sketch.stream_sketch_batch``            TensorTrainDRM  yes         no     yes        yes
-    ``sparse_fused.try_sparse_gauss_sketch``  the two hashed  yes         no     yes        yes
+    ``sparse_fused.try_sparse_gauss_sketch``  hashed, train   yes         no     yes        yes
     ========================================  ==============  ==========  =====  =========  ===============
 
-    ``stream_sketch_batch`` leaves the count of cores to ``TTSketchPlan``; the sparse DRMs have no cores, and that path
-    tests the number of modes with its other limits."""
+    ``stream_sketch_batch`` leaves the count of cores to ``TTSketchPlan``.  The sparse path takes SparseGaussianDRM,
+    SparseSignDRM and TensorTrainDRM in any pairing: the hashed DRMs have no cores, so it asks for no count here and tests
+    the number of modes, and ``d - 1`` cores of a train, with its other limits."""
     # (plain tests, no generator expressions: this runs on every public sketch call)
     if type(right_drm) not in kinds or not right_drm.transpose:
         return False
@@ -74,7 +75,8 @@ def drm_pair(shape, left_drm, right_drm, *, kinds=(TensorTrainDRM,), need_left: 
 
 # ------------------------------------------------------------------ kernel or composition
 # Where a path has both a kernel and a composition from ``contract`` calls, its entry takes ``route=``: None is the path's
-# cost rule (``cp_fused.chain_route_ms``, ``operator_product.route_ms``, ``hadamard_product.route_ms``, ``tensor_gram._gram_route_ms``), ``"composed"`` never
+# cost rule (``cp_fused.chain_route_ms``, ``operator_product.route_ms``, ``hadamard_product.route_ms``, ``tensor_gram._gram_route_ms``,
+# ``sparse_fused.chain_route_ms``), ``"composed"`` never
 # calls the library entry, ``"kernel"`` calls it and lets its ``TtskUnsupported`` propagate, so that a test or a benchmark
 # knows which code it ran.  ``forced`` sets the route of every call made without the keyword.
 ROUTES = (None, "kernel", "composed")
