@@ -12,7 +12,10 @@ For every (A, A2) of the list: the verdict of chain_fused_plan, and where chain_
   - a unit whose row lies beyond A holds row A - 1, one whose second column would lie beyond A2 holds columns 0, 1
     (restated here with a division, not the kernel's reciprocal);
   - a slice is a whole number of 64-unit pieces and the last piece of the last slice ends where the allocation ends
-    (every store of the driver's pack loop is bounds-checked)."""
+    (every store of the driver's pack loop is bounds-checked).
+
+A second driver does the same for the image chain_wide_kernel's loader gathers with e_image_unit_from: a chunk of rows from
+a row origin on, and odd A2 (WIDE_CASES below)."""
 import os
 import shutil
 import subprocess
@@ -127,20 +130,133 @@ int main(int argc, char **argv)
 """
 
 
-@pytest.fixture(scope="module")
-def report(tmp_path_factory):
+# The loader of chain_wide_kernel (chain_stages.h: chain_e_fill_gather<true>) builds the image of a CHUNK of rows [a0, a0 + ac)
+# of E_k with e_image_unit_from: a row origin, and for odd A2 the unit behind a row's last column reaching into the next
+# slice -- in the last slice it holds columns 0, 1 instead and column A2 - 1 is patched in element by element.
+# (A, A2, a0, ac); each with n = 1 (every slice is the last one) and n = 2 (an ordinary odd slice, then the last one).
+WIDE_CASES = ((20, 7, 0, 20), (57, 21, 40, 20), (33, 10, 16, 24))
+
+DRIVER_WIDE = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+#include "chain_plan.h"
+using namespace ttsk;
+
+#define REQUIRE(c) do { if (!(c)) { printf("FAIL %s line %d (A=%d A2=%d a0=%d ac=%d n=%d)\n", #c, __LINE__, A, A2, a0, ac, n); return 1; } } while (0)
+
+int main(int argc, char **argv)
+{
+    for (int i = 1; i + 4 < argc; i += 5) {
+        const int A = atoi(argv[i]), A2 = atoi(argv[i + 1]), a0 = atoi(argv[i + 2]), ac = atoi(argv[i + 3]), n = atoi(argv[i + 4]);
+        // the chunk structure chain_wide_plan picks for `ac` rows, its image and the output structure
+        int ci = -1;
+        for (int c = 0; c < 7 && ci < 0; ++c)
+            if (16 * CW_NQ[c] + 4 * CW_SQ[c] >= (ac + 3) / 4 * 4) ci = c;
+        REQUIRE(ci >= 0);
+        const int nq = CW_NQ[ci], sq = CW_SQ[ci], AP = 16 * nq + 4 * sq, KB2 = 4 * nq + sq;
+        const int A2P = A2 + (A2 & 1), eunits = (int)cdiv((int64_t)2 * (AP / 4) * A2P, 64) * 64, NI = eunits >> 6;
+        int nn, sn;
+        chain_tile_split(A2, nn, sn);
+        const int cnt = A - a0 < ac ? A - a0 : ac;
+        REQUIRE(a0 >= 0 && a0 < A && cnt >= 1 && AP >= cnt && eunits < (1 << 16));
+        std::vector<double> E((size_t)A * n * A2);
+        for (size_t e = 0; e < E.size(); ++e) E[e] = (double)(e + 1);
+        auto el = [&](int a, int k, int a2) { return E.at(((size_t)a * n + k) * A2 + a2); };
+        const uint32_t inv = e_image_inv(A2P);
+        const int64_t rowstride = (int64_t)n * A2;
+        long checked = 0, spilled = 0, patched = 0;
+        for (int k = 0; k < n; ++k) {
+            std::vector<double> img((size_t)eunits * 2, -1.0);
+            const bool tail = (A2 & 1) && k == n - 1;
+            // the loader's loop: unit U = 16 bytes from E_k + row rowstride + col, every read inside the core
+            for (int m = 0; m < NI; ++m)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int U = 64 * m + lane;
+                    const EUnit un = e_image_unit_from((uint32_t)U, inv, a0, A, A2, A2P, tail);
+                    REQUIRE(un.row >= a0 && un.row < A && un.col >= 0 && un.col < A2 && (un.col & 1) == 0);
+                    const size_t src = (size_t)k * A2 + (size_t)(un.row * rowstride) + un.col;
+                    img.at((size_t)U * 2) = E.at(src);
+                    img.at((size_t)U * 2 + 1) = E.at(src + 1);                      // odd A2, not the last slice: may be E_{k+1}[row][0]
+                    if (un.col + 1 == A2) { REQUIRE((A2 & 1) && !tail); ++spilled; }
+                    // restated with a division
+                    const int sec = U / A2P, u = U % A2P, row = a0 + 2 * sec + (u & 1), col = 2 * (u >> 1);
+                    REQUIRE(un.row == (row < A ? row : A - 1));
+                    REQUIRE(un.col == ((col + 1 < A2 || ((A2 & 1) && !tail && col < A2)) ? col : 0));
+                }
+            if (tail)
+                for (int lane = 0; lane < AP; ++lane, ++patched) {
+                    const int row = a0 + lane < A ? a0 + lane : A - 1;
+                    img.at(e_image_at(lane, A2 - 1, A2P)) = el(row, k, A2 - 1);
+                }
+            for (double v : img) REQUIRE(v >= 1.0);
+            // phase B: k-block kap of the chunk's T meets rows a0 + 4 kap + kq of E_k (beyond the chunk: zeros of T meet
+            // whatever finite row the image holds -- the next rows of E, clamped to A - 1)
+            for (int kap = 0; kap < KB2; ++kap)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int x16 = lane & 15, kq = lane >> 4, a = 4 * kap + kq, row = a0 + a < A ? a0 + a : A - 1;
+                    for (int t = 0; t < nn; ++t) {
+                        const int col = 16 * t + x16, pos = e_frag_lane(x16, kq, A2P) + kap * 4 * A2P + 32 * t;
+                        if (col >= A2) continue;                            // a zero-padded column tile: never stored
+                        REQUIRE(pos >= 0 && pos < 2 * eunits && img[pos] == el(row, k, col));
+                        ++checked;
+                    }
+                    for (int q = 0; q < sn; ++q) {
+                        const int es_col = 16 * nn + (x16 & 3), col = es_col + 4 * q;
+                        const int pos = e_strip_lane(kq, A2P) + e_image_at(0, es_col, A2P) + kap * 4 * A2P + 8 * q;
+                        REQUIRE(pos >= 0 && pos < 2 * eunits);              // read even where the column is never stored
+                        if (col >= A2) continue;
+                        REQUIRE(img[pos] == el(row, k, col));
+                        ++checked;
+                    }
+                }
+            for (int a = 0; a < cnt; ++a)
+                for (int a2 = 0; a2 < A2; ++a2, ++checked) REQUIRE(img[e_image_at(a, a2, A2P)] == el(a0 + a, k, a2));
+        }
+        printf("A=%d A2=%d a0=%d ac=%d n=%d cnt=%d AP=%d eunits=%d checked=%ld spilled=%ld patched=%ld\n", A, A2, a0, ac, n, cnt, AP,
+               eunits, checked, spilled, patched);
+    }
+    return 0;
+}
+"""
+
+
+def _run_driver(tmp_path_factory, name, text, args):
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if cxx is None:
         pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("chain_pack")
+    d = tmp_path_factory.mktemp(name)
     src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
+    src.write_text(text)
     subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
-    args = [str(x) for pair in RANKS for x in pair]
-    r = subprocess.run([str(exe)] + args, capture_output=True, text=True)
+    r = subprocess.run([str(exe)] + [str(x) for x in args], capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     return [dict(x.split("=") for x in line.split()) for line in r.stdout.splitlines()]
+
+
+@pytest.fixture(scope="module")
+def report(tmp_path_factory):
+    return _run_driver(tmp_path_factory, "chain_pack", DRIVER, [x for pair in RANKS for x in pair])
+
+
+@pytest.fixture(scope="module")
+def wide_report(tmp_path_factory):
+    return _run_driver(tmp_path_factory, "chain_wide_image", DRIVER_WIDE, [x for c in WIDE_CASES for n in (1, 2) for x in c + (n,)])
+
+
+def test_wide_loader_image_holds_what_phase_b_reads(wide_report):
+    """every case ran, every element of the chunk and every fragment read was compared, and the two odd-A2 rules occurred
+    where they must: the unit reaching into the next slice only in a slice that is not the last, the patch only in the last"""
+    assert [tuple(int(r[k]) for k in ("A", "A2", "a0", "ac", "n")) for r in wide_report] == [c + (n,) for c in WIDE_CASES for n in (1, 2)]
+    for r in wide_report:
+        A2, n, cnt, AP = int(r["A2"]), int(r["n"]), int(r["cnt"]), int(r["AP"])
+        assert int(r["checked"]) >= n * (cnt * A2 + AP * A2), r
+        assert int(r["patched"]) == (AP if A2 & 1 else 0), r
+        # one such unit per row of the image and slice that is not the last (the padding of the last 1 KB piece may add some)
+        assert int(r["spilled"]) >= AP * (n - 1) if A2 & 1 else int(r["spilled"]) == 0, r
+        assert n > 1 or int(r["spilled"]) == 0, r
+    assert [int(r["cnt"]) for r in wide_report] == [20, 20, 17, 17, 17, 17]
 
 
 def test_every_rank_pair_was_checked(report):

@@ -25,9 +25,11 @@
 //
 // Partial tiles (rank 100 = 6 x 16 + 4, rank 50 = 3 x 16 + 2) are 4-wide strips computed with
 // v_mfma_f64_4x4x4 (4 blocks): 16 instead of 64 cycles of the matrix pipe.
+//
+// Two workgroup-level stages -- the XCD mapping and the gathering E loader -- are defined in chain_stages.h, for this
+// kernel and chain_wide.h; the launchers' slab request and slab reduce at the end of this file, for all three.
 #pragma once
-#include "chain_plan.h"
-#include "skinny.h"
+#include "chain_stages.h"
 
 namespace ttsk {
 
@@ -375,17 +377,8 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 * OCC : 1) void chain_step_k
     double *El = cf_lds + a.ebase;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     constexpr int NT = 64 * NWV;
-    int prob, g;
-    if (a.xcd_map) {
-        // blocks b and b + 8 share an XCD: deal the slice ranges g over the XCDs, all problems of a
-        // range to the same one (they read the same E_k)
-        const int gpx = a.wpp >> 3, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        g = xcd * gpx + j % gpx;
-        prob = j / gpx;
-    } else {
-        prob = blockIdx.x / a.wpp;
-        g = blockIdx.x - prob * a.wpp;
-    }
+    int prob, g;                                       // the unit of a problem: its slice range g
+    chain_block_unit(a.xcd_map, a.wpp, prob, g);
     const int k_beg = (int)((int64_t)g * a.n / a.wpp), k_end = (int)((int64_t)(g + 1) * a.n / a.wpp);
     // k-blocks of phase A, padded to whole runs of UNR (the padded ones meet zero rows of the W image)
     const int KB1 = ((a.K1 + 3) / 4 + UNR - 1) / UNR * UNR;
@@ -426,11 +419,7 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 * OCC : 1) void chain_step_k
         nl = a.nload;
     }
     if (NWV == 8 ? w == 7 : __builtin_amdgcn_readfirstlane(pc >> 16) == CD_NONE) {
-        // ---- loader: E_k -> El in 16-byte units.  Unit u of section sec (rows 2 sec, 2 sec + 1) is
-        // columns (2 (u >> 1), + 1) of row 2 sec + (u & 1); lanes (kq in {0, 1}, x) of a fragment read 16
-        // consecutive units.  Rows beyond A repeat row A - 1: they meet exact zeros of T.
-        // (A rolled loop: unrolled, the 80 LDS destinations are hoisted into 80 scalar registers and the
-        // whole kernel starts spilling them.)
+        // ---- loader: E_k -> El in 16-byte units, gathered from the core (chain_e_fill_gather) or copied from its packed image.
         // levelled workgroups: the loader is the youngest of three waves on its SIMD and the arbiter serves the oldest
         // first -- left at that it issues one load per ~300 cycles and E_k lands after phase A is over
         if constexpr (NWV != 8) __builtin_amdgcn_s_setprio(3);
@@ -444,15 +433,8 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 * OCC : 1) void chain_step_k
         const uint32_t inv = e_image_inv(A2P);
         const int64_t rowstride = (int64_t)a.n * a.A2;
         const int ebuf = a.eunits * 2;                 // doubles per E image
-        auto fill_gather = [&](int k) {
-            const double *Ek = a.E + (int64_t)k * a.A2;
-            double *dst = El + (EBUF == 2 ? (k & 1) * ebuf : 0);
-#pragma unroll 2
-            for (int m = li; m < NI; m += nl) {
-                const EUnit un = e_image_unit(64u * (uint32_t)m + (uint32_t)lane, inv, a.A, a.A2, A2P);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(Ek + un.row * rowstride + un.col),
-                                                 (__attribute__((address_space(3))) void *)(dst + m * 128), 16, 0, 0);
-            }
+        auto fill_gather = [&](int k) {                // (A2 is even here: no odd-rank rule)
+            chain_e_fill_gather<false>(a, El + (EBUF == 2 ? (k & 1) * ebuf : 0), k, 0, A2P, inv, rowstride, NI, li, nl, lane);
         };
         // A packed core (chain_pack.hip) holds the image itself: piece m of slice k is 1 KB at Epk + (k eunits + 64 m) units,
         // a wave-uniform base that moves by a constant per instruction under the lane's fixed 16 bytes -- no division,
@@ -520,6 +502,18 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 * OCC : 1) void chain_step_k
         else if (kind == CD_ROWS4)
             cf_rows4<NQF, STRQ, NNF, STRN, D, WT, EBUF, UNR, APC>(a, Wl, El, tile, prob, g, k_beg, k_end, KB1, w, lane);
     }
+}
+
+// What the three launchers (chain_fused.hip, chain_wide.hip, chain_sum.hip) do around their kernel with the plan's
+// ChainLaunch: request the slab of partial results ...
+inline double *chain_slab_request(int stream, const ChainLaunch &l) { return (double *)scratch(stream, SCRATCH_GEMM, (size_t)l.slab * 8 + 64); }
+
+// ... and reduce it into Out[b] (J x A2 contiguous)
+inline int chain_slab_reduce(hipStream_t st, const double *slab, const ChainLaunch &l, const ChainStepArgs &c)
+{
+    ReduceOut ro{};
+    for (int b = 0; b < c.nb; ++b) ro.C[b] = c.Out[b];
+    return launch_r_reduce(st, slab, l.red_chunks, l.red_m, l.red_n, 1, (int64_t)c.J, ro, c.nb, (int64_t)c.A2, (int64_t)1, 1.0, 0);
 }
 
 // 1 = launched (the slab reduce included), 0 = shape not covered, < 0 = error

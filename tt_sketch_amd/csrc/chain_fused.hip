@@ -29,7 +29,7 @@ int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool for
     ChainFusedPlan p;
     if (!chain_fused_plan(c, n_cu, force, p)) return 0;
     ChainStep &a = p.a;
-    a.slab = (double *)scratch(stream, SCRATCH_GEMM, (size_t)p.l.slab * 8 + 64);
+    a.slab = chain_slab_request(stream, p.l);
     if (!a.slab) return TTSK_ERR_HIP;
     a.Epk = drm_packed_lookup(c.E, c.A, c.n, c.A2, a.A2P, a.eunits);
     // flops of BOTH products of the step (the pair this kernel replaces), reduce launch inside the bracket; the name as
@@ -65,11 +65,7 @@ int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool for
                         r[3] - t0, r[4] - t0);
             }
     }
-    if (rc == TTSK_OK) {
-        ReduceOut ro{};
-        for (int b = 0; b < c.nb; ++b) ro.C[b] = c.Out[b];
-        rc = launch_r_reduce(st, a.slab, p.l.red_chunks, p.l.red_m, p.l.red_n, 1, (int64_t)c.J, ro, c.nb, (int64_t)c.A2, (int64_t)1, 1.0, 0);
-    }
+    if (rc == TTSK_OK) rc = chain_slab_reduce(st, a.slab, p.l, c);
     return rc == TTSK_OK ? 1 : (rc == 1 ? 0 : rc);
 }
 

@@ -2,7 +2,9 @@
 // the cover tests, the LDS plan, the wave tables, the grid rule, the proofs that every 32-bit byte offset fits, the slab
 // of partial results and its closing reduce.  A plan holds the filled kernel-argument struct (all but `slab`, `Epk` and the
 // lab-only `diag` / `stamps`), the instantiation the launcher picks and the launch figures; the launchers
-// (chain_fused.hip, chain_wide.hip, chain_sum.hip) only carry it out.
+// (chain_fused.hip, chain_wide.hip, chain_sum.hip) only carry it out.  What the three plans share -- the common refusals
+// with the copy of the pointer tables, the common scalar fields, the launch figures -- is chain_plan_tables,
+// chain_plan_scalars and chain_plan_launch; the E image all three kernels read is e_image_*.
 //
 // Plain C++: no HIP types, so that the plans are compiled and checked by the host compiler alone
 // (tests/test_chain_plan.py, tests/test_chain_deal.py) before any kernel reads them.  Pointers are tested for alignment
@@ -86,6 +88,16 @@ constexpr EUnit e_image_unit(uint32_t U, uint32_t inv, int A, int A2, int A2P)
     int col = (int)(2 * (u >> 1));
     col = col + 1 < A2 ? col : 0;
     return EUnit{row, col};
+}
+
+// The same for an image that begins at row a0 of E (a chunk of the DRM rank, chain_wide_kernel) and for odd A2, where rows
+// are only 8-byte aligned: the unit behind the last column of a row then takes the first element of the next slice along
+// (it meets an output column that is never stored) -- except in the last slice (`last`), where it would reach past the
+// core: there it holds columns 0, 1 and column A2 - 1 is patched in afterwards, element by element.
+constexpr EUnit e_image_unit_from(uint32_t U, uint32_t inv, int a0, int A, int A2, int A2P, bool last)
+{
+    const EUnit un = e_image_unit(U, inv, A - a0, A2 + (((A2 & 1) && !last) ? 1 : 0), A2P);
+    return EUnit{a0 + un.row, un.col};
 }
 
 // The inverse view: the offset (doubles) of E[a][a2] in the image ...
@@ -257,22 +269,56 @@ inline void chain_phase_a_runs(int K1, int &unr, int &KB1)
     KB1 = unr == 25 ? pad25 : pad5;
 }
 
+// ---- what the three plans share ---------------------------------------------------------------------------------------
+// The refusals: the batch size, negative strides, rows of W shorter than A, a core that is not 8-byte aligned -- and, as the
+// cores are visited for that anyway, the copy of the pointer tables (T: the kernel's table, or nullptr for none).
+inline bool chain_plan_tables(const ChainStepArgs &c, const double **W, const double **X, double **T)
+{
+    if (c.nb < 1 || c.nb > SK_MAXB) return false;
+    if (c.x_j < 0 || c.x_k < 0 || c.x_c < 0 || c.w_c < c.A) return false;
+    for (int b = 0; b < c.nb; ++b) {
+        if ((uintptr_t)c.X[b] & 7) return false;
+        W[b] = c.W[b];
+        X[b] = c.X[b];
+        if (T) T[b] = c.T[b];
+    }
+    return true;
+}
+
+// the extents and strides every kernel-argument struct carries under the same names
+template <class KA>
+inline void chain_plan_scalars(const ChainStepArgs &c, KA &a)
+{
+    a.nb = c.nb; a.n = c.n; a.K1 = c.K1; a.A = c.A; a.A2 = c.A2; a.J = c.J;
+    a.w_c = c.w_c; a.x_j = c.x_j; a.x_k = c.x_k; a.x_c = c.x_c; a.x_extent = c.x_extent;
+    a.E = c.E;
+}
+
+// red_chunks partial results per problem
+inline ChainLaunch chain_plan_launch(const ChainStepArgs &c, size_t lds, int grid, int red_chunks)
+{
+    ChainLaunch l{};
+    l.lds = lds; l.grid = grid;
+    l.slab = (int64_t)c.nb * red_chunks * c.J * c.A2;
+    l.red_chunks = red_chunks; l.red_m = c.J; l.red_n = c.A2;
+    l.flops = 2.0 * c.nb * (double)c.n * c.J * ((double)c.K1 * c.A + (double)c.A * c.A2);
+    return l;
+}
+
 // ---- chain_step_kernel: 1 = covered, 0 = not -------------------------------------------------------------------------
 inline int chain_fused_plan(const ChainStepArgs &c, int n_cu, bool force, ChainFusedPlan &p)
 {
-    if (c.nb < 1 || c.nb > SK_MAXB) return 0;
     if (c.J < 1 || c.J > 112 || c.K1 < 1 || c.K1 > 128 || c.A < 4 || c.A2 < 4 || c.n < 1) return 0;
     if ((c.A2 & 1) || ((uintptr_t)c.E & 15)) return 0;                 // 16-byte units of E rows
     int nq, sq, nn, sn;
     chain_tile_split(c.A, nq, sq);
     chain_tile_split(c.A2, nn, sn);
     if (nq != nn || sq != sn || nq + (sq ? 1 : 0) > 7 || nq < 1) return 0;   // one instantiation per (tiles, strips)
-    if (c.x_j < 0 || c.x_k < 0 || c.x_c < 0 || c.w_c < c.A) return 0;
     p = ChainFusedPlan{};
     ChainStep &a = p.a;
-    a.nb = c.nb; a.n = c.n; a.K1 = c.K1; a.A = c.A; a.A2 = c.A2; a.J = c.J;
-    a.w_c = c.w_c; a.x_j = c.x_j; a.x_k = c.x_k; a.x_c = c.x_c; a.x_extent = c.x_extent;
-    a.E = c.E;
+    const bool wt = c.T != nullptr;
+    if (!chain_plan_tables(c, a.W, a.X, wt ? a.T : nullptr)) return 0;
+    chain_plan_scalars(c, a);
     int unr, KB1;
     chain_phase_a_runs(c.K1, unr, KB1);
     const int KB2 = nq * 4 + sq;                                         // k-blocks of phase B
@@ -292,7 +338,6 @@ inline int chain_fused_plan(const ChainStepArgs &c, int n_cu, bool force, ChainF
     // 32-bit byte offsets: the X walk (incl. the masked prefetch one slice past the end) and T
     if ((c.x_extent + c.x_k + 132 * c.x_c) * 8 >= (1ll << 32) - 64) return 0;
     if ((int64_t)c.A * c.n * c.A2 * 8 >= (1ll << 32) - 64) return 0;
-    const bool wt = c.T != nullptr;
     a.t_extent = (int64_t)c.A * c.n * c.J;
     if (wt && (a.t_extent + (int64_t)16 * c.n * c.J) * 8 >= (1ll << 32) - 64) return 0;
     // geometry: one workgroup per CU (the LDS images fill it), each a contiguous range of slices
@@ -317,18 +362,8 @@ inline int chain_fused_plan(const ChainStepArgs &c, int n_cu, bool force, ChainF
         }
     }
     a.xcd_map = (wpp % 8 == 0 && wpp >= 8) ? 1 : 0;
-    for (int b = 0; b < c.nb; ++b) {
-        if ((uintptr_t)c.X[b] & 7) return 0;
-        a.W[b] = c.W[b];
-        a.X[b] = c.X[b];
-        a.T[b] = wt ? c.T[b] : nullptr;
-    }
-    const int64_t nslab = (int64_t)c.nb * wpp;
     p.nq = nq; p.sq = sq; p.wt = wt; p.ebuf = ebuf; p.unr = unr; p.waves = deal.waves;
-    p.l.lds = lds; p.l.grid = (int)nslab;
-    p.l.slab = nslab * c.J * c.A2;
-    p.l.red_chunks = wpp; p.l.red_m = c.J; p.l.red_n = c.A2;
-    p.l.flops = 2.0 * c.nb * (double)c.n * c.J * ((double)c.K1 * c.A + (double)c.A * c.A2);
+    p.l = chain_plan_launch(c, lds, c.nb * wpp, wpp);
     return 1;
 }
 
@@ -375,9 +410,8 @@ inline bool cw_wave_table(int NT, bool mt2_ok, int tpw, ChainWide &a, bool &uses
 
 inline int chain_wide_plan(const ChainStepArgs &c, int n_cu, bool force, ChainWidePlan &p)
 {
-    if (c.nb < 1 || c.nb > SK_MAXB) return 0;
     if (c.J < 1 || c.K1 < 1 || c.A < 1 || c.A2 < 1 || c.n < 1) return 0;
-    if (((uintptr_t)c.E & 7) || c.x_j < 0 || c.x_k < 0 || c.x_c < 0 || c.w_c < c.A) return 0;
+    if ((uintptr_t)c.E & 7) return 0;
     int nn, sn;
     chain_tile_split(c.A2, nn, sn);
     if (nn + (sn ? 1 : 0) > 10 || (nn == 10 && sn)) return 0;
@@ -385,9 +419,9 @@ inline int chain_wide_plan(const ChainStepArgs &c, int n_cu, bool force, ChainWi
     if (NT > 11 || (NT > 7 && nn + (sn ? 1 : 0) > 7)) return 0;     // rows beyond 7 tiles need waves with two tiles
     p = ChainWidePlan{};
     ChainWide &a = p.a;
-    a.nb = c.nb; a.n = c.n; a.K1 = c.K1; a.A = c.A; a.A2 = c.A2; a.J = c.J;
-    a.w_c = c.w_c; a.x_j = c.x_j; a.x_k = c.x_k; a.x_c = c.x_c; a.x_extent = c.x_extent;
-    a.E = c.E;
+    const bool wt = c.T != nullptr;
+    if (!chain_plan_tables(c, a.W, a.X, wt ? a.T : nullptr)) return 0;
+    chain_plan_scalars(c, a);
     a.A2P = c.A2 + (c.A2 & 1);
     int unr, KB1;
     chain_phase_a_runs(c.K1, unr, KB1);
@@ -436,7 +470,6 @@ inline int chain_wide_plan(const ChainStepArgs &c, int n_cu, bool force, ChainWi
     a.nac = nac;
     // 32-bit byte offsets: the X walk (incl. the prefetch one slice past the end) and T
     if ((c.x_extent + c.x_k + ((int64_t)KB1 * 4 + 32) * c.x_c) * 8 >= (1ll << 32) - 64) return 0;
-    const bool wt = c.T != nullptr;
     a.t_extent = (int64_t)c.A * c.n * c.J;
     if (wt && (a.t_extent + (int64_t)80 * c.n * c.J) * 8 >= (1ll << 32) - 64) return 0;
     // geometry: one workgroup per CU, each a contiguous range of slices of one chunk
@@ -446,19 +479,9 @@ inline int chain_wide_plan(const ChainStepArgs &c, int n_cu, bool force, ChainWi
     a.wpp = wpp;
     const int units = wpp * nac;
     a.xcd_map = (units % 8 == 0) ? 1 : 0;
-    for (int b = 0; b < c.nb; ++b) {
-        if ((uintptr_t)c.X[b] & 7) return 0;
-        a.W[b] = c.W[b];
-        a.X[b] = c.X[b];
-        a.T[b] = wt ? c.T[b] : nullptr;
-    }
-    const int64_t nslab = (int64_t)c.nb * units;
     p.ci = ci; p.nn = nn; p.sn = sn; p.wt = wt; p.unr = unr;
     p.mt2 = CW_NQ[ci] <= 3 && nn + (sn ? 1 : 0) <= 7;
-    p.l.lds = lds; p.l.grid = ng * units;
-    p.l.slab = nslab * c.J * c.A2;
-    p.l.red_chunks = units; p.l.red_m = c.J; p.l.red_n = c.A2;
-    p.l.flops = 2.0 * c.nb * (double)c.n * c.J * ((double)c.K1 * c.A + (double)c.A * c.A2);
+    p.l = chain_plan_launch(c, lds, ng * units, units);
     return 1;
 }
 
@@ -590,18 +613,15 @@ inline bool cs_wave_table(int NRT, int NNF, int NS, ChainSumRole *role)
 inline int chain_sum_plan(const ChainSumArgs &cc, int n_cu, bool force, ChainSumPlan &p)
 {
     const ChainStepArgs &c = cc.s;
-    if (c.nb < 1 || c.nb > SK_MAXB) return 0;
     constexpr int JS = 5, KB1 = 5;                      // the instantiated structure: J, K1 <= 20
     if (c.J < 1 || c.J > 4 * JS || c.K1 < 1 || c.K1 > 4 * KB1 || c.A < 4 || c.A > 128 || c.A2 < 4 || c.A2 > 128 || c.n < 1) return 0;
     if ((c.A2 & 1) || ((uintptr_t)c.E & 15)) return 0;                 // 16-byte units of E rows
-    if (c.x_j < 0 || c.x_k < 0 || c.x_c < 0 || c.w_c < c.A) return 0;
     if (!force && c.nb < 4) return 0;                   // few terms: the rows of a workgroup would be mostly padding
     p = ChainSumPlan{};
     ChainSum &ka = p.ka;
     ChainSumS &a = ka.s;
-    a.nb = c.nb; a.n = c.n; a.K1 = c.K1; a.A = c.A; a.A2 = c.A2; a.J = c.J;
-    a.w_c = c.w_c; a.x_j = c.x_j; a.x_k = c.x_k; a.x_c = c.x_c; a.x_extent = c.x_extent;
-    a.E = c.E;
+    if (!chain_plan_tables(c, ka.W, ka.X, nullptr)) return 0;
+    chain_plan_scalars(c, a);
     a.T = cc.Tint; a.t_b = cc.t_b; a.t_ld = cc.t_ld; a.t_extent = cc.t_extent;
     a.c_fast = c.x_c == 1 ? 1 : 0;
     const int JP = 4 * JS, KP = 4 * KB1;
@@ -670,7 +690,7 @@ inline int chain_sum_plan(const ChainSumArgs &cc, int n_cu, bool force, ChainSum
     a.inv_ng = (1 << 20) / a.ngroups + 1;
     if ((int64_t)a.ngroups * nr * a.ngroups >= (1 << 20)) return 0;
     a.wpt = 8 / tpw;
-    a.e_inv = (uint32_t)(((1ull << 32) + (uint32_t)a.A2P - 1) / (uint32_t)a.A2P);
+    a.e_inv = e_image_inv(a.A2P);
     a.per = (KP * JP + a.wpt - 1) / a.wpt;
     a.gu = (a.per + 63) / 64;
     // 32-bit byte offsets
@@ -691,17 +711,8 @@ inline int chain_sum_plan(const ChainSumArgs &cc, int n_cu, bool force, ChainSum
     if ((int64_t)c.nb * nr * c.J * c.A2 * 8 >= lim32) return 0;
     a.slab_r8 = (uint32_t)((int64_t)c.J * c.A2 * 8);
     a.slab_t8 = (uint32_t)((int64_t)nr * c.J * c.A2 * 8);
-    for (int b = 0; b < c.nb; ++b) {
-        if ((uintptr_t)c.X[b] & 7) return 0;
-        ka.W[b] = c.W[b];
-        ka.X[b] = c.X[b];
-    }
-    const int64_t nslab = (int64_t)c.nb * nr;
     p.na_run = na_run; p.wt = a.T != nullptr;
-    p.l.lds = lds; p.l.grid = a.ngroups * nr;
-    p.l.slab = nslab * c.J * c.A2;
-    p.l.red_chunks = nr; p.l.red_m = c.J; p.l.red_n = c.A2;
-    p.l.flops = 2.0 * c.nb * (double)c.n * c.J * ((double)c.K1 * c.A + (double)c.A * c.A2);
+    p.l = chain_plan_launch(c, lds, a.ngroups * nr, nr);
     return 1;
 }
 

@@ -25,11 +25,6 @@
 
 namespace ttsk {
 
-__device__ __forceinline__ void st8s(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, double v)
-{
-    __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<v2i_t *>(&v), r, (int)voff, (int)soff, 0);
-}
-
 #ifdef TTSK_LAB
 #define CS_DIAG(bit) (a.diag & (bit))
 #else
@@ -128,22 +123,14 @@ __device__ __forceinline__ void cs_prologue(const ChainSumS &a, const ChainSumRo
         }
     }
     CS_PSTAMP(1);
-    // ---- E loader: unit U of the image = columns (2 (u >> 1), + 1) of row 2 sec + (u & 1), sec = U / A2P, u = U % A2P;
-    // wave w issues instructions w, w + 8, ... (1 KB each); the per-lane source offsets are the same for every slice.
-    // Rows beyond A repeat row A - 1 (they meet exact zeros of T).
+    // ---- E loader: the image of chain_plan.h (e_image_unit); wave w issues instructions w, w + 8, ... (1 KB each); the
+    // per-lane source offsets are the same for every slice.
     {
-        const uint32_t inv = a.e_inv;                // ceil(2^32 / A2P)
         const int rowstride = a.n * a.A2;
 #pragma unroll
         for (int i = 0; i < CS_DMAMAX; ++i) {
-            const int m = w + 8 * i;
-            const uint32_t U = 64u * (uint32_t)m + (uint32_t)lane;
-            const uint32_t sec = (uint32_t)(((uint64_t)U * inv) >> 32), u = U - sec * (uint32_t)A2P;
-            int row = (int)(2 * sec + (u & 1));
-            row = row < a.A ? row : a.A - 1;
-            int col = (int)(2 * (u >> 1));
-            col = col + 1 < a.A2 ? col : 0;
-            P.esrc[i] = (row * rowstride + col) * 8;   // bytes (< 2^32: checked by the host)
+            const EUnit un = e_image_unit(64u * (uint32_t)(w + 8 * i) + (uint32_t)lane, a.e_inv, a.A, a.A2, A2P);
+            P.esrc[i] = (un.row * rowstride + un.col) * 8;   // bytes (< 2^32: checked by the host)
         }
     }
     CS_PSTAMP(2);
@@ -151,8 +138,8 @@ __device__ __forceinline__ void cs_prologue(const ChainSumS &a, const ChainSumRo
     P.gl_lane = ro.term * (KP * JP) + kq * JP + (x16 & 3);                   // + (4 kb) JP + 4 qs
     P.gl_tile = ro.term * (KP * JP) + kq * JP + x16;                         // G fragment of a 16-row tile: + (4 kb) JP + 16 q
     P.tl_lane = (kq >> 1) * 2 * RP + 2 * x16 + (kq & 1);                      // + (2 kb) 2 RP + 32 rt
-    P.el_lane = (kq >> 1) * 2 * A2P + 4 * (x16 >> 1) + 2 * (kq & 1) + (x16 & 1);   // + (2 kb) 2 A2P + 32 ct
-    P.es_lane = (kq >> 1) * 2 * A2P + 4 * ((16 * a.NNF + (x16 & 3)) >> 1) + 2 * (kq & 1) + (x16 & 1);   // + 8 s
+    P.el_lane = e_frag_lane(x16, kq, A2P);                                    // + (2 kb) 2 A2P + 32 ct
+    P.es_lane = e_strip_lane(kq, A2P) + e_image_at(0, 16 * a.NNF + (x16 & 3), A2P);   // + 8 s
     // where this lane's phase-A results go.  Strips: lane (i = kq, beta, j4) holds a = 16 (at0 + p) + 4 beta + kq, row = term JP
     // + j4 (+ the strip's rows); tiles: register t of lane (x16, kq) is a = 16 (at0 + p) + 4 t + kq, row = term JP + x16
     // (four rows a further = t * 4 RP elements of the image).  Memory (WT): byte offsets without the slice term.

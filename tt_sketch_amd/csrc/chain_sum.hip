@@ -17,7 +17,7 @@ int chain_sum_try(const ChainSumArgs &cc, int stream, hipStream_t st, bool force
     if (!chain_sum_plan(cc, n_cu, force, p)) return 0;
     ChainSum &ka = p.ka;
     ChainSumS &a = ka.s;
-    a.slab = (double *)scratch(stream, SCRATCH_GEMM, (size_t)p.l.slab * 8 + 64);
+    a.slab = chain_slab_request(stream, p.l);
     if (!a.slab) return TTSK_ERR_HIP;
     ProfBracket prof(st, PROF_CURRENT, p.l.flops,
                      "chain_sum_kernel<5, 5, NA, %s>", p.wt ? "true" : "false");
@@ -58,11 +58,7 @@ int chain_sum_try(const ChainSumArgs &cc, int stream, hipStream_t st, bool force
             }
     }
 #endif
-    if (rc == TTSK_OK) {
-        ReduceOut ro{};
-        for (int b = 0; b < c.nb; ++b) ro.C[b] = c.Out[b];
-        rc = launch_r_reduce(st, a.slab, p.l.red_chunks, p.l.red_m, p.l.red_n, 1, (int64_t)c.J, ro, c.nb, (int64_t)c.A2, (int64_t)1, 1.0, 0);
-    }
+    if (rc == TTSK_OK) rc = chain_slab_reduce(st, a.slab, p.l, c);
     return rc == TTSK_OK ? 1 : rc;
 }
 

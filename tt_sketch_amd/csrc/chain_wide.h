@@ -20,7 +20,11 @@
 // a wave per tensor with both its tiles) and every E_k it brings into LDS is used by all of them.
 // Odd DRM ranks: the E image is filled in 16-byte units from 8-byte-aligned rows; the unit behind the last
 // column of a row takes the first element of the next slice along (it meets an output column that is never
-// stored), and the one unit that would reach past the end of the core is patched with an 8-byte load.
+// stored), and the one unit that would reach past the end of the core is patched with an 8-byte load
+// (chain_plan.h: e_image_unit_from).
+//
+// The XCD mapping and the gathering E loader are those of chain_stages.h; cw_compute is
+// cf_piece (chain_fused.h) with MT = 1 or 2 row tiles per wave, written out.
 #pragma once
 #include "chain_fused.h"
 
@@ -74,9 +78,9 @@ __device__ __forceinline__ void cw_compute(const ChainWide &a, const double *Wl,
 
     const int wl_lane = (kq >> 1) * 2 * AP + 2 * x16 + (kq & 1);
     const int ws_lane = (kq >> 1) * 2 * AP + 2 * (16 * NQF + (x16 & 3)) + (kq & 1);
-    const int el_lane = (kq >> 1) * 2 * A2P + 4 * (x16 >> 1) + 2 * (kq & 1) + (x16 & 1);
+    const int el_lane = e_frag_lane(x16, kq, A2P);
     const int es_col = 16 * NNF + (x16 & 3);
-    const int es_lane = (kq >> 1) * 2 * A2P + 2 * (kq & 1);
+    const int es_lane = e_strip_lane(kq, A2P);
 
     __amdgpu_buffer_rsrc_t rt;
     if constexpr (WT) rt = make_rsrc(uniform_ptr(a.T[prob]), a.t_extent * 8);
@@ -155,6 +159,8 @@ __device__ __forceinline__ void cw_compute(const ChainWide &a, const double *Wl,
         {
             const double *eb = El + ((a.ebuf2 && (k & 1)) ? a.eunits * 2 : 0);
             double bf[NNF ? NNF : 1], bs[STRN ? STRN : 1];
+            // (= es_lane + e_image_at(0, es_col, A2P), kept in this order of additions: written with the helper, 32 of the
+            // strip instantiations lose a wave of occupancy or gain spills)
             int el0 = el_lane, es0 = es_lane + 4 * (es_col >> 1) + (es_col & 1);
             asm volatile("" : "+v"(el0), "+v"(es0));
             auto efetch = [&](int kap, double (&f)[NNF ? NNF : 1], double (&g)[STRN ? STRN : 1]) {
@@ -227,17 +233,8 @@ __global__ __launch_bounds__(512, 2) void chain_wide_kernel(ChainWide a)
     double *Wl = cf_lds;
     double *El = cf_lds + a.ebase;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int units = a.wpp * a.nac;
-    int prob, unit;
-    if (a.xcd_map) {
-        // blocks b and b + 8 share an XCD: deal the units over the XCDs, all problems of a unit to the same one
-        const int upx = units >> 3, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        unit = xcd * upx + j % upx;
-        prob = j / upx;
-    } else {
-        prob = blockIdx.x / units;
-        unit = blockIdx.x - prob * units;
-    }
+    int prob, unit;                                    // unit = (slice range, chunk)
+    chain_block_unit(a.xcd_map, a.wpp * a.nac, prob, unit);
     const int prob0 = prob * a.tpw;                    // first tensor of this workgroup's group
     const int g = unit / a.nac, ac = unit - g * a.nac;
     const int a0 = ac * a.ac;
@@ -247,6 +244,8 @@ __global__ __launch_bounds__(512, 2) void chain_wide_kernel(ChainWide a)
     const int A2P = a.A2P;
 
     // ---- stage the chunk of W (of every tensor of the group): Wl[(c >> 1) * 2 AP + 2 col + (c & 1)] = W[c][a0 + col], zero beyond (K1, cnt)
+    // (the loop of chain_step_kernel with a column origin and 8 loads in flight: one shared function template moved the
+    // register count of the instantiations whose compute waves need fewer registers than this loop -- DESIGN.md)
     for (int sl = 0; sl < a.tpw; ++sl) {
         if (prob0 + sl >= a.nb) break;
         const double *Wp = uniform_ptr(a.W[prob0 + sl]);
@@ -272,38 +271,14 @@ __global__ __launch_bounds__(512, 2) void chain_wide_kernel(ChainWide a)
     }
 
     if (w == a.loader) {
-        // ---- loader: rows a0 .. of E_k -> El in 16-byte units (layout: chain_fused.h).  Rows beyond the chunk
-        // (and beyond A: clamped) meet exact zeros of T.
+        // ---- loader: rows a0 .. of E_k -> El in 16-byte units.  Rows beyond the chunk (and beyond A: clamped) meet exact
+        // zeros of T.
         const int NI = a.eunits >> 6;
-        const uint32_t inv = (uint32_t)(((1ull << 32) + (uint32_t)A2P - 1) / (uint32_t)A2P);   // U / A2P for U < 2^16
+        const uint32_t inv = e_image_inv(A2P);
         const int64_t rowstride = (int64_t)a.n * a.A2;
         const int ebuf = a.eunits * 2;                 // doubles per E image
-        const bool odd = a.A2 & 1;
         auto fill = [&](int k) {
-            const double *Ek = a.E + (int64_t)k * a.A2;
-            double *dst = El + ((a.ebuf2 && (k & 1)) ? ebuf : 0);
-            const bool tail = odd && k == a.n - 1;     // the unit behind the last column would reach past the core
-#pragma unroll 2
-            for (int m = 0; m < NI; ++m) {
-                const uint32_t U = 64u * (uint32_t)m + (uint32_t)lane;
-                const uint32_t sec = (uint32_t)(((uint64_t)U * inv) >> 32), u = U - sec * (uint32_t)A2P;
-                int row = a0 + (int)(2 * sec + (u & 1));
-                row = row < a.A ? row : a.A - 1;
-                int col = (int)(2 * (u >> 1));
-                col = (col + 1 < a.A2 || (odd && !tail && col < a.A2)) ? col : 0;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(Ek + row * rowstride + col),
-                                                 (__attribute__((address_space(3))) void *)(dst + m * 128), 16, 0, 0);
-            }
-            if (tail) {
-                // last slice, odd A2: column A2 - 1 of every row by an 8-byte load (after the units have landed)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane < AP) {
-                    int row = a0 + lane;
-                    row = row < a.A ? row : a.A - 1;
-                    const double v = Ek[row * rowstride + a.A2 - 1];
-                    dst[(lane >> 1) * 2 * A2P + 4 * ((a.A2 - 1) >> 1) + 2 * (lane & 1)] = v;
-                }
-            }
+            chain_e_fill_gather<true>(a, El + ((a.ebuf2 && (k & 1)) ? ebuf : 0), k, a0, A2P, inv, rowstride, NI, 0, 1, lane, AP);
         };
         __syncthreads();                               // W staged (all waves)
         if (a.ebuf2) {

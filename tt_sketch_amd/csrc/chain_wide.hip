@@ -33,17 +33,13 @@ int chain_wide_try(const ChainStepArgs &c, int stream, hipStream_t st, bool forc
     ChainWidePlan p;
     if (!chain_wide_plan(c, n_cu, force, p)) return 0;
     ChainWide &a = p.a;
-    a.slab = (double *)scratch(stream, SCRATCH_GEMM, (size_t)p.l.slab * 8 + 64);
+    a.slab = chain_slab_request(stream, p.l);
     if (!a.slab) return TTSK_ERR_HIP;
     ProfBracket prof(st, PROF_CURRENT, p.l.flops,
                      "chain_wide_kernel<%d, %d, %d, %d, %s, %d, %s>", CW_NQ[p.ci], CW_SQ[p.ci], p.nn, p.sn, p.wt ? "true" : "false", p.unr,
                      p.mt2 ? "true" : "false");
     int rc = launch_chain_wide(p.ci, a, p.nn, p.sn, p.wt, p.unr, p.l.lds, p.l.grid, st);
-    if (rc == TTSK_OK) {
-        ReduceOut ro{};
-        for (int b = 0; b < c.nb; ++b) ro.C[b] = c.Out[b];
-        rc = launch_r_reduce(st, a.slab, p.l.red_chunks, p.l.red_m, p.l.red_n, 1, (int64_t)c.J, ro, c.nb, (int64_t)c.A2, (int64_t)1, 1.0, 0);
-    }
+    if (rc == TTSK_OK) rc = chain_slab_reduce(st, a.slab, p.l, c);
     return rc == TTSK_OK ? 1 : (rc == 1 ? 0 : rc);
 }
 

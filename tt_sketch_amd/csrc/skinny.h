@@ -73,6 +73,12 @@ __device__ __forceinline__ void st8(__amdgpu_buffer_rsrc_t r, uint32_t voff, dou
     __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<v2i_t *>(&v), r, (int)voff, 0, 0);
 }
 
+// the same with a wave-uniform part of the offset
+__device__ __forceinline__ void st8s(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, double v)
+{
+    __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<v2i_t *>(&v), r, (int)voff, (int)soff, 0);
+}
+
 template <int NPT, int NT, bool SH, int D, int RB, bool BIG, int STR>
 __device__ __forceinline__ void skinny_s_wave_impl(const SkinnyS &a, const double *Wl, const int v, const int tile0,
                                                    const int tshared);
