@@ -307,6 +307,23 @@ int ttsk_cp_gather(const double *const *dev_factors, int64_t rank, const int64_t
 int ttsk_tt_gram(const double *const *dev_cores_a, const int64_t *ranks_a, int K, const double *const *dev_cores_b,
                  const int64_t *ranks_b, int M, const int64_t *shape, int d, double *dev_out, int stream);
 
+/* ---- the bond solve of Gram-SVD rounding (csrc/gram_round.hip, plan in csrc/gram_round_plan.h) ----
+ * Every bond of a tensor train truncated at once from the Gram matrices of its left and right parts (Al Daas, Ballard,
+ * Manning 2022).  For bond b of rank r = ranks[b], with GL = V_L L_L V_L^T and GR = V_R L_R V_R^T (the
+ * eigenpairs above r eps_machine of the largest) and M = L_L^{1/2} V_L^T V_R L_R^{1/2} = U S W^T:
+ *   dev_sigma[b]   (r) the singular values S of the b-th unfolding, descending, zero beyond those found
+ *   dev_rank_out   [b] = rho = max(1, min(#{S > S_1 eps}, caps[b]))
+ *   dev_pt[b]      (r, r) row-major, row c < rho the column c of P = V_L L_L^{-1/2} U_rho, rows >= rho zero
+ *   dev_q[b]       (r, r) row-major, row c < rho of Q = U_rho^T L_L^{1/2} V_L^T, rows >= rho zero
+ * so that the rounded cores are Q_k C_k P_{k+1}.  dev_gl[b], dev_gr[b]: (r, r) row-major.  The pointer tables and ranks
+ * are host arrays.  Two launches whatever count is (one workgroup per Gram, then one per bond), one-sided Jacobi; no
+ * atomics: the same bits on every call.  Singular values below about sqrt(eps_machine) of the largest are not resolved.
+ * TTSK_ERR_ARG: a NULL pointer, count < 1, a rank or cap < 1, eps negative or not finite.  TTSK_ERR_UNSUPPORTED before
+ * anything is launched: count > 64, a rank beyond 1024. */
+int ttsk_gram_round_bonds(const double *const *dev_gl, const double *const *dev_gr, const int64_t *ranks, const int64_t *caps,
+                          int count, double eps, double *const *dev_pt, double *const *dev_q, double *const *dev_sigma,
+                          int *dev_rank_out, int stream);
+
 /* ---- operator-times-train products, never formed (csrc/op_apply.hip, plan in csrc/op_apply_plan.h) ----
  * One step of sketching the product of a matrix product operator and a tensor train (tt_gmres.py:91-101) without its
  * cores: for every term p of a sum, with operator core M (R, n_in, n_out, R'), train core C (r, n_in, r') and the chain

@@ -119,6 +119,7 @@ ENTRY_POINTS = {
     "ttsk_tt_gather": Entry([POINTER(P), POINTER(I64), POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
     "ttsk_cp_gather": Entry([POINTER(P), I64, POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
     "ttsk_tt_gram": Entry([POINTER(P), POINTER(I64), I, POINTER(P), POINTER(I64), I, POINTER(I64), I, P, I], QUEUE),
+    "ttsk_gram_round_bonds": Entry([POINTER(P), POINTER(P), POINTER(I64), POINTER(I64), I, c_double, POINTER(P), POINTER(P), POINTER(P), P, I], QUEUE),
     "ttsk_op_apply": Entry([I, POINTER(P), POINTER(P), POINTER(P), POINTER(I64), POINTER(I64), I64, P, I64, I], QUEUE),
     "ttsk_hadamard_apply": Entry([P, P, P, POINTER(I64), POINTER(I64), P, I64, I64, I], QUEUE),
     "ttsk_cp_chain_step": Entry([P, I64, P, I64, I64, P, P, I64, I64, I64, I64, I64, I], QUEUE),

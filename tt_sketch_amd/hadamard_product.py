@@ -138,6 +138,6 @@ class HadamardProduct(Tensor):
 def hadamard_round(x: TensorTrain, y: TensorTrain, max_rank, eps: Optional[float] = None, method="sketch",
                    oversample_factor: float = 2) -> TensorTrain:
     """``x o y`` rounded to ``max_rank``: ``tt_gmres.round_tt_sum`` of the one-term sum.  The two sketched methods never
-    form the product; ``"exact"``, ``"pairwise"`` and None form it first."""
+    form the product; ``"exact"``, ``"pairwise"``, ``"gram"`` and None form it first."""
     from .tt_gmres import round_tt_sum
     return round_tt_sum(TensorSum([HadamardProduct(x, y)]), max_rank, eps=eps, method=method, oversample_factor=oversample_factor)

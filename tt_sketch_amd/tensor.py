@@ -13,7 +13,8 @@ has a device form it decides here whether to take it, and the pass itself lives 
 by an import inside the method: ``tensor_gather`` (evaluation at index lists: ``gather_dev``, ``support_error``,
 ``SparseTensor.dot``), ``tensor_dense`` (the pass over a dense tensor: ``dense_stats``, ``to_dense_dev`` and with them
 ``error`` / ``dot`` against a ``DenseTensor``) and ``tensor_gram`` (``tt_gram``, ``cp_gram`` and the chain of a train against a
-``CPTensor``: resident ``dot`` / ``norm`` / ``error(fast=True)``).  Those modules import the classes from this one and
+``CPTensor``: resident ``dot`` / ``norm`` / ``error(fast=True)``) and ``tensor_round`` (Gram-SVD rounding: ``round_gram``,
+``svdvals_gram``).  Those modules import the classes from this one and
 never ``_host``, so a device pass has no way to a host copy.  The TT sweeps ``orthogonalize_dev`` / ``round_dev`` are
 methods without a helper layer and stay with ``TensorTrain``.
 
@@ -607,6 +608,29 @@ class TensorTrain(_CoreList, Tensor):
                 V = contract("ab,cb->ac", Vt[:r], Qc)
             out.append(V.reshape(r, n, r2))
         return TensorTrain(out[::-1])
+
+    def round_gram(self, eps: Optional[float] = None, max_rank: Optional[TTRank] = None) -> "TensorTrain":
+        """Gram-SVD rounding on the device: the rank rule and the arguments of ``round``, all bonds
+        truncated at once from the Gram matrices of the left and right parts (``ttsk_gram_round_bonds``) instead of by
+        two sweeps.  Takes a resident train or host cores (uploaded once); the result is resident; one read-back, the
+        ``d - 1`` chosen ranks.  The same bits on every call.
+
+        The price is the floor of every Gram method (``gram_norm``, ``error(fast=True)``): singular values below about
+        ``sqrt(eps_machine)`` of the largest are not resolved, so a term of relative size 1e-10 is lost where ``round`` keeps
+        it: ``x.add(y * 1e-10)`` rounded at ``eps=1e-12`` comes back at the ranks of ``x`` with a relative error of 9.6e-11
+        against the input, the dropped term (``tests/test_gpu_gram_round.py``), where ``round`` keeps every rank at 2e-15.
+        Above the floor the ranks are those of ``round``; the error is within 0.6 % of its error on the test cases and, as
+        every bond is cut from the untruncated train, a few percent above it where a flat spectrum is cut hard (DESIGN
+        section 18).  Bond ranks up to 1024, as ``round_dev``, which stays the exact method."""
+        from .tensor_round import round_gram
+        return round_gram(self, eps, max_rank)
+
+    def svdvals_gram(self) -> List[npt.NDArray]:
+        """The singular values of the unfoldings at the ``d - 1`` bonds (entry ``b - 1``: bond ``b``, what ``svdvals()[b]``
+        holds) from the bond solve of ``round_gram`` with no truncation, on the device.  Values below about
+        ``sqrt(eps_machine)`` of the largest of a bond are not resolved: they come back as noise of that size or as zeros."""
+        from .tensor_round import svdvals_gram
+        return svdvals_gram(self)
 
     def round(self, eps: Optional[float] = None, max_rank: Optional[TTRank] = None,
               orthogonalized: bool = False) -> "TensorTrain":

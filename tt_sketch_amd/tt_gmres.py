@@ -214,7 +214,7 @@ class TTLinearMapSum:
         return TensorSum([lm(t) for lm in self.linear_maps for t in terms])
 
 
-ROUNDING_MODE = Literal["exact", "pairwise", "sketch", "orth_sketch", None]
+ROUNDING_MODE = Literal["exact", "pairwise", "gram", "sketch", "orth_sketch", None]
 
 
 def round_tt_sum(tt_sum: TensorSum, max_rank: TTRank, eps: Optional[float] = None,
@@ -222,17 +222,19 @@ def round_tt_sum(tt_sum: TensorSum, max_rank: TTRank, eps: Optional[float] = Non
     """Round a sum of trains to ``max_rank`` (reference tt_gmres.py:258-305): ``"exact"`` = direct
     sum then TT-SVD, ``"pairwise"`` = add and round term by term, ``"sketch"`` = streaming sketch
     with right rank ``ceil(oversample_factor * left)``, ``"orth_sketch"`` = orthogonal sketch,
-    ``None`` = no rounding.  The two SVD variants run ``add`` / ``round_dev`` on the device.  Only the two sketches take
-    an ``OperatorProduct`` or ``HadamardProduct`` term as it is; the other methods form it first."""
+    ``None`` = no rounding.  The two SVD variants run ``add`` / ``round_dev`` on the device; ``"gram"`` = direct sum on the
+    device then Gram-SVD rounding (``round_gram``: all bonds at once, one read-back, singular values below about 1e-8 of
+    the largest not resolved).  Only the two sketches take an ``OperatorProduct`` or ``HadamardProduct`` term as it is; the
+    other methods form it first."""
     lazy = (OperatorProduct, HadamardProduct)
-    if method in ("exact", "pairwise", None) and any(isinstance(t, lazy) for t in tt_sum.tensors):
+    if method in ("exact", "pairwise", "gram", None) and any(isinstance(t, lazy) for t in tt_sum.tensors):
         tt_sum = TensorSum([t.to_tt() if isinstance(t, lazy) else t for t in tt_sum.tensors])
-    if method == "exact":
+    if method in ("exact", "gram"):
         terms = [t.to_device() for t in tt_sum.tensors]
         tt = terms[0]
         for t in terms[1:]:
             tt = tt.add(t)
-        return tt.round_dev(eps, max_rank)
+        return tt.round_dev(eps, max_rank) if method == "exact" else tt.round_gram(eps, max_rank)
     if method == "pairwise":
         terms = [t.to_device() for t in tt_sum.tensors]
         tt = terms[0]
