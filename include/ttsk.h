@@ -292,6 +292,36 @@ int ttsk_cp_gather(const double *const *dev_factors, int64_t rank, const int64_t
                    const int64_t *dev_idx, int64_t row_stride, const int *row_order, size_t N,
                    const double *dev_val, double *dev_out, double *dev_stats, int stream);
 
+/* ---- a sparse tensor against another explicit tensor: join on sorted keys (csrc/sparse_join.hip, plan in
+ * csrc/sparse_join_plan.h) ----
+ * SparseTensor.gather (tensor.py:275-286, a dict of every nonzero) and SparseTensor.dot (tensor.py:250-255) against a
+ * sparse or a dense tensor.  The key of an index tuple is its C-order flat index in `shape` (np.ravel_multi_index); index
+ * matrices are addressed as in ttsk_tt_gather (row_stride, row_order), so a SparseTensor and its .T are read in place.
+ * TTSK_ERR_UNSUPPORTED before anything is launched or allocated: d > 32, a shape of more than 2^63 - 1 entries, a table
+ * of 2^31 nonzeros or more.  max_split: splitters kept per table, 0 for the library's choice (the same value in the calls
+ * that build and that read an index).
+ *
+ * Index of a table: the nonzeros sorted stably by key.
+ *   dev_keys_sorted (N) int64, dev_vals_sorted (N): dev_vals_sorted[i] = dev_val[perm[i]]
+ *   dev_splitters   every stride-th sorted key; stride and count from ttsk_sparse_join_layout */
+int ttsk_sparse_key_index(const int64_t *shape, int d, const int64_t *dev_idx, int64_t row_stride, const int *row_order, size_t N,
+                          const double *dev_val, int max_split, int64_t *dev_keys_sorted, double *dev_vals_sorted,
+                          int64_t *dev_splitters, int stream);
+/* Lookup of Nq index tuples in an index: dev_out[q] (or NULL) = the entry of the LAST nonzero of the table with the key of
+ * query q, 0.0 if there is none (a repeated index of the table counts once, the last one wins: the dict of the reference;
+ * every query counts); dev_dot (1 double, or NULL; needs dev_qval) = sum_q dev_qval[q] * that, summed in a fixed order
+ * without atomics: the same bits on every call, with or without dev_out.  N_table = 0 and Nq = 0 are legal. */
+int ttsk_sparse_join(const int64_t *dev_keys_sorted, const double *dev_vals_sorted, const int64_t *dev_splitters, size_t N_table,
+                     int max_split, const int64_t *shape, int d, const int64_t *dev_qidx, int64_t q_row_stride,
+                     const int *q_row_order, size_t Nq, const double *dev_qval, double *dev_out, double *dev_dot, int stream);
+/* The same against a contiguous C-order dense tensor dev_x of `shape`: the key is the element offset */
+int ttsk_dense_join(const double *dev_x, const int64_t *shape, int d, const int64_t *dev_qidx, int64_t q_row_stride,
+                    const int *q_row_order, size_t Nq, const double *dev_qval, double *dev_out, double *dev_dot, int stream);
+/* The plan's numbers for a table of N_table nonzeros and Nq queries on this device (host only, after ttsk_init):
+ * out[0..7] = SJ_MAX_SPLIT, stride, splitter count, steps of the LDS search, steps of the segment search, workgroups,
+ * queries per workgroup, longest chain of additions of the dot */
+int ttsk_sparse_join_layout(size_t N_table, size_t Nq, int max_split, int64_t *out);
+
 /* ---- Gram matrix of tensor trains (csrc/tt_gram.hip, plan in csrc/tt_gram_plan.h) ----
  * TensorTrain.dot (tensor.py:542-557) for every pair of two lists of trains at once: dev_out[p * M + q] = <A_p, B_q>.  With
  * it Tensor.error(fast=True) (tensor.py:68-72) of two trains is one 2 x 2 call, a Hessenberg column of tt_gmres.py:385-386

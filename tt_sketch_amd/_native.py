@@ -118,6 +118,10 @@ ENTRY_POINTS = {
     "ttsk_sparse_psi": Entry([P, P, P, S, P, I64, P, I64, I64, P, I], QUEUE),
     "ttsk_tt_gather": Entry([POINTER(P), POINTER(I64), POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
     "ttsk_cp_gather": Entry([POINTER(P), I64, POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
+    "ttsk_sparse_key_index": Entry([POINTER(I64), I, P, I64, POINTER(I), S, P, I, P, P, P, I], QUEUE),
+    "ttsk_sparse_join": Entry([P, P, P, S, I, POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
+    "ttsk_dense_join": Entry([P, POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
+    "ttsk_sparse_join_layout": Entry([S, S, I, POINTER(I64)]),
     "ttsk_tt_gram": Entry([POINTER(P), POINTER(I64), I, POINTER(P), POINTER(I64), I, POINTER(I64), I, P, I], QUEUE),
     "ttsk_gram_round_bonds": Entry([POINTER(P), POINTER(P), POINTER(I64), POINTER(I64), I, c_double, POINTER(P), POINTER(P), POINTER(P), P, I], QUEUE),
     "ttsk_op_apply": Entry([I, POINTER(P), POINTER(P), POINTER(P), POINTER(I64), POINTER(I64), I64, P, I64, I], QUEUE),

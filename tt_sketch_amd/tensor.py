@@ -13,8 +13,9 @@ has a device form it decides here whether to take it, and the pass itself lives 
 by an import inside the method: ``tensor_gather`` (evaluation at index lists: ``gather_dev``, ``support_error``,
 ``SparseTensor.dot``), ``tensor_dense`` (the pass over a dense tensor: ``dense_stats``, ``to_dense_dev`` and with them
 ``error`` / ``dot`` against a ``DenseTensor``) and ``tensor_gram`` (``tt_gram``, ``cp_gram`` and the chain of a train against a
-``CPTensor``: resident ``dot`` / ``norm`` / ``error(fast=True)``) and ``tensor_round`` (Gram-SVD rounding: ``round_gram``,
-``svdvals_gram``).  Those modules import the classes from this one and
+``CPTensor``: resident ``dot`` / ``norm`` / ``error(fast=True)``), ``tensor_round`` (Gram-SVD rounding: ``round_gram``,
+``svdvals_gram``) and ``tensor_sparse`` (the sorted-key join: ``SparseTensor.dot`` against a sparse or a dense tensor,
+``SparseTensor.gather`` / ``gather_dev``).  Those modules import the classes from this one and
 never ``_host``, so a device pass has no way to a host copy.  The TT sweeps ``orthogonalize_dev`` / ``round_dev`` are
 methods without a helper layer and stay with ``TensorTrain``.
 
@@ -365,10 +366,18 @@ class SparseTensor(Tensor):
     def norm(self) -> float:
         return float(np.linalg.norm(self.entries))
 
-    def dot(self, other, reverse=False) -> float:
+    def dot(self, other, reverse=False, route: Optional[str] = None) -> float:
+        """``<self, other>``.  ``route`` is the switch of ``paths.py`` for the lookup in another explicit tensor: the
+        sorted-key join on the device, or the host path (``"composed"``: the dict of the reference)."""
         if isinstance(other, _CoreList) and (other.resident() or self._dev is not None):
             from .tensor_gather import _gather_device
             return float(_gather_device(other, self, False, True)[1][0])      # one pass, no (N,) vector
+        if (isinstance(other, SparseTensor) and (self._dev is not None or other._dev is not None)) or \
+                (isinstance(other, DenseTensor) and (self._dev is not None or _dense_current(other))):
+            from .tensor_sparse import _join_dot
+            got = _join_dot(self, other, route)        # self as the queries: one join pass, nothing downloaded
+            if got is not None:
+                return got
         if hasattr(other, "gather"):
             return float(np.dot(other.gather(self.indices), self.entries))
         return super().dot(other, reverse=reverse)
@@ -382,7 +391,27 @@ class SparseTensor(Tensor):
     def __mul__(self, other: float) -> "SparseTensor":
         return SparseTensor(self.shape, self.indices, self.entries * other)
 
-    def gather(self, indices) -> npt.NDArray[np.float64]:
+    def gather_dev(self, idx) -> DevArray:
+        """Entries at the given multi-indices as a device array (N,), 0.0 where the tensor has none (of a repeated
+        index its last entry): ``idx`` is a ``SparseTensor`` of this shape, a ``(d, N)`` array or a tuple of ``d``
+        arrays.  One pass of the sorted-key join (``ttsk_sparse_join``)."""
+        from .tensor_sparse import _sparse_join
+        return _sparse_join(self, idx, True, False)[0]
+
+    def gather(self, indices, route: Optional[str] = None) -> npt.NDArray[np.float64]:
+        """Entries at the given multi-indices (reference tensor.py:275-286).  For an uploaded tensor one device pass and
+        one download of the result where the rule of ``tensor_sparse`` (or ``route``, as in ``dot``) takes it; host
+        otherwise, and for shapes the device entry refuses."""
+        if self._dev is not None:
+            from ._native import TtskUnsupported
+            from .paths import resolve
+            from .tensor_sparse import _join_routed
+            if _join_routed(self, len(indices[0]), route):
+                try:
+                    return self.gather_dev(indices).get()
+                except TtskUnsupported:
+                    if resolve(route) == "kernel":
+                        raise
         keys = np.ravel_multi_index(tuple(indices), self.shape)
         table = self.dict
         return np.array([table.get(int(k), 0.0) for k in keys])
