@@ -291,6 +291,17 @@ int ttsk_tt_gather(const double *const *dev_cores, const int64_t *ranks /* d + 1
 int ttsk_cp_gather(const double *const *dev_factors, int64_t rank, const int64_t *shape, int d,
                    const int64_t *dev_idx, int64_t row_stride, const int *row_order, size_t N,
                    const double *dev_val, double *dev_out, double *dev_stats, int stream);
+/* TuckerTensor entries (tensor.py:771-780 at single indices; csrc/tucker_gather.hip, plan in csrc/tucker_gather_plan.h):
+ *   t_e = sum_{a_1..a_d} C[a_1..a_d] prod_k U_k[a_k, i_k(e)]
+ *   dev_core       (ranks[0], .., ranks[d-1]) contiguous, C order
+ *   dev_factors[k] (ranks[k], shape[k]) contiguous
+ * indices, dev_val, dev_out, dev_stats, their summation order and the argument errors exactly as ttsk_tt_gather (and a
+ * rank below 1 is TTSK_ERR_ARG).  2 |C| flops per tuple on the fp64 matrix instructions, no atomics, the same bits on
+ * every call.  TTSK_ERR_UNSUPPORTED before anything is launched or allocated: d > 8, a core of more than 2^20 entries, a
+ * mode of 2^31 or more. */
+int ttsk_tucker_gather(const double *dev_core, const double *const *dev_factors, const int64_t *ranks /* d */,
+                       const int64_t *shape, int d, const int64_t *dev_idx, int64_t row_stride, const int *row_order,
+                       size_t N, const double *dev_val, double *dev_out, double *dev_stats /* 3 doubles */, int stream);
 
 /* ---- a sparse tensor against another explicit tensor: join on sorted keys (csrc/sparse_join.hip, plan in
  * csrc/sparse_join_plan.h) ----

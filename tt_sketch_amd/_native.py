@@ -118,6 +118,7 @@ ENTRY_POINTS = {
     "ttsk_sparse_psi": Entry([P, P, P, S, P, I64, P, I64, I64, P, I], QUEUE),
     "ttsk_tt_gather": Entry([POINTER(P), POINTER(I64), POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
     "ttsk_cp_gather": Entry([POINTER(P), I64, POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
+    "ttsk_tucker_gather": Entry([P, POINTER(P), POINTER(I64), POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
     "ttsk_sparse_key_index": Entry([POINTER(I64), I, P, I64, POINTER(I), S, P, I, P, P, P, I], QUEUE),
     "ttsk_sparse_join": Entry([P, P, P, S, I, POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),
     "ttsk_dense_join": Entry([P, POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),

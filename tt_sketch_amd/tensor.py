@@ -10,8 +10,10 @@ the tensor on every call) costs no copy and no PCIe traffic.
 
 The arithmetic of the classes (``error``, ``norm``, ``dot``, ``round``, ...) is plain NumPy on the host.  Where a method
 has a device form it decides here whether to take it, and the pass itself lives beside the name of its kernel, reached
-by an import inside the method: ``tensor_gather`` (evaluation at index lists: ``gather_dev``, ``support_error``,
-``SparseTensor.dot``), ``tensor_dense`` (the pass over a dense tensor: ``dense_stats``, ``to_dense_dev`` and with them
+by an import inside the method: ``tensor_gather`` (evaluation of a train, a CP or a Tucker tensor at index lists:
+``gather_dev``, ``support_error``, ``SparseTensor.dot``), ``tensor_tucker`` (a ``TuckerTensor`` against a Tucker tensor, a
+train or a CP tensor: resident ``dot`` / ``norm`` / ``error(fast=True)``), ``tensor_dense`` (the pass over a dense
+tensor: ``dense_stats``, ``to_dense_dev`` and with them
 ``error`` / ``dot`` against a ``DenseTensor``) and ``tensor_gram`` (``tt_gram``, ``cp_gram`` and the chain of a train against a
 ``CPTensor``: resident ``dot`` / ``norm`` / ``error(fast=True)``), ``tensor_round`` (Gram-SVD rounding: ``round_gram``,
 ``svdvals_gram``) and ``tensor_sparse`` (the sorted-key join: ``SparseTensor.dot`` against a sparse or a dense tensor,
@@ -369,9 +371,10 @@ class SparseTensor(Tensor):
     def dot(self, other, reverse=False, route: Optional[str] = None) -> float:
         """``<self, other>``.  ``route`` is the switch of ``paths.py`` for the lookup in another explicit tensor: the
         sorted-key join on the device, or the host path (``"composed"``: the dict of the reference)."""
-        if isinstance(other, _CoreList) and (other.resident() or self._dev is not None):
+        if isinstance(other, (_CoreList, TuckerTensor)) and (other.resident() or self._dev is not None):
             from .tensor_gather import _gather_device
-            return float(_gather_device(other, self, False, True)[1][0])      # one pass, no (N,) vector
+            tucker_route = (route,) if isinstance(other, TuckerTensor) else ()
+            return float(_gather_device(other, self, False, True, *tucker_route)[1][0])      # one pass, no (N,) vector
         if (isinstance(other, SparseTensor) and (self._dev is not None or other._dev is not None)) or \
                 (isinstance(other, DenseTensor) and (self._dev is not None or _dense_current(other))):
             from .tensor_sparse import _join_dot
@@ -757,6 +760,9 @@ class TensorTrain(_CoreList, Tensor):
             return float(acc.sum())
         if isinstance(other, DenseTensor) and (self.resident() or _dense_current(other)):
             return float(self.dense_stats(other)[0])
+        if isinstance(other, TuckerTensor) and (_on_device(self) or _on_device(other)):
+            from .tensor_tucker import tucker_tt_dot
+            return tucker_tt_dot(other, self)
         return super().dot(other, reverse=reverse)
 
     def error(self, other, relative: bool = False, rmse: bool = False, fast: bool = False) -> float:
@@ -909,6 +915,9 @@ class CPTensor(_CoreList, Tensor):
         if isinstance(other, TensorTrain) and (_on_device(self) or _on_device(other)):
             from .tensor_gram import _tt_cp_dot
             return _tt_cp_dot(other, self, route)
+        if isinstance(other, TuckerTensor) and (_on_device(self) or _on_device(other)):
+            from .tensor_tucker import tucker_cp_dot
+            return tucker_cp_dot(other, self)
         return super().dot(other, reverse=reverse)
 
     def __mul__(self, other: float) -> "CPTensor":
@@ -922,7 +931,16 @@ class CPTensor(_CoreList, Tensor):
 
 # --------------------------------------------------------------------------- Tucker
 class TuckerTensor(Tensor):
-    """Tucker format: core ``(s_1..s_d)`` and factors ``(s_k, n_k)`` (reference tensor.py:746-816)."""
+    """Tucker format: core ``(s_1..s_d)`` and factors ``(s_k, n_k)`` (reference tensor.py:746-816).
+
+    ``gather`` / ``gather_dev`` / ``support_error`` and ``SparseTensor.dot`` evaluate the tensor at index lists in one
+    device pass (``ttsk_tucker_gather``: the core against the Khatri-Rao rows of the factor columns on the fp64 matrix
+    instructions; ``tensor_gather``), with a composition from column gathers and batched ``contract`` calls beyond the
+    kernel's cover (``route=`` is the switch of ``paths.py``).  ``dot`` / ``norm`` against a ``TuckerTensor``, a
+    ``TensorTrain`` or a ``CPTensor`` run on the device when either operand is there (``resident()`` or uploaded already;
+    ``tensor_tucker``) and form no dense array, so ``error(fast=True)`` -- the reference's formula, whose floor is a
+    relative error of about 1e-8 -- does not either.  Two host objects keep the NumPy path, ``fast=False`` the reference's
+    dense formula, and a ``DenseTensor`` partner its current path."""
 
     def __init__(self, factors: ArrayList, core, _dev=None) -> None:
         self.core = core
@@ -930,6 +948,7 @@ class TuckerTensor(Tensor):
         self.shape = tuple(int(U.shape[1]) for U in factors)
         self.rank = tuple(int(U.shape[0]) for U in factors)
         self._dev = _dev
+        self._core_c = None               # (device core it was made from, its contiguous copy): a .T view's core is strided
 
     def dev_parts(self) -> Tuple[List[DevArray], DevArray]:
         if self._dev is None:
@@ -938,11 +957,83 @@ class TuckerTensor(Tensor):
 
     prepare_device = dev_parts
 
+    def dev_core_contiguous(self) -> DevArray:
+        """The device core in C order, as ``ttsk_tucker_gather`` reads it: the core itself, or for a strided view (``.T``)
+        a copy made on the device once and kept."""
+        core = self.dev_parts()[1]
+        if core.is_contiguous():
+            return core
+        if self._core_c is None or self._core_c[0] is not core:
+            self._core_c = (core, core.contiguous())
+        return self._core_c[1]
+
+    def resident(self) -> bool:
+        """True if the core and all factors live in HBM only; arithmetic on such a tensor stays on the device."""
+        return isinstance(self.core, DevArray) and all(isinstance(U, DevArray) for U in self.factors)
+
+    def to_device(self) -> "TuckerTensor":
+        """A resident copy: core and factors as device arrays (uploaded once, shared with this tensor's cache)."""
+        factors, core = self.dev_parts()
+        return TuckerTensor(list(factors), core, (factors, core))
+
+    def gather_dev(self, idx, route: Optional[str] = None) -> DevArray:
+        """Entries at the given multi-indices as a device array (N,): ``idx`` is a ``SparseTensor`` of this shape (its
+        resident index matrix is used in place), a ``(d, N)`` array or a tuple of ``d`` arrays.  ``route``: the switch of
+        ``paths.py`` between ``ttsk_tucker_gather`` and its composition."""
+        from .tensor_gather import _gather_device
+        return _gather_device(self, idx, True, False, route)[0]
+
+    def gather(self, idx, route: Optional[str] = None) -> npt.NDArray:
+        """Entries at the given multi-indices; on the device (``gather_dev``) for a resident tensor or a ``SparseTensor``
+        of indices, otherwise on the host mode by mode over chunks of the list: no dense array is formed."""
+        if self.resident() or isinstance(idx, SparseTensor):
+            return self.gather_dev(idx, route).get()
+        arr = np.stack(idx) if isinstance(idx, (tuple, list)) else np.asarray(idx)
+        if arr.ndim != 2 or arr.shape[0] != self.ndim:
+            raise ValueError(f"gather: {self.ndim} index rows expected, got an array of shape {arr.shape}")
+        core, N = _host(self.core), arr.shape[1]
+        out = np.empty(N)
+        chunk = max(1, (1 << 22) // max(1, core.size // max(1, core.shape[0])))
+        for lo in range(0, N, chunk):
+            sl = arr[:, lo:lo + chunk]
+            v = _host(self.factors[0])[:, sl[0]].T @ core.reshape(core.shape[0], -1)
+            for k in range(1, self.ndim):
+                v = np.einsum("esr,se->er", v.reshape(v.shape[0], core.shape[k], -1), _host(self.factors[k])[:, sl[k]])
+            out[lo:lo + chunk] = v[:, 0]
+        return out
+
+    def support_error(self, sparse: "SparseTensor", relative: bool = False, route: Optional[str] = None) -> float:
+        """``|| self[indices] - entries ||`` over all nonzeros of ``sparse`` in one device pass, as the method of
+        ``TensorTrain`` / ``CPTensor``.  ``relative``: divided by ``||entries||``."""
+        from .tensor_gather import _gather_device
+        err = float(np.sqrt(_gather_device(self, sparse, False, True, route)[1][2]))
+        return _error_tail(err, sparse.norm() if relative else None, None, relative, False)
+
+    def norm(self) -> float:
+        if _on_device(self):
+            from .tensor_tucker import tucker_dot
+            return float(np.sqrt(abs(tucker_dot(self, self))))
+        return super().norm()
+
+    def dot(self, other, reverse=False, route: Optional[str] = None) -> float:
+        """``<self, other>``.  Against a ``SparseTensor`` the one pass of ``SparseTensor.dot`` (``route``: its switch);
+        against a ``TuckerTensor``, a ``TensorTrain`` or a ``CPTensor`` with either operand on the device the products of
+        ``tensor_tucker``."""
+        if isinstance(other, SparseTensor) and (self.resident() or other._dev is not None):
+            return other.dot(self, route=route)
+        if isinstance(other, (TuckerTensor, TensorTrain, CPTensor)) and (_on_device(self) or _on_device(other)):
+            from . import tensor_tucker as tk
+            if isinstance(other, TuckerTensor):
+                return tk.tucker_dot(self, other)
+            return tk.tucker_tt_dot(self, other) if isinstance(other, TensorTrain) else tk.tucker_cp_dot(self, other)
+        return super().dot(other, reverse=reverse)
+
     @property
     def T(self) -> "TuckerTensor":
         axes = tuple(reversed(range(len(self.shape))))
         dev = None if self._dev is None else (self._dev[0][::-1], self._dev[1].transpose(axes))
-        return TuckerTensor(self.factors[::-1], np.transpose(self.core, axes), dev)
+        core = self.core.transpose(axes) if isinstance(self.core, DevArray) else np.transpose(self.core, axes)
+        return TuckerTensor(self.factors[::-1], core, dev)
 
     @property
     def size(self) -> int:
@@ -955,6 +1046,10 @@ class TuckerTensor(Tensor):
         return acc
 
     def __mul__(self, other: float) -> "TuckerTensor":
+        if isinstance(self.core, DevArray):
+            core = self.core.copy()
+            axpby(core, core, float(other), 0.0)
+            return TuckerTensor(self.factors, core)
         return TuckerTensor(self.factors, _host(self.core) * other)
 
     @classmethod

@@ -1,6 +1,8 @@
 """Evaluation of a ``TensorTrain`` / ``CPTensor`` at index lists: the device pass of ``csrc/tt_gather.hip``
 (``ttsk_tt_gather`` / ``ttsk_cp_gather``) and, for train ranks beyond its cover, the chain from
-``ttsk_sparse_ttdrm_step``.
+``ttsk_sparse_ttdrm_step``.  Of a ``TuckerTensor``: ``ttsk_tucker_gather`` (``csrc/tucker_gather.hip``)
+and, beyond its cover or under ``route="composed"``, column gathers of the factors and batched ``contract`` calls
+(DESIGN section 20).
 
 Entry point: ``_gather_device``, which ``gather_dev`` / ``support_error`` of the two classes and ``SparseTensor.dot``
 call.  ``_PANEL_BYTES`` is the memory budget of the composed fallback.
@@ -10,9 +12,11 @@ from __future__ import annotations
 import numpy as np
 
 from .device import DevArray, axpby, contract, copy_into
-from .tensor import SparseTensor, TensorTrain
+from .paths import resolve
+from .tensor import SparseTensor, TensorTrain, TuckerTensor
 
 _PANEL_BYTES = 256 << 20      # composed fallback: the two (chunk x rank) panels of a step stay below this
+_GEMM_MAX_BATCH = 65535       # problems of one ``ttsk_gemm`` call: the Tucker composition's tuples ride in its batch index
 
 
 def _gather_indices(idx, shape):
@@ -52,23 +56,80 @@ def _tt_gather_composed(cores, dev_idx, stride, order, N, val, want_out, want_st
         if want_out:
             copy_into(out[lo:lo + m], v.reshape(m))
         if want_stats:
-            x = val[lo:lo + m].reshape(m, 1)
-            res = v.copy()
-            axpby(res, x, -1.0, 1.0)                                   # t - x
-            for j, (a, b) in enumerate(((x, v), (v, v), (res, res))):
-                stats[j] += float(contract("ka,kb->ab", a, b).get()[0, 0])
+            _chunk_stats(stats, v, val[lo:lo + m].reshape(m, 1))
     return out, stats
 
 
-def _gather_device(tensor, idx, want_out: bool, want_stats: bool):
-    """One pass of ``ttsk_tt_gather`` / ``ttsk_cp_gather`` over an index list: (DevArray (N,) or None, the three sums
-    (x . t, t . t, |t - x|^2) as a host array or None).  Nothing of the tensor or the list is downloaded."""
+def _chunk_stats(stats, v, x):
+    """adds (x . v, v . v, |v - x|^2) of a chunk, ``v`` and ``x`` device arrays (m, 1), to the host sums"""
+    res = v.copy()
+    axpby(res, x, -1.0, 1.0)                                           # v - x
+    for j, (a, b) in enumerate(((x, v), (v, v), (res, res))):
+        stats[j] += float(contract("ka,kb->ab", a, b).get()[0, 0])
+
+
+def _tucker_gather_composed(factors, core, shape, dev_idx, stride, order, N, val, want_out, want_stats):
+    """A Tucker tensor at an index list without the fused kernel: per mode the columns ``U_k[:, i_k(e)]`` by
+    ``ttsk_sparse_densedrm_gather`` (one index row, ``m = 1``), the core contracted with them mode by mode with the tuple
+    as the batch index.  Chunks of the list keep the widest panel (chunk x prod_{k >= 1} s_k) under ``_PANEL_BYTES`` and the
+    batch of a ``contract`` call under ``_GEMM_MAX_BATCH``."""
     import ctypes
     from . import _native as nat
+    ranks, d = core.shape, len(shape)
+    rest = core.size // ranks[0]
+    chunk = max(1, min(_GEMM_MAX_BATCH, _PANEL_BYTES // (16 * max(rest, max(ranks)))))
+    out = DevArray.empty((N,)) if want_out else None
+    stats = np.zeros(3) if want_stats else None
+    for lo in range(0, N, chunk):
+        m = min(chunk, N - lo)
+        cols = []
+        for k in range(d):
+            G = DevArray.empty((m, ranks[k]))
+            nat.call("ttsk_sparse_densedrm_gather", factors[k], ranks[k], shape[k], dev_idx[:, lo:lo + m], stride,
+                     (ctypes.c_int * 1)(order[k]), nat.i64_array(shape[k:k + 1]), 1, m, G, 0)
+            cols.append(G)
+        v = contract("es,sr->er", cols[0], core.reshape(ranks[0], rest))
+        for k in range(1, d):
+            v = contract("esr,es->er", v.reshape(m, ranks[k], -1), cols[k])
+        if want_out:
+            copy_into(out[lo:lo + m], v.reshape(m))
+        if want_stats:
+            _chunk_stats(stats, v, val[lo:lo + m].reshape(m, 1))
+    return out, stats
+
+
+def _tucker_gather(tensor, dev_idx, stride, order, N, val, want_out, want_stats, route):
+    import ctypes
+    from . import _native as nat
+    d = tensor.ndim
+    factors = [U.contiguous() for U in tensor.dev_parts()[0]]
+    core = tensor.dev_core_contiguous()
+    if route != "composed":
+        out = DevArray.empty((N,)) if want_out else None
+        stats = DevArray.empty((3,)) if want_stats else None
+        try:
+            nat.call("ttsk_tucker_gather", core, nat.ptr_array(factors), nat.i64_array(tensor.rank), nat.i64_array(tensor.shape), d,
+                     dev_idx, stride, (ctypes.c_int * d)(*order), N, val if want_stats else None, out, stats, 0)
+            return out, (stats.get() if want_stats else None)
+        except nat.TtskUnsupported:
+            if route == "kernel":
+                raise
+    return _tucker_gather_composed(factors, core, tensor.shape, dev_idx, stride, order, N, val, want_out, want_stats)
+
+
+def _gather_device(tensor, idx, want_out: bool, want_stats: bool, route=None):
+    """One pass of ``ttsk_tt_gather`` / ``ttsk_cp_gather`` / ``ttsk_tucker_gather`` over an index list: (DevArray (N,) or
+    None, the three sums (x . t, t . t, |t - x|^2) as a host array or None).  Nothing of the tensor or the list is
+    downloaded.  ``route``: the switch of ``paths.py``, for a ``TuckerTensor``."""
+    import ctypes
+    from . import _native as nat
+    route = resolve(route)
     dev_idx, stride, order, N, val = _gather_indices(idx, tensor.shape)
     if want_stats and val is None:
         raise ValueError("gather: the sums need the entries of a SparseTensor")
     d = tensor.ndim
+    if isinstance(tensor, TuckerTensor):
+        return _tucker_gather(tensor, dev_idx, stride, order, N, val, want_out, want_stats, route)
     cores = [c.contiguous() for c in tensor.dev_cores()]
     out = DevArray.empty((N,)) if want_out else None
     stats = DevArray.empty((3,)) if want_stats else None
