@@ -404,6 +404,30 @@ int ttsk_op_apply(int K, const double *const *L, const double *const *M, const d
 int ttsk_hadamard_apply(const double *L, const double *X, const double *Y, const int64_t *dims, const int64_t *strides,
                         double *W, int64_t w_cols, int64_t w_off, int stream);
 
+/* ---- inner product of two such products: the closing half of a mode (csrc/hadamard_close.hip, plan in
+ * csrc/hadamard_close_plan.h) ----
+ * <x o y, u o v> carries a chain G (R, r, S, s) over the ranks of x, y, u and v.  Per mode, ttsk_hadamard_apply with
+ * l = S s takes G through the cores of x and y: Wl ((gamma c), i, p) with p = (beta' a').  This entry takes Wl through the cores
+ * U (S, n, S') of u and V (s, n, s') of v and sums over the mode:
+ *   out[p, gamma' s' + c'] (+)= sum_{i < n} sum_gamma U[gamma, i, gamma'] sum_c Wl[(gamma s + c), i, p] V[c, i, c'];
+ * the inner sum stays on the chip and no array indexed by i is written.
+ *   Wl            contiguous (S s, n, P)
+ *   U, V          strided: (S, n, S') and (s, n, s')
+ *   dims          S, S', s, s', n, P
+ *   strides       in elements: U over (gamma, i, gamma'), then V over (c, i, c')
+ *   out           contiguous (P, S' s'); accumulate = 1 adds to what it holds
+ *   work          a slab of the caller's, work_doubles doubles, at least what ttsk_hadamard_close_layout names; every double
+ *                 of that size is overwritten
+ * The mode is cut into ichunks ranges of i so that few (p, c', gamma') tiles still fill the device; a workgroup writes its
+ * partial tile to work (ichunks, P, S' s') and ttsk_sum_slices adds the slices in ascending order into out.  The cut depends
+ * on dims alone.  No atomics: the same bits on every call.  TTSK_ERR_ARG: a NULL pointer, an extent below 1, accumulate
+ * not 0 or 1, a slab smaller than the plan's.  TTSK_ERR_UNSUPPORTED: an extent or the number of workgroups (ichunks x
+ * ceil(P / 16) x ceil(s' / 16) x ceil(S' / 64)) of 2^31 or more.  A refused call launches nothing and writes nothing.  Inside those bounds every shape runs. */
+int ttsk_hadamard_close(const double *Wl, const double *U, const double *V, const int64_t *dims, const int64_t *strides, double *out,
+                        int accumulate, double *work, int64_t work_doubles, int stream);
+/* The plan's numbers for those dims (host only): out[0] = ichunks, out[1] = doubles of the slab */
+int ttsk_hadamard_close_layout(const int64_t *dims, int64_t *out);
+
 /* ---- CP tensors against tensor-train DRMs, no panels (csrc/cp_pass.hip, plan in csrc/cp_pass_plan.h) ----
  * A CP tensor of rank N has factor matrices V_mu (n x N).  The step of TensorTrainDRM.sketch_cp (tensor_train_drm.py:90-107)
  * and the Psi / Omega of cp_sketch.py:6-36 are one GEMM each whose Khatri-Rao operand is formed in registers; the N x n x

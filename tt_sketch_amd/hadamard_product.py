@@ -17,7 +17,7 @@ import numpy as np
 from . import _native as nat
 from .device import DevArray, contract, copy_into
 from .paths import resolve, taken
-from .tensor import Tensor, TensorSum, TensorTrain, _host
+from .tensor import DenseTensor, Tensor, TensorSum, TensorTrain, _error_tail, _fast_error, _host
 
 # The routing rule of DESIGN section 15, its constants measured on one MI355X (profiles/hadamard_sketch_bench.json, the
 # four shapes of hadamard_apply alone): a ttsk_hadamard_apply call costs its floor or its flops at the kernel's rate,
@@ -127,6 +127,36 @@ class HadamardProduct(Tensor):
 
     def to_numpy(self):
         return self.to_tt().to_numpy()
+
+    # -- inner products, norm and fast error on the factors alone (hadamard_gram.py)
+    def dot(self, other, reverse=False, route: Optional[str] = None) -> float:
+        """``<self, other>`` against a ``TensorTrain`` or another ``HadamardProduct`` by a chain over the factors' cores: no
+        Kronecker core and no dense array is formed, on the device when a factor is there and in NumPy otherwise.  ``route`` is
+        the switch of ``paths.py`` for the closing step against a product (``hadamard_gram.hadamard_close``).  Every other
+        partner goes through the base class."""
+        if isinstance(other, HadamardProduct):
+            from .hadamard_gram import hadamard_dot
+            return hadamard_dot(self, other, route)
+        if isinstance(other, TensorTrain):
+            from .hadamard_gram import hadamard_tt_dot
+            return hadamard_tt_dot(self, other)
+        return super().dot(other, reverse=reverse)
+
+    def error(self, other, relative: bool = False, rmse: bool = False, fast: bool = False) -> float:
+        """``||self - other||``.  ``fast=True`` is the reference's formula on ``<self, self>``, ``<self, other>`` and
+        ``<other, other>``, which form nothing dense against trains and Hadamard products (or sums of them); it has that
+        formula's floor of about 1e-8 relative.  ``fast=False`` keeps the dense difference of the base class."""
+        if not fast:
+            return super().error(other, relative=relative, rmse=rmse, fast=False)
+        if isinstance(other, np.ndarray):
+            other = DenseTensor(other)
+        aa, ab, bb = self.dot(self), self.dot(other), other.dot(other)
+        err = float(_fast_error(aa, ab, bb)) if aa + bb > 0 else 0.0
+        return float(_error_tail(err, float(np.sqrt(abs(bb))), self.shape, relative, rmse))
+
+    def gather(self, idx) -> np.ndarray:
+        """Entries at the given multi-indices: those of the two factors, multiplied on the host."""
+        return self.x.gather(idx) * self.y.gather(idx)
 
     def __mul__(self, other: float) -> "HadamardProduct":
         return HadamardProduct(self.x, self.y * other)

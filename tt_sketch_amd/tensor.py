@@ -774,7 +774,15 @@ class TensorTrain(_CoreList, Tensor):
         Against a ``CPTensor`` (or a ``TensorSum`` that holds one) ``fast=True`` is the reference's formula on
         ``self.norm()``, ``other.norm()`` and ``self.dot(other)``, which stay on the device when either side is there
         (``cp_gram``, ``_tt_cp_dot``) and form no dense array; that formula has the reference's floor of about 1e-8
-        relative.  ``fast=False`` against CP keeps the reference's dense formula."""
+        relative.  ``fast=False`` against CP keeps the reference's dense formula.
+
+        Against a ``HadamardProduct`` ``fast=True`` is the same formula on three chains over the factors' cores
+        (``hadamard_gram``): the product's Kronecker cores are not formed."""
+        from .hadamard_product import HadamardProduct
+        if fast and isinstance(other, HadamardProduct):
+            aa, ab, bb = self.dot(self), other.dot(self), other.dot(other)
+            err = float(_fast_error(aa, ab, bb)) if aa + bb > 0 else 0.0
+            return float(_error_tail(err, float(np.sqrt(abs(bb))), self.shape, relative, rmse))    # sqrt|bb| is other.norm()
         if hasattr(other, "to_tt"):
             other = other.to_tt()
         dense = DenseTensor(other) if isinstance(other, np.ndarray) else other
