@@ -1,9 +1,10 @@
 """Register / scratch / occupancy table of every chain-step kernel instantiation, and the comparison of two such tables.
 
-  python profiles/scripts/chain_resources.py table [--csrc DIR] [--jobs N] OUT.json
+  python profiles/scripts/chain_resources.py table [--csrc DIR] [--jobs N] [--units PATTERN ...] OUT.json
       compiles the device side of every chain_fused_i*.hip, chain_wide_i*.hip and chain_sum_i*.hip of DIR (default: this
       tree's tt_sketch_amd/csrc) for gfx950 with -Rpass-analysis=kernel-resource-usage and records, per kernel:
       SGPRs, VGPRs, AGPRs, ScratchSize, Occupancy, SGPR and VGPR spills, LDS size.  No GPU needed.
+      --units names other units by glob patterns, e.g. hadamard_apply.hip hadamard_close.hip op_apply.hip.
   python profiles/scripts/chain_resources.py compare PARENT.json NEW.json
       the rule a restructuring of these kernels has to keep: per kernel equal ScratchSize and spill counts, occupancy not
       lower; lists every kernel whose VGPR count moved by more than 8.  Exit status 1 if the rule is broken.
@@ -62,12 +63,15 @@ def demangle(name):
     return _demangled[name]
 
 
-def table(csrc, jobs, out, only=None):
-    srcs = sorted(s for pat in ("chain_fused_i*.hip", "chain_wide_i*.hip", "chain_sum_i*.hip") for s in glob.glob(os.path.join(csrc, pat)))
+CHAIN_UNITS = ("chain_fused_i*.hip", "chain_wide_i*.hip", "chain_sum_i*.hip")
+
+
+def table(csrc, jobs, out, only=None, units=CHAIN_UNITS):
+    srcs = sorted(s for pat in units for s in glob.glob(os.path.join(csrc, pat)))
     if only:
         srcs = [s for s in srcs if re.search(only, os.path.basename(s))]
     if not srcs:
-        raise SystemExit(f"no chain-step instantiation units under {csrc}")
+        raise SystemExit(f"no unit matches {' '.join(units)} under {csrc}")
     kernels = {}
     with concurrent.futures.ThreadPoolExecutor(jobs) as ex:
         for src, t in zip(srcs, ex.map(lambda s: unit_table(s, csrc), srcs)):
@@ -114,13 +118,14 @@ def main():
     t.add_argument("--csrc", default=os.path.join(ROOT, "tt_sketch_amd", "csrc"))
     t.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     t.add_argument("--only", default=None, help="regular expression: only the units whose file name matches")
+    t.add_argument("--units", nargs="+", default=CHAIN_UNITS, metavar="PATTERN", help="glob patterns of the units under --csrc")
     t.add_argument("out")
     c = sub.add_parser("compare")
     c.add_argument("parent")
     c.add_argument("new")
     a = ap.parse_args()
     if a.cmd == "table":
-        table(a.csrc, a.jobs, a.out, a.only)
+        table(a.csrc, a.jobs, a.out, a.only, a.units)
     else:
         sys.exit(compare(a.parent, a.new))
 

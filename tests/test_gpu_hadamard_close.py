@@ -3,7 +3,8 @@
 ``gather`` and ``TensorTrain.error(fast=True)`` on resident trains against dense NumPy.
 
 Bar of the entry (tests/hadamard_close_ref.py): |G' - G'_ref| <= 2 (s + S + n + 3) 2^-53 G'_abs entry by entry, the same bits on
-a second call, nothing written past the plan's slab.  Bars of the surface: inner products within 1e-12 ||a|| ||b||, the fast
+a second call, nothing written past the plan's slab; at n = 1 the floats of ``ttsk_hadamard_apply`` on the same operands
+(both kernels run the stages of csrc/hadamard_stages.h).  Bars of the surface: inner products within 1e-12 ||a|| ||b||, the fast
 error within 1e-10 of the dense one on tensors at a relative distance of 0.1 or more.
 """
 import ctypes
@@ -15,6 +16,7 @@ import pytest
 
 from oracle import ttsk_oracle as orc
 from tests import hadamard_close_ref as ref
+from tests import hadamard_ref as apply_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -95,6 +97,24 @@ def test_c_entry_vs_restatement(tsa, truth, case):
         assert (np.abs((got - out0) - ref.close_term(Wl, U, V)) <= tol).all()
     rc2, got2, work2 = c_hadamard_close(Wl, U, V, out0)
     assert rc2 == 0 and np.array_equal(got, got2) and np.array_equal(work, work2, equal_nan=True)     # the same bits on every call
+
+
+@pytest.mark.parametrize("case", apply_ref.CASES, ids=lambda c: c.name)
+def test_one_mode_of_close_is_apply_bit_for_bit(tsa, case):
+    """The two kernels run the same stages (csrc/hadamard_stages.h).  At n = 1 the plan makes one chunk of i and
+    ttsk_sum_slices adds a single slice, so closing Wl = L (R r, 1, l) with mode i of X and Y performs the matrix
+    instructions of ttsk_hadamard_apply at that i in the same order: the same floats, +0 and -0 taken as equal."""
+    from tests.test_gpu_hadamard import c_hadamard_apply
+    L, X, Y, w_off, w_cols = apply_ref.case_arrays(case)
+    rc, W = c_hadamard_apply(L, X, Y, w_off, w_cols)
+    assert rc == 0
+    assert ref.layout(case.R, case.R1, case.r, case.r1, 1, case.l)[0] == 1          # one chunk of i
+    for i in sorted({0, case.n - 1}):
+        rc, out, _ = c_hadamard_close(L.reshape(case.R * case.r, 1, case.l), X[:, i:i + 1, :], Y[:, i:i + 1, :], None)
+        assert rc == 0
+        want = W[:, i, w_off:w_off + case.R1 * case.r1]
+        print(f"{case.name}, i = {i}: {np.count_nonzero(out != want)} of {want.size} floats differ")
+        assert np.array_equal(out, want), i
 
 
 # ---- 2. the ABI

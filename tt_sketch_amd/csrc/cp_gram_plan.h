@@ -27,7 +27,6 @@ constexpr int CPG_KC = 16;                       // rows i of a mode's two slabs
 constexpr int CPG_PITCH = 80;                    // doubles per slab row: 32 modulo 64 dwords, so the two rows a half-wave reads fall on disjoint banks
 constexpr int CPG_WG_PER_CU = 3;                 // grid cap: three workgroups (three waves per SIMD) per compute unit, which registers and LDS allow
 constexpr size_t CPG_LDS = (size_t)2 * 2 * CPG_KC * CPG_PITCH * 8;      // two buffers of (A slab, B slab)
-constexpr int64_t CPG_MAX_EXTENT = (1ll << 31) - 1;
 // additions a term passes inside one tile: 16 accumulator registers of a lane one by one, the 6 butterfly steps of a
 // wave, the four waves as (w0 + w1) + (w2 + w3)
 constexpr int CPG_TILE_SUMS = 16 + 6 + 2;
@@ -81,34 +80,32 @@ struct CpGramPlan {
     char msg[200];               // why not, when the status is not TTSK_OK
 };
 
-#define CPG_PLAN_FAIL(status, ...) do { snprintf(p->msg, sizeof(p->msg), __VA_ARGS__); return status; } while (0)
-
 inline int cp_gram_plan(const double *const *dev_a, const int64_t *lda, int64_t N, const double *const *dev_b, const int64_t *ldb, int64_t M,
                         const int64_t *shape, int d, int sym, double *dev_out, int n_cu, CpGramPlan *p)
 {
     *p = CpGramPlan{};
-    if (!dev_a || !lda || !dev_b || !ldb || !shape || !dev_out) CPG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: NULL argument");
-    if (d < 1) CPG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: d = %d must be positive", d);
-    if (d > CPG_MAX_MODES) CPG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_gram: %d modes, at most %d are covered", d, CPG_MAX_MODES);
-    if (N < 1 || M < 1) CPG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: N = %lld, M = %lld must be positive", (long long)N, (long long)M);
+    if (!dev_a || !lda || !dev_b || !ldb || !shape || !dev_out) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: NULL argument");
+    if (d < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: d = %d must be positive", d);
+    if (d > CPG_MAX_MODES) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_gram: %d modes, at most %d are covered", d, CPG_MAX_MODES);
+    if (N < 1 || M < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: N = %lld, M = %lld must be positive", (long long)N, (long long)M);
     for (int k = 0; k < d; ++k)
-        if (shape[k] < 1) CPG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: mode %d has size %lld", k, (long long)shape[k]);
+        if (shape[k] < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: mode %d has size %lld", k, (long long)shape[k]);
     for (int k = 0; k < d; ++k) {
-        if (!dev_a[k] || !dev_b[k]) CPG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: factor %d is NULL", k);
+        if (!dev_a[k] || !dev_b[k]) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: factor %d is NULL", k);
         if (lda[k] < N || ldb[k] < M)
-            CPG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: leading dimensions %lld, %lld of mode %d below N = %lld, M = %lld", (long long)lda[k],
-                          (long long)ldb[k], k, (long long)N, (long long)M);
+            PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: leading dimensions %lld, %lld of mode %d below N = %lld, M = %lld", (long long)lda[k],
+                      (long long)ldb[k], k, (long long)N, (long long)M);
     }
     if (sym) {
-        if (M != N) CPG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: sym with N = %lld, M = %lld", (long long)N, (long long)M);
+        if (M != N) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: sym with N = %lld, M = %lld", (long long)N, (long long)M);
         for (int k = 0; k < d; ++k)
-            if (dev_b[k] != dev_a[k] || ldb[k] != lda[k]) CPG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: sym, but factor %d of b is not that of a", k);
+            if (dev_b[k] != dev_a[k] || ldb[k] != lda[k]) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_gram: sym, but factor %d of b is not that of a", k);
     }
     // ---- the cover
-    if (N > CPG_MAX_EXTENT || M > CPG_MAX_EXTENT) CPG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_gram: N or M of 2^31 or more; below 2^31 is covered");
+    if (N > PLAN_MAX_EXTENT || M > PLAN_MAX_EXTENT) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_gram: N or M of 2^31 or more; below 2^31 is covered");
     for (int k = 0; k < d; ++k)
-        if (shape[k] > CPG_MAX_EXTENT)
-            CPG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_gram: mode %d of size %lld, below 2^31 is covered", k, (long long)shape[k]);
+        if (shape[k] > PLAN_MAX_EXTENT)
+            PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_gram: mode %d of size %lld, below 2^31 is covered", k, (long long)shape[k]);
     CpGramArgs &a = p->a;
     int64_t sum_n = 0;
     for (int k = 0; k < d; ++k) {
@@ -130,7 +127,5 @@ inline int cp_gram_plan(const double *const *dev_a, const int64_t *lda, int64_t 
     p->depth = sum_n + (d - 1) + CPG_TILE_SUMS + p->run + cdiv(p->grid, 256) + CPG_CLOSE_SUMS;
     return TTSK_OK;
 }
-
-#undef CPG_PLAN_FAIL
 
 }  // namespace ttsk

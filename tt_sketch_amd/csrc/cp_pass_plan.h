@@ -9,11 +9,11 @@
 #include <cstdint>
 #include <cstdio>
 #include "ttsk.h"
+#include "plan_common.h"
 
 namespace ttsk {
 
 constexpr int CP_MAX_RANK = 128;                 // rho, rho', l, r of the cover
-constexpr int64_t CP_MAX_EXTENT = (1ll << 31) - 1;
 constexpr int64_t CP_MAX_BLOCKS = (1ll << 31) - 1;
 
 // ---- chain step: out (N x rho') = A (N x rho n) D (rho n x rho'), A[j, (a, k)] = L[j, a] V[k, j] formed in registers
@@ -47,26 +47,24 @@ struct CpChainPlan {
     char msg[200];               // why not, when the status is not TTSK_OK
 };
 
-#define CP_PLAN_FAIL(status, ...) do { snprintf(p->msg, sizeof(p->msg), __VA_ARGS__); return status; } while (0)
-
 inline int cp_chain_plan(const double *L, int64_t ldl, const double *V, int64_t v_k, int64_t v_j, const double *D, double *out, int64_t ldo,
                          int64_t N, int64_t rho, int64_t n, int64_t rho1, CpChainPlan *p)
 {
     *p = CpChainPlan{};
-    if (!V || !D || !out) CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_chain_step: NULL argument");
+    if (!V || !D || !out) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_chain_step: NULL argument");
     if (N < 1 || rho < 1 || n < 1 || rho1 < 1)
-        CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_chain_step: N = %lld, rho = %lld, n = %lld, rho' = %lld must be positive", (long long)N, (long long)rho,
-                     (long long)n, (long long)rho1);
-    if (!L && rho != 1) CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_chain_step: no L stands for rho = 1, not %lld", (long long)rho);
-    if (L && ldl < rho) CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_chain_step: leading dimension %lld of L below rho = %lld", (long long)ldl, (long long)rho);
-    if (ldo < rho1) CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_chain_step: leading dimension %lld of out below rho' = %lld", (long long)ldo, (long long)rho1);
+        PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_chain_step: N = %lld, rho = %lld, n = %lld, rho' = %lld must be positive", (long long)N, (long long)rho,
+                  (long long)n, (long long)rho1);
+    if (!L && rho != 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_chain_step: no L stands for rho = 1, not %lld", (long long)rho);
+    if (L && ldl < rho) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_chain_step: leading dimension %lld of L below rho = %lld", (long long)ldl, (long long)rho);
+    if (ldo < rho1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_chain_step: leading dimension %lld of out below rho' = %lld", (long long)ldo, (long long)rho1);
     // ---- the cover
     if (rho > CP_MAX_RANK || rho1 > CP_MAX_RANK)
-        CP_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_chain_step: rank %lld; up to %d is covered", (long long)(rho > CP_MAX_RANK ? rho : rho1), CP_MAX_RANK);
-    if (N > CP_MAX_EXTENT || n > CP_MAX_EXTENT) CP_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_chain_step: N or n of 2^31 or more; below 2^31 is covered");
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_chain_step: rank %lld; up to %d is covered", (long long)(rho > CP_MAX_RANK ? rho : rho1), CP_MAX_RANK);
+    if (N > PLAN_MAX_EXTENT || n > PLAN_MAX_EXTENT) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_chain_step: N or n of 2^31 or more; below 2^31 is covered");
     // the kernel's 32-bit row counters of D run up to two stages past rho n
-    if (rho * n > CP_MAX_EXTENT - 2 * CP_KC)
-        CP_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_chain_step: rho n = %lld; up to 2^31 - %d is covered", (long long)(rho * n), 2 * CP_KC + 1);
+    if (rho * n > PLAN_MAX_EXTENT - 2 * CP_KC)
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_chain_step: rho n = %lld; up to 2^31 - %d is covered", (long long)(rho * n), 2 * CP_KC + 1);
     CpChainArgs &a = p->a;
     a.L = L; a.V = V; a.D = D; a.out = out;
     a.ldl = L ? ldl : 0; a.v_k = v_k; a.v_j = v_j; a.ldo = ldo;
@@ -118,24 +116,24 @@ inline int cp_psi_plan(const double *L, int64_t ldl, const double *R, int64_t ld
                        const double *R_om, int64_t ld_om, int64_t r_om, double *omega, int64_t N, int64_t l, int64_t n, int64_t r, CpPsiPlan *p)
 {
     *p = CpPsiPlan{};
-    if (!psi && !omega) CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: NULL output: neither psi nor omega");
-    if (psi && !V) CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: NULL factor matrix V");
+    if (!psi && !omega) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: NULL output: neither psi nor omega");
+    if (psi && !V) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: NULL factor matrix V");
     if (N < 1 || l < 1 || r < 1 || (psi && n < 1))
-        CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: N = %lld, l = %lld, n = %lld, r = %lld must be positive", (long long)N, (long long)l,
-                     (long long)n, (long long)r);
-    if (!L && l != 1) CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: no L stands for l = 1, not %lld", (long long)l);
-    if (!R && r != 1) CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: no R stands for r = 1, not %lld", (long long)r);
-    if (L && ldl < l) CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: leading dimension %lld of L below l = %lld", (long long)ldl, (long long)l);
-    if (R && ldr < r) CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: leading dimension %lld of R below r = %lld", (long long)ldr, (long long)r);
+        PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: N = %lld, l = %lld, n = %lld, r = %lld must be positive", (long long)N, (long long)l,
+                  (long long)n, (long long)r);
+    if (!L && l != 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: no L stands for l = 1, not %lld", (long long)l);
+    if (!R && r != 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: no R stands for r = 1, not %lld", (long long)r);
+    if (L && ldl < l) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: leading dimension %lld of L below l = %lld", (long long)ldl, (long long)l);
+    if (R && ldr < r) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: leading dimension %lld of R below r = %lld", (long long)ldr, (long long)r);
     if (!R_om) { R_om = R; ld_om = ldr; r_om = r; }
     if (!omega) r_om = 0;
     if (omega && (r_om < 1 || ld_om < r_om))
-        CP_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: Omega's right operand has r = %lld, leading dimension %lld", (long long)r_om, (long long)ld_om);
+        PLAN_FAIL(TTSK_ERR_ARG, "ttsk_cp_psi_omega: Omega's right operand has r = %lld, leading dimension %lld", (long long)r_om, (long long)ld_om);
     // ---- the cover
     if (l > CP_MAX_RANK || r > CP_MAX_RANK || r_om > CP_MAX_RANK)
-        CP_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_psi_omega: rank %lld; up to %d is covered", (long long)(l > CP_MAX_RANK ? l : r > CP_MAX_RANK ? r : r_om),
-                     CP_MAX_RANK);
-    if (N > CP_MAX_EXTENT || (psi && n > CP_MAX_EXTENT)) CP_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_psi_omega: N or n of 2^31 or more; below 2^31 is covered");
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_psi_omega: rank %lld; up to %d is covered", (long long)(l > CP_MAX_RANK ? l : r > CP_MAX_RANK ? r : r_om),
+                  CP_MAX_RANK);
+    if (N > PLAN_MAX_EXTENT || (psi && n > PLAN_MAX_EXTENT)) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_psi_omega: N or n of 2^31 or more; below 2^31 is covered");
     CpPsiArgs &a = p->a;
     a.L = L; a.R = R; a.V = V; a.Ro = omega ? R_om : nullptr; a.psi = psi; a.omega = omega;
     a.ldl = L ? ldl : 0; a.ldr = R ? ldr : 0; a.ldro = a.Ro ? ld_om : 0; a.v_k = v_k; a.v_j = v_j;
@@ -145,24 +143,22 @@ inline int cp_psi_plan(const double *L, int64_t ldl, const double *R, int64_t ld
     const int64_t cblocks = (a.cols + CP_PSI_COLS - 1) / CP_PSI_COLS;    // below 2^32
     const int64_t chunks = (N + CP_N_CHUNK - 1) / CP_N_CHUNK;            // below 2^22
     if (cblocks > CP_MAX_BLOCKS || cblocks * chunks > CP_MAX_BLOCKS)
-        CP_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_psi_omega: %lld column blocks x %lld chunks of N; up to 2^31 - 1 workgroups are covered",
-                     (long long)cblocks, (long long)chunks);
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_psi_omega: %lld column blocks x %lld chunks of N; up to 2^31 - 1 workgroups are covered",
+                  (long long)cblocks, (long long)chunks);
     a.cblocks = (int)cblocks; a.chunks = (int)chunks;
     p->blocks = cblocks * chunks;
     const int64_t out_elems = l * a.cols;                                // below 2^46
     if (chunks > 1) {
         if (out_elems > (int64_t)(((size_t)-1 >> 1) / 8) / chunks)
-            CP_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_psi_omega: the partials of %lld chunks are not addressable", (long long)chunks);
+            PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_psi_omega: the partials of %lld chunks are not addressable", (long long)chunks);
         p->ws_bytes = (size_t)chunks * (size_t)out_elems * 8;
         p->reduce_blocks = (out_elems + CP_REDUCE_THREADS - 1) / CP_REDUCE_THREADS;
-        if (p->reduce_blocks > CP_MAX_BLOCKS) CP_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_psi_omega: more than 2^31 workgroups in the closing sum");
+        if (p->reduce_blocks > CP_MAX_BLOCKS) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_cp_psi_omega: more than 2^31 workgroups in the closing sum");
     }
     p->flops = 2.0 * (double)l * (double)N * (double)a.cols;
     p->bytes = 8.0 * ((double)N * (L ? l : 0) + (double)N * (R && psi ? r : 0) + (double)N * (a.Ro && a.Ro != R ? r_om : 0) + (psi ? (double)N * n : 0.0) +
                       (double)out_elems) + 2.0 * (double)p->ws_bytes;
     return TTSK_OK;
 }
-
-#undef CP_PLAN_FAIL
 
 }  // namespace ttsk

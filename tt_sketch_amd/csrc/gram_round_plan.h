@@ -104,29 +104,27 @@ struct GramRoundPlan {
     char msg[200];                    // why not, when the status is not TTSK_OK
 };
 
-#define GRB_PLAN_FAIL(status, ...) do { snprintf(p->msg, sizeof(p->msg), __VA_ARGS__); return status; } while (0)
-
 inline int gram_round_plan(const double *const *dev_gl, const double *const *dev_gr, const int64_t *ranks, const int64_t *caps, int count,
                            double eps, double *const *dev_pt, double *const *dev_q, double *const *dev_sigma, int *dev_rank_out,
                            GramRoundPlan *p)
 {
     *p = GramRoundPlan{};
     if (!dev_gl || !dev_gr || !ranks || !caps || !dev_pt || !dev_q || !dev_sigma || !dev_rank_out)
-        GRB_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_gram_round_bonds: NULL argument");
-    if (count < 1) GRB_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_gram_round_bonds: count = %d must be positive", count);
-    if (!(eps >= 0.0) || std::isinf(eps)) GRB_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_gram_round_bonds: eps = %g must be finite and not negative", eps);
+        PLAN_FAIL(TTSK_ERR_ARG, "ttsk_gram_round_bonds: NULL argument");
+    if (count < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_gram_round_bonds: count = %d must be positive", count);
+    if (!(eps >= 0.0) || std::isinf(eps)) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_gram_round_bonds: eps = %g must be finite and not negative", eps);
     if (count > GRB_MAX_BONDS)
-        GRB_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_gram_round_bonds: %d bonds, at most %d are covered", count, GRB_MAX_BONDS);
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_gram_round_bonds: %d bonds, at most %d are covered", count, GRB_MAX_BONDS);
     for (int b = 0; b < count; ++b) {
         if (ranks[b] < 1 || caps[b] < 1)
-            GRB_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_gram_round_bonds: bond %d has rank %lld and cap %lld", b, (long long)ranks[b], (long long)caps[b]);
+            PLAN_FAIL(TTSK_ERR_ARG, "ttsk_gram_round_bonds: bond %d has rank %lld and cap %lld", b, (long long)ranks[b], (long long)caps[b]);
         if (!dev_gl[b] || !dev_gr[b] || !dev_pt[b] || !dev_q[b] || !dev_sigma[b])
-            GRB_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_gram_round_bonds: a NULL pointer at bond %d", b);
+            PLAN_FAIL(TTSK_ERR_ARG, "ttsk_gram_round_bonds: a NULL pointer at bond %d", b);
     }
     for (int b = 0; b < count; ++b)
         if (ranks[b] > GRB_MAX_RANK)
-            GRB_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_gram_round_bonds: bond %d has rank %lld, at most %d is covered (one workgroup per bond)", b,
-                          (long long)ranks[b], GRB_MAX_RANK);
+            PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_gram_round_bonds: bond %d has rank %lld, at most %d is covered (one workgroup per bond)", b,
+                      (long long)ranks[b], GRB_MAX_RANK);
     GramRoundArgs &a = p->a;
     int64_t at = 0;
     for (int b = 0; b < count; ++b) {
@@ -151,7 +149,5 @@ inline int gram_round_plan(const double *const *dev_gl, const double *const *dev
     p->scratch = (size_t)at * 8;
     return TTSK_OK;
 }
-
-#undef GRB_PLAN_FAIL
 
 }  // namespace ttsk

@@ -14,8 +14,8 @@
 
 namespace ttsk {
 
-// The stages are those of hadamard_apply: gamma in chunks of HD_KC through LDS at HD_PITCH, HD_COLS values of gamma' per
-// workgroup, HD_LDS bytes.  What is new is the split of the mode: the kernel sums over i, so i is not a grid index that
+// The stages are those of hadamard_apply (hadamard_stages.h): gamma in chunks of HD_KC through LDS at HD_PITCH, HD_COLS
+// values of gamma' per workgroup, HD_LDS bytes.  What is new is the split of the mode: the kernel sums over i, so i is not a grid index that
 // comes for free.  A (p, c', gamma') tile count below HC_FILL is multiplied by cutting i into chunks until the grid holds
 // HC_FILL workgroups: two per compute unit of a 256-CU device, which is what the kernel's registers and LDS allow to be
 // resident.  Where the grid then ends in a round of HC_FILL that is less than nine tenths full, i is cut once more, up to
@@ -45,28 +45,24 @@ struct HadamardClosePlan {
     char msg[200];               // why not, when the status is not TTSK_OK
 };
 
-#define HC_PLAN_FAIL(status, ...) do { snprintf(p->msg, sizeof(p->msg), __VA_ARGS__); return status; } while (0)
-
 // The part of the plan that needs no pointers: dims are S, S', s, s', n, P.  ttsk_hadamard_close_layout is this.
 inline int hadamard_close_layout(const int64_t *dims, HadamardClosePlan *p)
 {
     static const char *const names[6] = {"S", "S'", "s", "s'", "n", "P"};
     *p = HadamardClosePlan{};
-    if (!dims) HC_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_close: NULL argument");
-    for (int i = 0; i < 6; ++i)
-        if (dims[i] < 1) HC_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_close: %s = %lld must be positive", names[i], (long long)dims[i]);
+    if (!dims) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_close: NULL argument");
+    bool wide = false;
+    if (const int rc = hadamard_extents("ttsk_hadamard_close", names, dims, &wide, p)) return rc;
     // ---- the cover
-    for (int i = 0; i < 6; ++i)
-        if (dims[i] > HD_MAX_EXTENT)
-            HC_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_hadamard_close: an extent of 2^31 or more; below 2^31 is covered");
+    if (wide) return hadamard_wide("ttsk_hadamard_close", p);
     HadamardCloseArgs &a = p->a;
     a.S = (int)dims[0]; a.S1 = (int)dims[1]; a.s = (int)dims[2]; a.s1 = (int)dims[3]; a.n = (int)dims[4]; a.P = (int)dims[5];
     a.ptiles = (int)cdiv(dims[5], 16);
     a.ctiles = (int)cdiv(dims[3], 16);
     a.gblocks = (int)cdiv(dims[1], HD_COLS);
     const int64_t tiles = (int64_t)a.ptiles * a.ctiles;             // below 2^56
-    if (tiles > HD_MAX_EXTENT || tiles * a.gblocks > HD_MAX_EXTENT)
-        HC_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_hadamard_close: 2^31 workgroups or more");
+    if (tiles > PLAN_MAX_EXTENT || tiles * a.gblocks > PLAN_MAX_EXTENT)
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_hadamard_close: 2^31 workgroups or more");
     const int64_t groups = tiles * a.gblocks;
     int64_t want = cdiv(HC_FILL, groups);
     for (int tries = 0;; ++tries, ++want) {
@@ -78,7 +74,7 @@ inline int hadamard_close_layout(const int64_t *dims, HadamardClosePlan *p)
         // the last round of HC_FILL workgroups nearly full, or nothing left to cut
         if (HC_TAIL_DEN * p->blocks >= HC_TAIL_NUM * rounds * HC_FILL || want >= dims[4] || tries == HC_TRIES) break;
     }
-    if (p->blocks > HD_MAX_EXTENT) HC_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_hadamard_close: 2^31 workgroups or more");
+    if (p->blocks > PLAN_MAX_EXTENT) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_hadamard_close: 2^31 workgroups or more");
     // a workgroup covers at most 16 x 16 x HD_COLS elements of its slice: the slab is below 2^14 x 2^31 doubles
     p->slab = dims[1] * dims[3] * dims[5] * a.ichunks;
     p->flops = 2.0 * (double)dims[4] * (double)dims[5] * ((double)dims[0] * dims[2] * dims[3] + (double)dims[0] * dims[1] * dims[3]);
@@ -90,18 +86,16 @@ inline int hadamard_close_plan(const double *Wl, const double *U, const double *
                                double *out, int accumulate, double *work, int64_t work_doubles, HadamardClosePlan *p)
 {
     *p = HadamardClosePlan{};
-    if (!Wl || !U || !V || !dims || !strides || !out || !work) HC_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_close: NULL argument");
-    if (accumulate != 0 && accumulate != 1) HC_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_close: accumulate = %d, 0 or 1", accumulate);
+    if (!Wl || !U || !V || !dims || !strides || !out || !work) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_close: NULL argument");
+    if (accumulate != 0 && accumulate != 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_close: accumulate = %d, 0 or 1", accumulate);
     const int rc = hadamard_close_layout(dims, p);
     if (rc) return rc;
     if (work_doubles < p->slab)
-        HC_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_close: a slab of %lld doubles, the plan needs %lld", (long long)work_doubles, (long long)p->slab);
+        PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_close: a slab of %lld doubles, the plan needs %lld", (long long)work_doubles, (long long)p->slab);
     HadamardCloseArgs &a = p->a;
     a.Wl = Wl; a.U = U; a.V = V; a.work = work;
     for (int i = 0; i < 3; ++i) { a.sU[i] = strides[i]; a.sV[i] = strides[3 + i]; }
     return TTSK_OK;
 }
-
-#undef HC_PLAN_FAIL
 
 }  // namespace ttsk

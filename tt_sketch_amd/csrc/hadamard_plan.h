@@ -18,7 +18,6 @@ constexpr int HD_COL_TILES = 4;                  // 16-column tiles of beta' a w
 constexpr int HD_COLS = 16 * HD_COL_TILES;
 constexpr int HD_PITCH = OP_PITCH;               // one beta row of T1 is a 16 x 16 tile of (l, a'), at op_apply's conflict-free pitch
 constexpr size_t HD_LDS = (size_t)HD_KC * HD_PITCH * 8;
-constexpr int64_t HD_MAX_EXTENT = (1ll << 31) - 1;
 
 // the kernel's argument
 struct HadamardArgs {
@@ -38,7 +37,23 @@ struct HadamardPlan {
     char msg[200];               // why not, when the status is not TTSK_OK
 };
 
-#define HD_PLAN_FAIL(status, ...) do { snprintf(p->msg, sizeof(p->msg), __VA_ARGS__); return status; } while (0)
+// The six extents of `entry` (hadamard_apply or hadamard_close), named for its messages: each is positive, or the plan
+// fails; *wide is set where one is 2^31 or more, which hadamard_wide refuses once the argument checks are through.
+template <class Plan>
+inline int hadamard_extents(const char *entry, const char *const *names, const int64_t *dims, bool *wide, Plan *p)
+{
+    for (int i = 0; i < 6; ++i)
+        if (dims[i] < 1) PLAN_FAIL(TTSK_ERR_ARG, "%s: %s = %lld must be positive", entry, names[i], (long long)dims[i]);
+    for (int i = 0; i < 6; ++i)
+        if (dims[i] > PLAN_MAX_EXTENT) *wide = true;
+    return TTSK_OK;
+}
+
+template <class Plan>
+inline int hadamard_wide(const char *entry, Plan *p)
+{
+    PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "%s: an extent of 2^31 or more; below 2^31 is covered", entry);
+}
 
 // dims: R, R', r, r', n, l; strides in elements: X (beta, i, beta') then Y (a, i, a')
 inline int hadamard_apply_plan(const double *L, const double *X, const double *Y, const int64_t *dims, const int64_t *strides,
@@ -46,20 +61,17 @@ inline int hadamard_apply_plan(const double *L, const double *X, const double *Y
 {
     static const char *const names[6] = {"R", "R'", "r", "r'", "n", "l"};
     *p = HadamardPlan{};
-    if (!L || !X || !Y || !dims || !strides || !W) HD_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_apply: NULL argument");
-    for (int i = 0; i < 6; ++i)
-        if (dims[i] < 1) HD_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_apply: %s = %lld must be positive", names[i], (long long)dims[i]);
+    if (!L || !X || !Y || !dims || !strides || !W) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_apply: NULL argument");
+    bool wide = w_cols > PLAN_MAX_EXTENT;
+    if (const int rc = hadamard_extents("ttsk_hadamard_apply", names, dims, &wide, p)) return rc;
     if (w_cols < 1 || w_off < 0)
-        HD_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_apply: w_cols = %lld, w_off = %lld", (long long)w_cols, (long long)w_off);
-    bool wide = w_cols > HD_MAX_EXTENT;
-    for (int i = 0; i < 6; ++i)
-        if (dims[i] > HD_MAX_EXTENT) wide = true;
+        PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_apply: w_cols = %lld, w_off = %lld", (long long)w_cols, (long long)w_off);
     // (extents below 2^31: the product below is below 2^62)
     if (!wide && (w_off > w_cols || dims[1] * dims[3] > w_cols - w_off))
-        HD_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_apply: columns %lld + %lld x %lld pass w_cols = %lld", (long long)w_off, (long long)dims[1],
-                     (long long)dims[3], (long long)w_cols);
+        PLAN_FAIL(TTSK_ERR_ARG, "ttsk_hadamard_apply: columns %lld + %lld x %lld pass w_cols = %lld", (long long)w_off, (long long)dims[1],
+                  (long long)dims[3], (long long)w_cols);
     // ---- the cover
-    if (wide) HD_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_hadamard_apply: an extent of 2^31 or more; below 2^31 is covered");
+    if (wide) return hadamard_wide("ttsk_hadamard_apply", p);
     HadamardArgs &a = p->a;
     a.L = L; a.X = X; a.Y = Y; a.W = W;
     for (int i = 0; i < 3; ++i) { a.sX[i] = strides[i]; a.sY[i] = strides[3 + i]; }
@@ -69,13 +81,11 @@ inline int hadamard_apply_plan(const double *L, const double *X, const double *Y
     a.atiles = (int)cdiv(dims[3], 16);
     a.cblocks = (int)cdiv(dims[1], HD_COLS);
     const int64_t tiles = (int64_t)a.ltiles * a.atiles;             // below 2^56
-    if (tiles > HD_MAX_EXTENT || tiles * a.cblocks > HD_MAX_EXTENT || tiles * a.cblocks * dims[4] > HD_MAX_EXTENT)
-        HD_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_hadamard_apply: 2^31 workgroups or more");
+    if (tiles > PLAN_MAX_EXTENT || tiles * a.cblocks > PLAN_MAX_EXTENT || tiles * a.cblocks * dims[4] > PLAN_MAX_EXTENT)
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_hadamard_apply: 2^31 workgroups or more");
     p->blocks = tiles * a.cblocks * dims[4];
     p->flops = 2.0 * (double)dims[5] * (double)dims[4] * ((double)dims[0] * dims[2] * dims[3] + (double)dims[0] * dims[1] * dims[3]);
     return TTSK_OK;
 }
-
-#undef HD_PLAN_FAIL
 
 }  // namespace ttsk

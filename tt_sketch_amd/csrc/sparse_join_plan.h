@@ -61,8 +61,6 @@ struct SjJoinPlan {
     char msg[200];
 };
 
-#define SJ_PLAN_FAIL(status, ...) do { snprintf(p->msg, sizeof(p->msg), __VA_ARGS__); return status; } while (0)
-
 inline int sj_ceil_log2(int64_t n)
 {
     int s = 0;
@@ -75,23 +73,23 @@ template <typename Plan>
 inline int sj_key_map(const char *who, const int64_t *shape, int d, const void *dev_idx, int64_t row_stride, const int *row_order, uint64_t N,
                       SjKeyMap *km, Plan *p)
 {
-    if (!shape) SJ_PLAN_FAIL(TTSK_ERR_ARG, "%s: NULL shape", who);
-    if (d < 1) SJ_PLAN_FAIL(TTSK_ERR_ARG, "%s: d = %d must be positive", who, d);
-    if (d > SJ_MAX_MODES) SJ_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "%s: %d modes, at most %d are covered", who, d, SJ_MAX_MODES);
-    if (!dev_idx && N) SJ_PLAN_FAIL(TTSK_ERR_ARG, "%s: NULL index matrix", who);
+    if (!shape) PLAN_FAIL(TTSK_ERR_ARG, "%s: NULL shape", who);
+    if (d < 1) PLAN_FAIL(TTSK_ERR_ARG, "%s: d = %d must be positive", who, d);
+    if (d > SJ_MAX_MODES) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "%s: %d modes, at most %d are covered", who, d, SJ_MAX_MODES);
+    if (!dev_idx && N) PLAN_FAIL(TTSK_ERR_ARG, "%s: NULL index matrix", who);
     if (row_stride < 0 || (uint64_t)row_stride < N)
-        SJ_PLAN_FAIL(TTSK_ERR_ARG, "%s: row_stride %lld below N = %llu", who, (long long)row_stride, (unsigned long long)N);
+        PLAN_FAIL(TTSK_ERR_ARG, "%s: row_stride %lld below N = %llu", who, (long long)row_stride, (unsigned long long)N);
     for (int k = 0; k < d; ++k) {
-        if (shape[k] < 1) SJ_PLAN_FAIL(TTSK_ERR_ARG, "%s: mode %d has size %lld", who, k, (long long)shape[k]);
+        if (shape[k] < 1) PLAN_FAIL(TTSK_ERR_ARG, "%s: mode %d has size %lld", who, k, (long long)shape[k]);
         const int row = row_order ? row_order[k] : k;
-        if (row < 0) SJ_PLAN_FAIL(TTSK_ERR_ARG, "%s: row_order[%d] = %d", who, k, row);
+        if (row < 0) PLAN_FAIL(TTSK_ERR_ARG, "%s: row_order[%d] = %d", who, k, row);
         km->row[k] = row;
     }
     int64_t total = 1;
     for (int k = d - 1; k >= 0; --k) {
         km->mult[k] = total;
         if (__builtin_mul_overflow(total, shape[k], &total))
-            SJ_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "%s: the shape has more than 2^63 - 1 entries, a key is an int64", who);
+            PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "%s: the shape has more than 2^63 - 1 entries, a key is an int64", who);
     }
     km->total = total;
     km->row_stride = row_stride;
@@ -122,9 +120,9 @@ inline int sparse_key_index_plan(const int64_t *shape, int d, const void *dev_id
 {
     *p = SjIndexPlan{};
     const char *who = "ttsk_sparse_key_index";
-    if (N > (uint64_t)SJ_MAX_N) SJ_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "%s: %llu nonzeros, below 2^31 is covered", who, (unsigned long long)N);
+    if (N > (uint64_t)SJ_MAX_N) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "%s: %llu nonzeros, below 2^31 is covered", who, (unsigned long long)N);
     if (int rc = sj_key_map(who, shape, d, dev_idx, row_stride, row_order, N, &p->km, p)) return rc;
-    if (N && (!dev_val || !dev_keys || !dev_vals || !dev_split)) SJ_PLAN_FAIL(TTSK_ERR_ARG, "%s: NULL entries or output", who);
+    if (N && (!dev_val || !dev_keys || !dev_vals || !dev_split)) PLAN_FAIL(TTSK_ERR_ARG, "%s: NULL entries or output", who);
     if (int rc = sj_check_split(who, max_split, p->msg, sizeof(p->msg))) return rc;
     p->bits = 1;
     while (p->bits < 63 && ((int64_t)1 << p->bits) < p->km.total) ++p->bits;
@@ -140,11 +138,11 @@ inline int sparse_join_plan(int dense, const void *dev_keys, const void *dev_val
     *p = SjJoinPlan{};
     const char *who = dense ? "ttsk_dense_join" : "ttsk_sparse_join";
     if (!dense && N_table > (uint64_t)SJ_MAX_N)
-        SJ_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "%s: a table of %llu nonzeros, below 2^31 is covered", who, (unsigned long long)N_table);
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "%s: a table of %llu nonzeros, below 2^31 is covered", who, (unsigned long long)N_table);
     if (int rc = sj_key_map(who, shape, d, dev_qidx, q_stride, q_row_order, Nq, &p->km, p)) return rc;
-    if (dense ? !dev_keys : (N_table && (!dev_keys || !dev_vals || !dev_split))) SJ_PLAN_FAIL(TTSK_ERR_ARG, "%s: NULL table", who);
-    if (!dev_out && !dev_dot) SJ_PLAN_FAIL(TTSK_ERR_ARG, "%s: neither dev_out nor dev_dot given", who);
-    if (dev_dot && !dev_qval && Nq) SJ_PLAN_FAIL(TTSK_ERR_ARG, "%s: the dot needs dev_qval", who);
+    if (dense ? !dev_keys : (N_table && (!dev_keys || !dev_vals || !dev_split))) PLAN_FAIL(TTSK_ERR_ARG, "%s: NULL table", who);
+    if (!dev_out && !dev_dot) PLAN_FAIL(TTSK_ERR_ARG, "%s: neither dev_out nor dev_dot given", who);
+    if (dev_dot && !dev_qval && Nq) PLAN_FAIL(TTSK_ERR_ARG, "%s: the dot needs dev_qval", who);
     if (int rc = sj_check_split(who, max_split, p->msg, sizeof(p->msg))) return rc;
     if (dense) { p->stride = 1; p->n_split = 0; }
     else sj_split(N_table, max_split, &p->stride, &p->n_split);
@@ -159,7 +157,5 @@ inline int sparse_join_plan(int dense, const void *dev_keys, const void *dev_val
     p->scratch = (size_t)p->grid * 8;
     return TTSK_OK;
 }
-
-#undef SJ_PLAN_FAIL
 
 }  // namespace ttsk

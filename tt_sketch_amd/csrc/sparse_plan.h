@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include "ttsk.h"
+#include "plan_common.h"
 
 #ifdef __HIPCC__
 #define SG_HD __host__ __device__
@@ -125,22 +126,20 @@ struct SgPlan {
     char msg[160];                   // why not, when the status is not TTSK_OK
 };
 
-#define SG_PLAN_FAIL(status, ...) do { snprintf(p->msg, sizeof(p->msg), __VA_ARGS__); return status; } while (0)
-
 // the chain factor at position i: its descriptor checked and restated as p->ch[i]
 inline int sg_plan_chain(const ttsk_sg_factor *f, int i, int w32, SgPlan *p)
 {
     const SgPlanF &F = p->f[i];
     SgPlanCh &c = p->ch[i];
     const ttsk_sg_chain *ch = f->chain;
-    if (!ch) SG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: a chain factor without its descriptor", i);
+    if (!ch) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: a chain factor without its descriptor", i);
     if (!w32)
-        SG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: a chain factor takes the 32-bit streams only", i);
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: a chain factor takes the 32-bit streams only", i);
     if (!(ch->steps >= 0 && ch->steps <= SG_CHAIN_MAX))
-        SG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: chain of %d steps, up to %d are covered", i, ch->steps, SG_CHAIN_MAX);
-    if (!ch->rows && ch->steps == 0) SG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain with neither a table nor a core", i);
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: chain of %d steps, up to %d are covered", i, ch->steps, SG_CHAIN_MAX);
+    if (!ch->rows && ch->steps == 0) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain with neither a table nor a core", i);
     if (ch->rows >= (1ull << 31))
-        SG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: chain table of %llu rows, below 2^31 is covered", i, (unsigned long long)ch->rows);
+        PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: chain table of %llu rows, below 2^31 is covered", i, (unsigned long long)ch->rows);
     c.steps = ch->steps;
     c.has_table = ch->rows > 0;
     c.rows = (uint32_t)ch->rows;
@@ -148,23 +147,23 @@ inline int sg_plan_chain(const ttsk_sg_factor *f, int i, int w32, SgPlan *p)
     int widest = 1;
     for (int s = 0; s <= c.steps; ++s) {
         c.rank[s] = ch->rank[s];
-        if (c.rank[s] < 1) SG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain rank %d is %d", i, s, c.rank[s]);
+        if (c.rank[s] < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain rank %d is %d", i, s, c.rank[s]);
         if (c.rank[s] > SG_CHAIN_RANK)
-            SG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: chain rank %d is %d, up to %d are covered", i, s, c.rank[s], SG_CHAIN_RANK);
+            PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: chain rank %d is %d, up to %d are covered", i, s, c.rank[s], SG_CHAIN_RANK);
         if (c.rank[s] > widest) widest = c.rank[s];
     }
-    if (!c.has_table && c.rank[0] != 1) SG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain from the first core with rank %d in front of it", i, c.rank[0]);
+    if (!c.has_table && c.rank[0] != 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain from the first core with rank %d in front of it", i, c.rank[0]);
     for (int s = 0; s < c.steps; ++s) {
-        if (!ch->core[s]) SG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain core %d is NULL", i, s);
-        if (ch->n[s] < 1) SG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain mode %d has size %lld", i, s, (long long)ch->n[s]);
+        if (!ch->core[s]) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain core %d is NULL", i, s);
+        if (ch->n[s] < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain mode %d has size %lld", i, s, (long long)ch->n[s]);
         if (ch->n[s] >= (1ll << 31))
-            SG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: chain mode %d of size %lld, below 2^31 is covered", i, s, (long long)ch->n[s]);
+            PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: chain mode %d of size %lld, below 2^31 is covered", i, s, (long long)ch->n[s]);
         c.n[s] = (uint32_t)ch->n[s];
         c.dn[s] = sg_div_make((uint64_t)ch->n[s]);
     }
     c.lo = f->rank_min;
     if (!(c.lo >= 0 && c.lo + F.w <= c.rank[c.steps]))
-        SG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: columns [%d, %d) of a chain that ends in rank %d", i, c.lo, c.lo + F.w, c.rank[c.steps]);
+        PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: columns [%d, %d) of a chain that ends in rank %d", i, c.lo, c.lo + F.w, c.rank[c.steps]);
     c.gsh = widest <= 16 ? 4 : 5;
     return TTSK_OK;
 }
@@ -184,10 +183,10 @@ inline int sg_plan(const ttsk_sg_factor *A, const ttsk_sg_factor *B, const ttsk_
         if (F.kind) F.w = fs[i]->w;
         const int full = fs[i]->full, nnz = fs[i]->nnz, lo = fs[i]->rank_min;
         if (!(F.kind >= 0 && F.kind <= 4 && F.w >= 1 && F.w <= 32))
-            SG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: kind %d, width %d", i, F.kind, F.w);
+            PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: kind %d, width %d", i, F.kind, F.w);
         if (F.kind == 3 && !(full >= 1 && full <= 32 && nnz >= 0 && nnz <= full && lo >= 0 && lo + F.w <= full))
-            SG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: sign row of %d entries, %d non-zero, columns [%d, %d)", i, full,
-                         nnz, lo, lo + F.w);
+            PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: sign row of %d entries, %d non-zero, columns [%d, %d)", i, full,
+                      nnz, lo, lo + F.w);
         if (F.kind == 3) {                             // the whole row is staged; the products read its slice
             F.off = cols + lo;
             cols += full;
@@ -239,7 +238,7 @@ inline int sg_plan(const ttsk_sg_factor *A, const ttsk_sg_factor *B, const ttsk_
     const size_t by_regs = p->NT == 1 ? 3 : 2;
     p->wg_per_cu = SG_LDS_BUDGET / (p->lds + fixed);
     if (p->wg_per_cu > by_regs) p->wg_per_cu = by_regs;
-    if (p->wg_per_cu < 1) SG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: a staged tile of %d columns does not fit the LDS", p->tcols);
+    if (p->wg_per_cu < 1) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: a staged tile of %d columns does not fit the LDS", p->tcols);
     const size_t resident = n_cu * 4 * p->wg_per_cu;
     p->chunk = ((N + resident - 1) / resident + SG_T - 1) / SG_T * SG_T;
     if (p->chunk < (size_t)SG_MIN_TILES * SG_T) p->chunk = (size_t)SG_MIN_TILES * SG_T;
@@ -255,7 +254,5 @@ inline int sg_plan(const ttsk_sg_factor *A, const ttsk_sg_factor *B, const ttsk_
     p->scratch = p->j_off + wtot * 16 + 256;          // (three ints per wave, rounded up)
     return TTSK_OK;
 }
-
-#undef SG_PLAN_FAIL
 
 }  // namespace ttsk

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include "ttsk.h"
+#include "plan_common.h"
 
 namespace ttsk {
 
@@ -45,8 +46,6 @@ struct GramPlan {
     char msg[160];               // why not, when the status is not TTSK_OK
 };
 
-#define GRAM_PLAN_FAIL(status, ...) do { snprintf(p->msg, sizeof(p->msg), __VA_ARGS__); return status; } while (0)
-
 inline int gram_round(int x, int m) { return (x + m - 1) / m * m; }
 
 // LDS of one stage (doubles): acc, then T
@@ -73,30 +72,30 @@ inline void gram_lds(GramModePlan &m, bool pad)
 inline int gram_plan(const int64_t *ranks_a, const int64_t *ranks_b, const int64_t *shape, int d, int K, int M, int n_cu, GramPlan *p)
 {
     *p = GramPlan{};
-    if (!ranks_a || !ranks_b || !shape) GRAM_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tt_gram: NULL rank table or shape");
-    if (d < 1 || K < 1 || M < 1) GRAM_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tt_gram: d = %d, K = %d, M = %d must be positive", d, K, M);
-    if (d > GRAM_MAX_MODES) GRAM_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: %d modes, at most %d are covered", d, GRAM_MAX_MODES);
+    if (!ranks_a || !ranks_b || !shape) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tt_gram: NULL rank table or shape");
+    if (d < 1 || K < 1 || M < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tt_gram: d = %d, K = %d, M = %d must be positive", d, K, M);
+    if (d > GRAM_MAX_MODES) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: %d modes, at most %d are covered", d, GRAM_MAX_MODES);
     for (int side = 0; side < 2; ++side) {
         const int64_t *rk = side ? ranks_b : ranks_a;
         for (int t = 0; t < (side ? M : K); ++t, rk += d + 1) {
             if (rk[0] != 1 || rk[d] != 1)
-                GRAM_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tt_gram: boundary ranks (%lld, %lld) of train %d of side %d are not 1", (long long)rk[0],
-                               (long long)rk[d], t, side);
+                PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tt_gram: boundary ranks (%lld, %lld) of train %d of side %d are not 1", (long long)rk[0],
+                          (long long)rk[d], t, side);
             for (int k = 0; k <= d; ++k)
-                if (rk[k] < 1) GRAM_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tt_gram: rank %d of train %d of side %d is %lld", k, t, side, (long long)rk[k]);
+                if (rk[k] < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tt_gram: rank %d of train %d of side %d is %lld", k, t, side, (long long)rk[k]);
         }
     }
     for (int k = 0; k < d; ++k)
-        if (shape[k] < 1) GRAM_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tt_gram: mode %d has size %lld", k, (long long)shape[k]);
+        if (shape[k] < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tt_gram: mode %d has size %lld", k, (long long)shape[k]);
     // ---- the cover
     for (int k = 0; k < d; ++k)
-        if (shape[k] >= (1ll << 31)) GRAM_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: mode %d of size %lld, below 2^31 is covered", k, (long long)shape[k]);
+        if (shape[k] >= (1ll << 31)) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: mode %d of size %lld, below 2^31 is covered", k, (long long)shape[k]);
     for (int side = 0; side < 2; ++side) {
         const int64_t *rk = side ? ranks_b : ranks_a;
         for (int i = 0; i < (side ? M : K) * (d + 1); ++i)
-            if (rk[i] > GRAM_MAX_RANK) GRAM_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: rank %lld, up to %d is covered", (long long)rk[i], GRAM_MAX_RANK);
+            if (rk[i] > GRAM_MAX_RANK) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: rank %lld, up to %d is covered", (long long)rk[i], GRAM_MAX_RANK);
     }
-    if (K + M > GRAM_MAX_TRAINS) GRAM_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: %d trains in one call, up to %d are covered", K + M, GRAM_MAX_TRAINS);
+    if (K + M > GRAM_MAX_TRAINS) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: %d trains in one call, up to %d are covered", K + M, GRAM_MAX_TRAINS);
     p->d = d; p->K = K; p->M = M;
     p->pairs = (int64_t)K * M;
     if (n_cu < 1) n_cu = 1;
@@ -137,10 +136,10 @@ inline int gram_plan(const int64_t *ranks_a, const int64_t *ranks_b, const int64
             if (m.S > 1) --m.S;
             else if (m.TA > 1) --m.TA;
             else if (pad) pad = false;
-            else GRAM_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: mode %d: acc (%d x %d) and one tile of T do not fit the LDS", k, m.ra, m.rb);
+            else PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: mode %d: acc (%d x %d) and one tile of T do not fit the LDS", k, m.ra, m.rb);
         }
         if (m.body == GRAM_BODY_FMA && (int64_t)m.ra1 * m.rb1 > GRAM_FMA_CELLS)
-            GRAM_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: mode %d: %d x %d sums on the FMA body", k, m.ra1, m.rb1);
+            PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tt_gram: mode %d: %d x %d sums on the FMA body", k, m.ra1, m.rb1);
         m.slab_bytes = (size_t)m.chunks * (size_t)m.sum_a1 * (size_t)m.sum_b1 * 8;
         if (m.slab_bytes > widest[k & 1]) widest[k & 1] = m.slab_bytes;
     }
@@ -151,7 +150,5 @@ inline int gram_plan(const int64_t *ranks_a, const int64_t *ranks_b, const int64
     p->launches = d + 1 - p->fold_last;
     return TTSK_OK;
 }
-
-#undef GRAM_PLAN_FAIL
 
 }  // namespace ttsk

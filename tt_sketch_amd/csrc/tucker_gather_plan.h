@@ -17,7 +17,6 @@ namespace ttsk {
 
 constexpr int TKG_MAX_MODES = 8;                 // the cover: d
 constexpr int64_t TKG_MAX_CORE = 1ll << 20;      // ... entries of the core
-constexpr int64_t TKG_MAX_EXTENT = (1ll << 31) - 1;
 constexpr int TKG_TILES = 4;                     // tiles of 16 tuples a wave carries: a wave owns 64 tuples, one per lane
 constexpr int TKG_BATCH = 4 * 16 * TKG_TILES;    // tuples of a workgroup (four waves) at a time: one residency of a chunk serves them all
 constexpr int TKG_MAX_CT = 4;                    // column tiles: Q padded to 16, 32 or 64
@@ -66,36 +65,34 @@ inline int64_t tkg_split_cost(int64_t P, int64_t Q, int d, int m)
     return 4 * (cdiv(P, 4) * 4) * ct + P + Q * (d - m);
 }
 
-#define TKG_PLAN_FAIL(status, ...) do { snprintf(p->msg, sizeof(p->msg), __VA_ARGS__); return status; } while (0)
-
 inline int tucker_gather_plan(const void *dev_core, const void *const *dev_factors, const int64_t *ranks, const int64_t *shape, int d,
                               const void *dev_idx, int64_t row_stride, const int *row_order, size_t N, const void *dev_val,
                               const void *dev_out, const void *dev_stats, int n_cu, TuckerGatherPlan *p)
 {
     *p = TuckerGatherPlan{};
-    if (!dev_core || !dev_factors || !ranks || !shape) TKG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: NULL core / factors / ranks / shape");
-    if (d < 1) TKG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: d = %d < 1", d);
-    if (!dev_out && !dev_stats) TKG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: neither dev_out nor dev_stats given");
-    if (dev_stats && !dev_val) TKG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: the statistics need dev_val");
-    if (!dev_idx && N != 0) TKG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: NULL index matrix");
+    if (!dev_core || !dev_factors || !ranks || !shape) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: NULL core / factors / ranks / shape");
+    if (d < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: d = %d < 1", d);
+    if (!dev_out && !dev_stats) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: neither dev_out nor dev_stats given");
+    if (dev_stats && !dev_val) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: the statistics need dev_val");
+    if (!dev_idx && N != 0) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: NULL index matrix");
     if (row_stride < 0 || (size_t)row_stride < N)
-        TKG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: row_stride %lld below N = %zu", (long long)row_stride, N);
-    if (d > TKG_MAX_MODES) TKG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tucker_gather: %d modes, at most %d are covered", d, TKG_MAX_MODES);
+        PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: row_stride %lld below N = %zu", (long long)row_stride, N);
+    if (d > TKG_MAX_MODES) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tucker_gather: %d modes, at most %d are covered", d, TKG_MAX_MODES);
     for (int k = 0; k < d; ++k) {
-        if (!dev_factors[k]) TKG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: factor %d is NULL", k);
-        if (shape[k] < 1) TKG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: mode %d has size %lld", k, (long long)shape[k]);
-        if (ranks[k] < 1) TKG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: rank %d is %lld", k, (long long)ranks[k]);
+        if (!dev_factors[k]) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: factor %d is NULL", k);
+        if (shape[k] < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: mode %d has size %lld", k, (long long)shape[k]);
+        if (ranks[k] < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: rank %d is %lld", k, (long long)ranks[k]);
         const int row = row_order ? row_order[k] : k;
-        if (row < 0) TKG_PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: row_order[%d] = %d", k, row);
+        if (row < 0) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_tucker_gather: row_order[%d] = %d", k, row);
         p->row[k] = row;
     }
     // ---- the cover
     int64_t core = 1;
     for (int k = 0; k < d; ++k) {
-        if (shape[k] > TKG_MAX_EXTENT)
-            TKG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tucker_gather: mode %d of size %lld, below 2^31 is covered", k, (long long)shape[k]);
+        if (shape[k] > PLAN_MAX_EXTENT)
+            PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tucker_gather: mode %d of size %lld, below 2^31 is covered", k, (long long)shape[k]);
         if (ranks[k] > TKG_MAX_CORE || (core *= ranks[k]) > TKG_MAX_CORE)
-            TKG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tucker_gather: a core of more than 2^20 entries; up to 2^20 is covered");
+            PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tucker_gather: a core of more than 2^20 entries; up to 2^20 is covered");
     }
     TuckerGatherArgs &a = p->a;
     a.core = (const double *)dev_core;
@@ -117,8 +114,8 @@ inline int tucker_gather_plan(const void *dev_core, const void *const *dev_facto
     p->ct = (int)cdiv(a.Q, 16) == 3 ? 4 : (int)cdiv(a.Q, 16);
     p->chunks = (int)cdiv(a.P, TKG_KC);
     p->lds = ((size_t)TKG_KC * tkg_b_pitch(p->ct) + (size_t)4 * TKG_KC * TKG_A_PITCH + 256) * 8 + (size_t)4 * d * 64 * 4;
-    if (p->lds > TKG_LDS_LIMIT) TKG_PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tucker_gather: %zu bytes of LDS", p->lds);   // not reached inside the cover
-    if (n_cu < 1) n_cu = 1;
+    if (p->lds > TKG_LDS_LIMIT) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_tucker_gather: %zu bytes of LDS", p->lds);   // not reached inside the cover
+                                          if (n_cu < 1) n_cu = 1;
     const size_t batches = (N + TKG_BATCH - 1) / TKG_BATCH, cap = (size_t)TKG_WG_PER_CU * n_cu;
     p->grid = (unsigned)(batches < cap ? batches : cap);
     p->run = p->grid ? (int64_t)((batches + p->grid - 1) / p->grid) : 0;
@@ -128,7 +125,5 @@ inline int tucker_gather_plan(const void *dev_core, const void *const *dev_facto
     p->stat_depth = 2 + p->run + TKG_BLOCK_SUMS + cdiv(p->grid, 256) + TKG_BLOCK_SUMS;
     return TTSK_OK;
 }
-
-#undef TKG_PLAN_FAIL
 
 }  // namespace ttsk
