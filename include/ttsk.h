@@ -428,6 +428,34 @@ int ttsk_hadamard_close(const double *Wl, const double *U, const double *V, cons
 /* The plan's numbers for those dims (host only): out[0] = ichunks, out[1] = doubles of the slab */
 int ttsk_hadamard_close_layout(const int64_t *dims, int64_t *out);
 
+/* ---- inner product of two operator-times-train products: the closing half of a mode (csrc/op_close.hip, plan in
+ * csrc/op_close_plan.h) ----
+ * <M x, N y> carries a chain G (R, r, s, S) over the ranks of M, x, y and N, flattened with the train rank of y major,
+ * l = c S + gamma.  Per mode, ttsk_op_apply with that l takes G through the cores of M and x: Wl ((c gamma), i, p) with
+ * p = (beta' a').  This entry takes Wl through the cores N (S, n_in, n_out, S') of the operator and Y (s, n_in, s') of the
+ * train and sums over both mode indices:
+ *   out[p, c' S' + gamma'] (+)= sum_{j < n_in} sum_c Y[c, j, c'] sum_gamma sum_{i < n_out} Wl[(c S + gamma), i, p] N[gamma, j, i, gamma'];
+ * the inner sums stay on the chip and no array indexed by j is written.
+ *   Wl            contiguous (s S, n_out, P)
+ *   N, Y          strided: (S, n_in, n_out, S') and (s, n_in, s').  (gamma, i) of N must be one run,
+ *                 stride[gamma] == n_out stride[i] (where S or n_out is 1 the other's stride is the run's): a contiguous
+ *                 (S, n_out, n_in, S') array viewed as (S, n_in, n_out, S'), padded or not, is; an operator core as stored is not
+ *   dims          S, S', s, s', n_in, n_out, P
+ *   strides       in elements: N over (gamma, j, i, gamma'), then Y over (c, j, c')
+ *   out           contiguous (P, s' S'), columns in (c', gamma') order; accumulate = 1 adds to what it holds
+ *   work          a slab of the caller's, work_doubles doubles, at least what ttsk_op_close_layout names; every double
+ *                 of that size is overwritten
+ * The in-index is cut into jchunks ranges of j so that few (p, gamma', c') tiles still fill the device; a workgroup writes
+ * its partial tile to work (jchunks, P, s' S') and ttsk_sum_slices adds the slices in ascending order into out.  The cut
+ * depends on dims alone.  No atomics: the same bits on every call.  TTSK_ERR_ARG: a NULL pointer, an extent below 1,
+ * accumulate not 0 or 1, a slab smaller than the plan's.  TTSK_ERR_UNSUPPORTED: an N whose (gamma, i) is not one run; an
+ * extent, S n_out or the number of workgroups (jchunks x ceil(P / 16) x ceil(S' / 16) x ceil(s' / 64)) of 2^31 or more.  A
+ * refused call launches nothing and writes nothing.  Inside those bounds every shape runs. */
+int ttsk_op_close(const double *Wl, const double *N, const double *Y, const int64_t *dims, const int64_t *strides, double *out,
+                  int accumulate, double *work, int64_t work_doubles, int stream);
+/* The plan's numbers for those dims (host only): out[0] = jchunks, out[1] = doubles of the slab */
+int ttsk_op_close_layout(const int64_t *dims, int64_t *out);
+
 /* ---- CP tensors against tensor-train DRMs, no panels (csrc/cp_pass.hip, plan in csrc/cp_pass_plan.h) ----
  * A CP tensor of rank N has factor matrices V_mu (n x N).  The step of TensorTrainDRM.sketch_cp (tensor_train_drm.py:90-107)
  * and the Psi / Omega of cp_sketch.py:6-36 are one GEMM each whose Khatri-Rao operand is formed in registers; the N x n x

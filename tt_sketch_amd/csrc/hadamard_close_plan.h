@@ -45,6 +45,23 @@ struct HadamardClosePlan {
     char msg[200];               // why not, when the status is not TTSK_OK
 };
 
+// The filling rule above for `groups` tiles and a summed index of extent n (op_close_plan.h cuts its j by it too): chunk q
+// sums q per .. min(n, (q + 1) per); returns the workgroups of the launch, groups x chunks.
+inline int64_t hc_cut(int64_t groups, int64_t n, int *per, int *chunks)
+{
+    int64_t want = cdiv(HC_FILL, groups), blocks;
+    for (int tries = 0;; ++tries, ++want) {
+        if (want > n) want = n;
+        *per = (int)cdiv(n, want);
+        *chunks = (int)cdiv(n, *per);                               // no chunk is empty
+        blocks = groups * *chunks;
+        const int64_t rounds = cdiv(blocks, HC_FILL);
+        // the last round of HC_FILL workgroups nearly full, or nothing left to cut
+        if (HC_TAIL_DEN * blocks >= HC_TAIL_NUM * rounds * HC_FILL || want >= n || tries == HC_TRIES) break;
+    }
+    return blocks;
+}
+
 // The part of the plan that needs no pointers: dims are S, S', s, s', n, P.  ttsk_hadamard_close_layout is this.
 inline int hadamard_close_layout(const int64_t *dims, HadamardClosePlan *p)
 {
@@ -63,17 +80,7 @@ inline int hadamard_close_layout(const int64_t *dims, HadamardClosePlan *p)
     const int64_t tiles = (int64_t)a.ptiles * a.ctiles;             // below 2^56
     if (tiles > PLAN_MAX_EXTENT || tiles * a.gblocks > PLAN_MAX_EXTENT)
         PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_hadamard_close: 2^31 workgroups or more");
-    const int64_t groups = tiles * a.gblocks;
-    int64_t want = cdiv(HC_FILL, groups);
-    for (int tries = 0;; ++tries, ++want) {
-        if (want > dims[4]) want = dims[4];
-        a.iper = (int)cdiv(dims[4], want);
-        a.ichunks = (int)cdiv(dims[4], a.iper);                     // no chunk is empty
-        p->blocks = groups * a.ichunks;
-        const int64_t rounds = cdiv(p->blocks, HC_FILL);
-        // the last round of HC_FILL workgroups nearly full, or nothing left to cut
-        if (HC_TAIL_DEN * p->blocks >= HC_TAIL_NUM * rounds * HC_FILL || want >= dims[4] || tries == HC_TRIES) break;
-    }
+    p->blocks = hc_cut(tiles * a.gblocks, dims[4], &a.iper, &a.ichunks);
     if (p->blocks > PLAN_MAX_EXTENT) PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_hadamard_close: 2^31 workgroups or more");
     // a workgroup covers at most 16 x 16 x HD_COLS elements of its slice: the slab is below 2^14 x 2^31 doubles
     p->slab = dims[1] * dims[3] * dims[5] * a.ichunks;

@@ -37,14 +37,15 @@ struct HadamardPlan {
     char msg[200];               // why not, when the status is not TTSK_OK
 };
 
-// The six extents of `entry` (hadamard_apply or hadamard_close), named for its messages: each is positive, or the plan
-// fails; *wide is set where one is 2^31 or more, which hadamard_wide refuses once the argument checks are through.
+// The extents of `entry` (six of hadamard_apply or hadamard_close, seven of op_close), named for its messages: each is
+// positive, or the plan fails; *wide is set where one is 2^31 or more, which hadamard_wide refuses once the argument checks
+// are through.
 template <class Plan>
-inline int hadamard_extents(const char *entry, const char *const *names, const int64_t *dims, bool *wide, Plan *p)
+inline int hadamard_extents(const char *entry, const char *const *names, const int64_t *dims, bool *wide, Plan *p, int count = 6)
 {
-    for (int i = 0; i < 6; ++i)
+    for (int i = 0; i < count; ++i)
         if (dims[i] < 1) PLAN_FAIL(TTSK_ERR_ARG, "%s: %s = %lld must be positive", entry, names[i], (long long)dims[i]);
-    for (int i = 0; i < 6; ++i)
+    for (int i = 0; i < count; ++i)
         if (dims[i] > PLAN_MAX_EXTENT) *wide = true;
     return TTSK_OK;
 }

@@ -23,7 +23,10 @@
 // column, a fragment past the stream's end the base of its operand.  One workgroup forms each element in a fixed order
 // (kappa ascending within i, c ascending within kappa), no atomics: the same bits on every call.
 //
-// The functions are inlined into two kernels at 237 and 241 VGPRs, two workgroups per CU.  The stage-2 fragments of C are
+// op_close_kernel (op_close.hip) runs the same stages with A = Wl, B = an operator core whose inner index is the pair
+// (gamma, i), C = a train core, looping over the operator's in-index.
+//
+// The functions are inlined into three kernels at 237, 241 and 239 VGPRs, two workgroups per CU.  The stage-2 fragments of C are
 // held as one 4-vector: written as four doubles the compiler made that vector in the kernels' own bodies and not in
 // these functions, and the k-block loop of stage 2 came out four waits longer ("Hadamard stages").
 #pragma once

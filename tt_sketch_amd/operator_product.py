@@ -15,7 +15,7 @@ import numpy as np
 from . import _native as nat
 from .device import DevArray, contract, copy_into
 from .paths import resolve, taken
-from .tensor import Tensor, TensorTrain, _host
+from .tensor import DenseTensor, Tensor, TensorTrain, _error_tail, _fast_error, _host
 
 MAX_TERMS = 24          # OP_MAX_TERMS of csrc/op_apply_plan.h: the terms of one ttsk_op_apply call
 
@@ -146,6 +146,36 @@ class OperatorProduct(Tensor):
 
     def to_numpy(self):
         return self.to_tt().to_numpy()
+
+    # -- inner products, norm and fast error on the factors alone (operator_gram.py)
+    def dot(self, other, reverse=False, route: Optional[str] = None) -> float:
+        """``<self, other>`` against a ``TensorTrain`` or another ``OperatorProduct`` by a chain over the factors' cores: no
+        product core and no dense array is formed, on the device when a factor is there and in NumPy otherwise.  ``route`` is
+        the switch of ``paths.py`` for the closing step against a product (``operator_gram.op_close``).  Every other partner
+        goes through the base class."""
+        if isinstance(other, OperatorProduct):
+            from .operator_gram import op_dot
+            return op_dot(self, other, route)
+        if isinstance(other, TensorTrain):
+            from .operator_gram import op_tt_dot
+            return op_tt_dot(self, other)
+        return super().dot(other, reverse=reverse)
+
+    def norm(self) -> float:
+        """``||M x||`` from ``<M x, M x>`` (``operator_gram.op_dot``)"""
+        return float(np.sqrt(abs(self.dot(self))))
+
+    def error(self, other, relative: bool = False, rmse: bool = False, fast: bool = False) -> float:
+        """``||self - other||``.  ``fast=True`` is the reference's formula on ``<self, self>``, ``<self, other>`` and
+        ``<other, other>``, which form nothing dense against trains and operator products (or sums of them); it has that
+        formula's floor of about 1e-8 relative.  ``fast=False`` keeps the dense difference of the base class."""
+        if not fast:
+            return super().error(other, relative=relative, rmse=rmse, fast=False)
+        if isinstance(other, np.ndarray):
+            other = DenseTensor(other)
+        aa, ab, bb = self.dot(self), self.dot(other), other.dot(other)
+        err = float(_fast_error(aa, ab, bb)) if aa + bb > 0 else 0.0
+        return float(_error_tail(err, float(np.sqrt(abs(bb))), self.shape, relative, rmse))
 
     def __mul__(self, other: float) -> "OperatorProduct":
         return OperatorProduct(self.mpo, self.tt * other)

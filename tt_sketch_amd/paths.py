@@ -75,7 +75,7 @@ def drm_pair(shape, left_drm, right_drm, *, kinds=(TensorTrainDRM,), need_left: 
 
 # ------------------------------------------------------------------ kernel or composition
 # Where a path has both a kernel and a composition from ``contract`` calls, its entry takes ``route=``: None is the path's
-# cost rule (``cp_fused.chain_route_ms``, ``operator_product.route_ms``, ``hadamard_product.route_ms``, ``hadamard_gram.close_route_ms``, ``tensor_gram._gram_route_ms``,
+# cost rule (``cp_fused.chain_route_ms``, ``operator_product.route_ms``, ``hadamard_product.route_ms``, ``hadamard_gram.close_route_ms``, ``operator_gram.close_route_ms``, ``tensor_gram._gram_route_ms``,
 # ``sparse_fused.chain_route_ms``), ``"composed"`` never
 # calls the library entry, ``"kernel"`` calls it and lets its ``TtskUnsupported`` propagate, so that a test or a benchmark
 # knows which code it ran.  ``forced`` sets the route of every call made without the keyword.

@@ -777,9 +777,11 @@ class TensorTrain(_CoreList, Tensor):
         relative.  ``fast=False`` against CP keeps the reference's dense formula.
 
         Against a ``HadamardProduct`` ``fast=True`` is the same formula on three chains over the factors' cores
-        (``hadamard_gram``): the product's Kronecker cores are not formed."""
+        (``hadamard_gram``): the product's Kronecker cores are not formed.  The same against an ``OperatorProduct``
+        (``operator_gram``); ``fast=False`` forms ``mpo(tt)`` as before."""
         from .hadamard_product import HadamardProduct
-        if fast and isinstance(other, HadamardProduct):
+        from .operator_product import OperatorProduct
+        if fast and isinstance(other, (HadamardProduct, OperatorProduct)):
             aa, ab, bb = self.dot(self), other.dot(self), other.dot(other)
             err = float(_fast_error(aa, ab, bb)) if aa + bb > 0 else 0.0
             return float(_error_tail(err, float(np.sqrt(abs(bb))), self.shape, relative, rmse))    # sqrt|bb| is other.norm()

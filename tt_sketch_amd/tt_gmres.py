@@ -54,6 +54,8 @@ class MPO(Tensor, TTLinearMap):
         self._dev = None
         self._views = None
         self._dev_key = None
+        self._packed = None           # the cores as ttsk_op_close reads them (operator_gram.packed_views)
+        self._packed_key = None
 
     def resident(self) -> bool:
         """True if ``dev_views`` has the cores of this very list in HBM already"""
@@ -212,6 +214,21 @@ class TTLinearMapSum:
             return TensorSum([lm.lazy(t) if isinstance(lm, MPO) and type(t) is TensorTrain else lm(t)
                               for lm in self.linear_maps for t in terms])
         return TensorSum([lm(t) for lm in self.linear_maps for t in terms])
+
+    def residual(self, x: TensorTrain, b: TensorTrain, relative: bool = False) -> float:
+        """``||b - sum_p A_p x||`` (``relative``: over ``||b||``), the true residual of the linear system, from ``<b, b>``, the
+        ``<A_p x, b>`` and the ``<A_p x, A_q x>`` for ``q >= p``, each off-diagonal pair computed once and counted twice.  No
+        product ``A_p x`` of an ``MPO`` is formed (``OperatorProduct.dot``); maps that are not ``MPO``s are applied and enter as
+        plain trains.  The squares are subtracted, so a relative residual below about 1e-8 is not resolved."""
+        terms = [OperatorProduct(lm, x) if isinstance(lm, MPO) and type(x) is TensorTrain else lm(x) for lm in self.linear_maps]
+        bb = b.dot(b)
+        total = bb - 2.0 * sum(t.dot(b) for t in terms)
+        for p, t in enumerate(terms):
+            total += t.dot(t) + 2.0 * sum(t.dot(u) for u in terms[p + 1:])
+        res = float(np.sqrt(max(total, 0.0)))
+        if relative:
+            return res / float(np.sqrt(bb)) if bb > 0 else float("inf")
+        return res
 
 
 ROUNDING_MODE = Literal["exact", "pairwise", "gram", "sketch", "orth_sketch", None]
