@@ -456,6 +456,31 @@ int ttsk_op_close(const double *Wl, const double *N, const double *Y, const int6
 /* The plan's numbers for those dims (host only): out[0] = jchunks, out[1] = doubles of the slab */
 int ttsk_op_close_layout(const int64_t *dims, int64_t *out);
 
+/* ---- the same for many pairs in one launch (csrc/op_close.hip, plan in csrc/op_close_batch_plan.h) ----
+ * The work of ttsk_op_close for npairs independent pairs: one launch in which every pair's workgroups run side by side,
+ * and one launch that adds every pair's slices into its out.  Two launches whatever npairs is.
+ *   Wl, N, Y, out npairs pointers each, as ttsk_op_close takes them, but for
+ *   ldw           npairs numbers: the elements between consecutive (l, i) rows of a pair's Wl, at least its P.  A column
+ *                 slice of the W (l, n_out, sum of columns) that one ttsk_op_apply call wrote for many terms is read in
+ *                 place with ldw = the width of that W
+ *   dims          npairs x 7: S, S', s, s', n_in, n_out, P of each pair
+ *   strides       npairs x 7 in elements: N over (gamma, j, i, gamma'), then Y over (c, j, c')
+ *   accumulate    one flag for the whole call: 1 adds to what every out holds
+ *   work          one slab of the caller's for all pairs, work_doubles doubles, at least what ttsk_op_close_batch_layout
+ *                 names; every double of that size is overwritten
+ * The out arrays must not overlap each other, work or any input: the entry cannot check this.
+ * Each pair is planned as ttsk_op_close plans it (the same cut of j, tiles and slab for the same dims) and its slices are
+ * added in the same order, so out holds the bits of a ttsk_op_close call on the same operands, wherever in the list the
+ * pair stands.  No atomics: the same bits on every call.  TTSK_ERR_ARG: a NULL array or element, npairs below 1, an
+ * extent below 1, ldw below P, accumulate not 0 or 1, a slab smaller than the plan's.  TTSK_ERR_UNSUPPORTED: more than 23
+ * pairs (the table of pairs is the kernel's argument); for any pair what ttsk_op_close refuses; 2^31 workgroups or more
+ * in all.  The message names the pair.  A refused call launches nothing and writes nothing. */
+int ttsk_op_close_batch(int npairs, const double *const *Wl, const double *const *N, const double *const *Y, const int64_t *dims,
+                        const int64_t *strides, const int64_t *ldw, double *const *out, int accumulate, double *work,
+                        int64_t work_doubles, int stream);
+/* The slab of those pairs (host only): out[p] = first double of pair p, p < npairs; out[npairs] = doubles of the slab */
+int ttsk_op_close_batch_layout(int npairs, const int64_t *dims, int64_t *out);
+
 /* ---- CP tensors against tensor-train DRMs, no panels (csrc/cp_pass.hip, plan in csrc/cp_pass_plan.h) ----
  * A CP tensor of rank N has factor matrices V_mu (n x N).  The step of TensorTrainDRM.sketch_cp (tensor_train_drm.py:90-107)
  * and the Psi / Omega of cp_sketch.py:6-36 are one GEMM each whose Khatri-Rao operand is formed in registers; the N x n x

@@ -131,6 +131,8 @@ ENTRY_POINTS = {
     "ttsk_hadamard_close_layout": Entry([POINTER(I64), POINTER(I64)]),
     "ttsk_op_close": Entry([P, P, P, POINTER(I64), POINTER(I64), P, I, P, I64, I], QUEUE),
     "ttsk_op_close_layout": Entry([POINTER(I64), POINTER(I64)]),
+    "ttsk_op_close_batch": Entry([I, POINTER(P), POINTER(P), POINTER(P), POINTER(I64), POINTER(I64), POINTER(I64), POINTER(P), I, P, I64, I], QUEUE),
+    "ttsk_op_close_batch_layout": Entry([I, POINTER(I64), POINTER(I64)]),
     "ttsk_cp_chain_step": Entry([P, I64, P, I64, I64, P, P, I64, I64, I64, I64, I64, I], QUEUE),
     "ttsk_cp_psi_omega": Entry([P, I64, P, I64, P, I64, I64, P, P, I64, I64, P, I64, I64, I64, I64, I], QUEUE),
     "ttsk_cp_gram": Entry([POINTER(P), POINTER(I64), I64, POINTER(P), POINTER(I64), I64, POINTER(I64), I, I, P, I], QUEUE),

@@ -17,10 +17,14 @@ Against a product ``N y``, ``N`` of ranks ``S`` with cores ``(S, n_in, n_out, S'
 With ``c`` major the rows of ``Wl`` are ``(c, (gamma, i))``: the pair ``(gamma, i)`` that is contracted against ``N`` is one run, which is
 what the stages of csrc/hadamard_stages.h walk, and ``G'`` comes out in the same ``(c', gamma')`` order for the next mode.  B is
 ``op_close``: one ``ttsk_op_close`` call (csrc/op_close.hip) or its composition from ``contract`` / ``copy_into`` calls.
+
+``op_gram`` is the Gram matrix of lists of products and trains: every pair advances through a mode in
+the same launches -- one ``op_apply`` per distinct ``l`` with the pairs as its terms, one ``ttsk_op_close_batch`` call for
+half B of all of them (``close_batch``) -- and all closing scalars are read back once.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -212,3 +216,226 @@ def op_dot(op: OperatorProduct, oq: OperatorProduct, route: Optional[str] = None
             op_close(W, N if whole else N[:, :, i0:i1, :], Y, out=Gn, accumulate=q > 0, route=route)      # half B
         G = Gn.reshape(R1, r1, s1 * S1)
     return _scalar(G)
+
+
+# ---- the Gram matrix of lists of products and trains: every pair advances through a mode together
+MAX_PAIRS = 23          # OP_CLOSE_MAX_PAIRS of csrc/op_close_batch_plan.h: the pairs of one ttsk_op_close_batch call
+
+
+def close_batch(Wls: Sequence[DevArray], Ns: Sequence[DevArray], Ys: Sequence[DevArray], outs: Sequence[DevArray],
+                accumulate: bool = False, stream: int = 0) -> None:
+    """Half B of many pairs: ``outs[p] (+)=`` what ``op_close`` makes of ``Wls[p]``, ``Ns[p]`` and ``Ys[p]``, by one
+    ``ttsk_op_close_batch`` call per ``MAX_PAIRS`` pairs and with the bits of that pair's ``ttsk_op_close`` call.  A
+    ``Wls[p] (s S, n_out, P)`` is read in place: a column slice of the W of a many-term ``op_apply`` (rows one pitch apart,
+    columns next to each other).  Every N is one run already (``pack``); the ``outs`` are contiguous ``(P, s' S')`` and do not
+    overlap."""
+    for a in range(0, len(Wls), MAX_PAIRS):
+        b = min(a + MAX_PAIRS, len(Wls))
+        dims, strides, ldws = [], [], []
+        for Wl, N, Y, out in zip(Wls[a:b], Ns[a:b], Ys[a:b], outs[a:b]):
+            S, n_in, n_out, S1 = N.shape
+            s, ny, s1 = Y.shape
+            P = int(Wl.shape[2])
+            ldw = Wl.strides[1] if n_out > 1 else (Wl.strides[0] if s * S > 1 else P)
+            if ny != n_in or Wl.shape[:2] != (s * S, n_out) or (P > 1 and Wl.strides[2] != 1) or (s * S > 1 and Wl.strides[0] != n_out * ldw):
+                raise ValueError(f"W of shape {Wl.shape} and strides {Wl.strides} against cores {N.shape} and {Y.shape}")
+            if out.shape != (P, s1 * S1) or not out.is_contiguous():
+                raise ValueError(f"out of shape {out.shape}, expected a contiguous {(P, s1 * S1)}")
+            dims += [S, S1, s, s1, n_in, n_out, P]
+            strides += list(N.strides) + list(Y.strides)
+            ldws.append(ldw)
+        n = b - a
+        offs = nat.i64_array([0] * (n + 1))
+        nat.call("ttsk_op_close_batch_layout", n, nat.i64_array(dims), offs)
+        slab = int(offs[n])
+        work = DevArray.empty((slab,), stream=stream)
+        nat.call("ttsk_op_close_batch", n, nat.ptr_array(Wls[a:b]), nat.ptr_array(Ns[a:b]), nat.ptr_array(Ys[a:b]), nat.i64_array(dims),
+                 nat.i64_array(strides), nat.i64_array(ldws), nat.ptr_array(outs[a:b]), 1 if accumulate else 0, work, slab, stream)
+
+
+def tt_close_route_ms(s: int, s1: int, n: int, P: int, alone: bool = False) -> Tuple[float, float]:
+    """(in the batch, its own `contract`) milliseconds expected for closing a mode against a train core ``Z (s, n, s')``.  In
+    the batch the pair is the degenerate one of ``_Side.right`` (``S = s``, ``s = n_in = 1``): it pays no launch of its own
+    unless it is ``alone`` there, but with one row of ``c`` stage 1 has ONE tile per chunk, which one wave of the four forms
+    (csrc/hadamard_stages.h), so its padded flops count four times, and stage 2 multiplies a padded 4 x 16 block by the one.
+    The `contract` is one launch and the flops asked for.  Constants: those of ``close_route_ms``; measured at both shapes
+    in profiles/operator_gram_batch_bench.json (``close_train``)."""
+    padded = 2.0 * _up(P, 16) * _up(s1, 16) * (4 * _up(s * n, 4) + 4 * 16)
+    return (max(_CLOSE_FLOOR_MS if alone else 0.0, padded / (_CLOSE_TFLOPS * 1e9)),
+            _CLOSE_LAUNCH_MS + 2.0 * P * s1 * s * n / (_CLOSE_GEMM_TFLOPS * 1e9))
+
+
+def _host_dot(a, b) -> float:
+    """one pair on host factors: the NumPy recurrences"""
+    if isinstance(a, OperatorProduct):
+        return op_dot(a, b) if isinstance(b, OperatorProduct) else op_tt_dot(a, b)
+    return op_tt_dot(b, a) if isinstance(b, OperatorProduct) else float(a.dot(b))
+
+
+class _Step(NamedTuple):
+    """one pair at one mode: the cores of half A (M, C) and of half B (N, Y), P = R' r', the columns s' S' of its G', and
+    whether it closes in the batch"""
+    M: DevArray
+    C: DevArray
+    N: DevArray
+    Y: DevArray
+    P: int
+    cols: int
+    kernel: Optional[bool]
+
+
+class _Side:
+    """a member's cores as one side of a pair reads them, fetched once per member"""
+
+    def __init__(self, t) -> None:
+        self.t = t
+        self.product = isinstance(t, OperatorProduct)
+        self._left = self._right = None
+
+    def left(self) -> Tuple[List[DevArray], List[DevArray]]:
+        """(operator cores, train cores) that half A carries the chain through"""
+        if self._left is None:
+            self._left = self.t.dev_parts()
+        return self._left
+
+    def right(self) -> Tuple[List[DevArray], List[DevArray]]:
+        """(N, Y) per mode for half B.  A train z is the product of its cores Z (s, n, s') viewed as operator cores
+        (S = s, n_in = 1, n_out = n, S' = s'), one run as a contiguous core lies, with the train of ones: stage 2 multiplies
+        by exactly 1."""
+        if self._right is None:
+            if self.product:
+                self._right = (packed_views(self.t.mpo), self.t.tt.dev_cores())
+            else:
+                cores = [c.contiguous() for c in self.t.dev_cores()]
+                self._right = ([c.reshape(c.shape[0], 1, c.shape[1], c.shape[2]) for c in cores], [chain_start()] * len(cores))
+        return self._right
+
+
+def _device_gram(As, Bs, todo, sym: bool, route: Optional[str], G: np.ndarray) -> None:
+    from .tensor_gram import _GRAM_MAX_TRAINS, _gram_pass, tt_gram
+    sides_a = [_Side(t) for t in As]
+    sides_b = sides_a if sym else [_Side(t) for t in Bs]
+    # a pair (p, q, left, right): the left side is a product, carried by half A; a train on the left is the swapped pair
+    pairs = []
+    for p, q in todo:
+        a, b = sides_a[p], sides_b[q]
+        if a.product or b.product:
+            pairs.append((p, q, a, b) if a.product else (p, q, b, a))
+    ta = [p for p, a in enumerate(sides_a) if not a.product]
+    tb = ta if sym else [q for q, b in enumerate(sides_b) if not b.product]
+    block = len(ta) * len(tb)                                          # the train-train pairs: one tt_gram block
+    d = len(As[0].shape)
+    chains = [chain_start()] * len(pairs)                              # G_pq (R, r, s S) of every pair, side by side
+    Gn, offs, at = None, [], 0
+    for k in range(d):
+        n_out = int(As[0].shape[k])
+        parts, at = [], 0
+        offs = []
+        for (_, _, a, b), L in zip(pairs, chains):
+            M, C = a.left()[0][k], a.left()[1][k]
+            N, Y = b.right()[0][k], b.right()[1][k]
+            P, cols = M.shape[3] * C.shape[2], Y.shape[2] * N.shape[3]
+            dims = (N.shape[0], N.shape[3], Y.shape[0], Y.shape[2], N.shape[1], n_out, P)
+            if route is not None:
+                kernel = route == "kernel"
+            elif b.product:
+                kernel = taken(None, *close_route_ms(*dims)) == "kernel"
+            else:
+                kernel = None                                           # a train: decided below, once the product pairs are
+            parts.append(_Step(M, C, N, Y, P, cols, kernel))
+            offs.append(at)
+            at += _up(P * cols, 2)                                     # every pair's G' starts on 16 bytes
+        riding = any(pt.kernel for pt in parts)                         # the batch has a launch that a train's pair can ride on
+        parts = [pt if pt.kernel is not None else
+                 pt._replace(kernel=taken(None, *tt_close_route_ms(pt.N.shape[0], pt.N.shape[3], n_out, pt.P, alone=not riding)) == "kernel")
+                 for pt in parts]
+        # the G' of all pairs are slices of one allocation; behind the last mode they are the closing scalars, and the
+        # block of the train-train pairs joins them: one read-back for everything
+        Gn = DevArray.empty((at + (block if k == d - 1 else 0),))
+        outs = [Gn[o:o + pt.P * pt.cols].reshape(pt.P, pt.cols) for o, pt in zip(offs, parts)]
+        cuts = _slices(n_out, max(1, sum(L.shape[2] * pt.P for L, pt in zip(chains, parts))))
+        whole = len(cuts) == 1                                          # a slice of i of a packed core is not one run: packed again
+        for c, (i0, i1) in enumerate(cuts):
+            batch = [x for x, pt in enumerate(parts) if pt.kernel]
+            # ---- half A of the batch: one op_apply per l, the pairs (of one chain and one left product: once) as its terms
+            Wls = {}
+            for l in sorted({chains[x].shape[2] for x in batch}):
+                terms, Ls, Ms, Cs = {}, [], [], []
+                for x in batch:
+                    if chains[x].shape[2] == l and (id(chains[x]), id(pairs[x][2])) not in terms:
+                        terms[(id(chains[x]), id(pairs[x][2]))] = len(Ls)
+                        Ls.append(chains[x])
+                        Ms.append(parts[x].M if whole else parts[x].M[:, :, i0:i1, :])
+                        Cs.append(parts[x].C)
+                W, woffs = op_apply(Ls, Ms, Cs, route=route)
+                W = W.contiguous()
+                for x in batch:
+                    if chains[x].shape[2] == l:
+                        o = woffs[terms[(id(chains[x]), id(pairs[x][2]))]]
+                        Wls[x] = W[:, :, o:o + parts[x].P]
+            # ---- half B of the batch: every pair's Wl in place in the W of its l
+            if batch:
+                close_batch([Wls[x] for x in batch], [parts[x].N if whole else pack(parts[x].N[:, :, i0:i1, :]) for x in batch],
+                            [parts[x].Y for x in batch], [outs[x] for x in batch], accumulate=c > 0)
+            # ---- the others pair by pair, as op_dot and op_tt_dot compose them
+            for x, (M, C, N, Y, P, cols, kernel) in enumerate(parts):
+                if kernel:
+                    continue
+                W, _ = op_apply([chains[x]], [M if whole else M[:, :, i0:i1, :]], [C], route=route)
+                if pairs[x][3].product:
+                    op_close(W, N if whole else N[:, :, i0:i1, :], Y, out=outs[x], accumulate=c > 0, route="composed")
+                else:                                                   # against a train: (g, i) one contracted index of W and of Z
+                    Z = N.reshape(N.shape[0], N.shape[2], N.shape[3])
+                    contract("gip,gih->ph", W, Z[:, i0:i1, :].contiguous(), out=outs[x], accumulate=c > 0)
+        chains = [o.reshape(pt.M.shape[3], pt.C.shape[2], pt.cols) for o, pt in zip(outs, parts)]
+    # ---- the train-train block
+    tt_host = None
+    if block:
+        TA, TB = [As[p] for p in ta], [Bs[q] for q in tb]
+        if Gn is None:
+            Gn, at = DevArray.empty((block,)), 0
+        if not (len(TA) + len(TB) <= _GRAM_MAX_TRAINS and _gram_pass(TA, TB, sym, route, Gn[at:at + block].reshape(len(ta), len(tb)))):
+            tt_host = tt_gram(TA, None if sym else TB, route=route)
+    flat = Gn.get()                                                     # the one read-back
+    for (p, q, _, _), o in zip(pairs, offs):
+        G[p, q] = flat[o]
+    if block:
+        G[np.ix_(ta, tb)] = flat[at:at + block].reshape(len(ta), len(tb)) if tt_host is None else tt_host
+
+
+def op_gram(As, Bs=None, route: Optional[str] = None) -> np.ndarray:
+    """``G[p, q] = <As[p], Bs[q]>`` as a ``(K, M)`` array for lists of ``OperatorProduct``s and ``TensorTrain``s of one shape
+    (``Bs=None``: the symmetric Gram of ``As``, its upper triangle computed and mirrored).  No product is formed.
+
+    Train-train pairs are one ``tt_gram`` block.  Every other pair carries its chain through the modes side by side with the
+    others: per mode one ``op_apply`` per distinct ``l`` with the pairs as its terms, then ONE ``ttsk_op_close_batch`` call
+    that reads every pair's ``Wl`` in place (``close_batch``); a product against a train rides along as the degenerate pair
+    of ``_Side.right``.  All closing scalars lie in one device array and are read once.  A pair in the batch gets the bits
+    ``op_dot`` gives it on the kernel route.
+
+    ``route`` is the switch of ``paths.py``: None sends the pairs for which ``close_route_ms`` names the kernel into the
+    batch and composes the others pair by pair as ``op_dot`` / ``op_tt_dot`` do; ``"kernel"`` sends every pair into the
+    batch and half A to ``ttsk_op_apply``, with the entries' ``TtskUnsupported`` where they refuse; ``"composed"`` calls no
+    entry of the batch.  With every factor of every member on the host the NumPy recurrences run pair by pair and the device
+    is not touched."""
+    route = resolve(route)
+    As = list(As)
+    sym = Bs is None
+    Bs = As if sym else list(Bs)
+    if not As or not Bs:
+        raise ValueError("op_gram: an empty list")
+    for t in As + ([] if sym else Bs):
+        if not isinstance(t, (OperatorProduct, TensorTrain)):
+            raise TypeError(f"op_gram: {type(t).__name__} is neither an OperatorProduct nor a TensorTrain")
+        _check(As[0], t)
+    G = np.empty((len(As), len(Bs)))
+    todo = [(p, q) for p in range(len(As)) for q in range(len(Bs)) if not sym or q >= p]
+    if _host_only(*As, *Bs):
+        for p, q in todo:
+            G[p, q] = _host_dot(As[p], Bs[q])
+    else:
+        _device_gram(As, Bs, todo, sym, route, G)
+    if sym:
+        for p, q in todo:
+            G[q, p] = G[p, q]
+    return G

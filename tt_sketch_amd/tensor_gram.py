@@ -64,11 +64,13 @@ def _gram_composed(As, Bs, sym: bool) -> np.ndarray:
     return G
 
 
-def _gram_block(As: Sequence[TensorTrain], Bs: Sequence[TensorTrain], sym: bool = False, route: Optional[str] = None) -> np.ndarray:
+def _gram_pass(As: Sequence[TensorTrain], Bs: Sequence[TensorTrain], sym: bool, route: Optional[str], out: DevArray) -> bool:
+    """One block by ``ttsk_tt_gram`` into ``out``, a contiguous ``(K, M)`` on the device, nothing read back.  False, and
+    nothing written, where the block goes to the composed chain: ``route`` says so, the rule does, or the entry refuses
+    and the route is not ``"kernel"``."""
     from . import _native as nat
-    route = resolve(route)
     if route == "composed":
-        return _gram_composed(As, Bs, sym)
+        return False
     d = As[0].ndim
     cores = [[c.contiguous() for c in t.dev_cores()] for t in list(As) + list(Bs)]
     ranks = [[c.shape[0] for c in cs] + [cs[-1].shape[2]] for cs in cores]
@@ -76,8 +78,7 @@ def _gram_block(As: Sequence[TensorTrain], Bs: Sequence[TensorTrain], sym: bool 
     if route is None:
         work, chain = _gram_route_ms(np.array(ranks[:K]), np.array(ranks[K:]), As[0].shape)
         if taken(route, work, chain * (K + 1) / (2 * M) if sym else chain) == "composed":   # of a symmetric block the chain forms the upper triangle
-            return _gram_composed(As, Bs, sym)
-    out = DevArray.empty((K, M))
+            return False
     try:
         nat.call("ttsk_tt_gram", nat.ptr_array([c for cs in cores[:K] for c in cs]), nat.i64_array([r for rk in ranks[:K] for r in rk]), K,
                  nat.ptr_array([c for cs in cores[K:] for c in cs]), nat.i64_array([r for rk in ranks[K:] for r in rk]), M,
@@ -85,8 +86,16 @@ def _gram_block(As: Sequence[TensorTrain], Bs: Sequence[TensorTrain], sym: bool 
     except nat.TtskUnsupported:
         if route == "kernel":
             raise
+        return False
+    return True
+
+
+def _gram_block(As: Sequence[TensorTrain], Bs: Sequence[TensorTrain], sym: bool = False, route: Optional[str] = None) -> np.ndarray:
+    route = resolve(route)
+    if route == "composed":
         return _gram_composed(As, Bs, sym)
-    return out.get()
+    out = DevArray.empty((len(As), len(Bs)))
+    return out.get() if _gram_pass(As, Bs, sym, route, out) else _gram_composed(As, Bs, sym)
 
 
 def tt_gram(As: Sequence[TensorTrain], Bs: Optional[Sequence[TensorTrain]] = None, route: Optional[str] = None) -> np.ndarray:

@@ -190,6 +190,16 @@ class TTPrecond(TTLinearMap):
     __call__ = backward_call
 
 
+def _residual_squares(terms, b) -> Tuple[float, float]:
+    """``(||b - sum_p t_p||^2, <b, b>)`` pair by pair: ``<b, b>``, the ``<t_p, b>`` and the ``<t_p, t_q>`` for ``q >= p``, one ``dot``
+    and one scalar each"""
+    bb = b.dot(b)
+    total = bb - 2.0 * sum(t.dot(b) for t in terms)
+    for p, t in enumerate(terms):
+        total += t.dot(t) + 2.0 * sum(t.dot(u) for u in terms[p + 1:])
+    return total, bb
+
+
 class TTLinearMapSum:
     """A list of ``TTLinearMap`` applied to a train (or to each term of a sum of trains); the result
     is the lazy sum of all products (reference tt_gmres.py:171-207).  ``lazy=True``: the ``MPO`` maps among them return
@@ -219,12 +229,19 @@ class TTLinearMapSum:
         """``||b - sum_p A_p x||`` (``relative``: over ``||b||``), the true residual of the linear system, from ``<b, b>``, the
         ``<A_p x, b>`` and the ``<A_p x, A_q x>`` for ``q >= p``, each off-diagonal pair computed once and counted twice.  No
         product ``A_p x`` of an ``MPO`` is formed (``OperatorProduct.dot``); maps that are not ``MPO``s are applied and enter as
-        plain trains.  The squares are subtracted, so a relative residual below about 1e-8 is not resolved."""
+        plain trains.  The squares are subtracted, so a relative residual below about 1e-8 is not resolved.
+
+        With a factor on the device all of these are one symmetric ``operator_gram.op_gram`` of the ``A_p x`` and ``b``: every
+        pair advances through a mode in the same launches and the scalars are read back once.  Host
+        factors keep the pair-by-pair NumPy recurrences."""
+        from .operator_gram import _host_only, op_gram
         terms = [OperatorProduct(lm, x) if isinstance(lm, MPO) and type(x) is TensorTrain else lm(x) for lm in self.linear_maps]
-        bb = b.dot(b)
-        total = bb - 2.0 * sum(t.dot(b) for t in terms)
-        for p, t in enumerate(terms):
-            total += t.dot(t) + 2.0 * sum(t.dot(u) for u in terms[p + 1:])
+        if all(isinstance(t, (OperatorProduct, TensorTrain)) for t in terms + [b]) and not _host_only(*terms, b):
+            G, k = op_gram(terms + [b]), len(terms)
+            bb = float(G[k, k])
+            total = bb - 2.0 * float(G[:k, k].sum()) + float(G[:k, :k].sum())
+        else:
+            total, bb = _residual_squares(terms, b)
         res = float(np.sqrt(max(total, 0.0)))
         if relative:
             return res / float(np.sqrt(bb)) if bb > 0 else float("inf")
