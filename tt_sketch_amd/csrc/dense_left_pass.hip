@@ -23,16 +23,13 @@
 // workgroups per CU in turn), bytes: X once + A_3 once + Z_0 written = 14 GB.
 #include <type_traits>
 #include "common.h"
+#include "dense_pass_plan.h"
 #include "prof.h"
 #include "skinny.h"
 
 namespace ttsk {
 
 namespace {
-
-constexpr int LP_CT = 512;       // columns per workgroup
-constexpr int LP_XP = 528;       // row pitch of the X image (16 mod 32: the two k rows a half wave reads hit different banks)
-constexpr int LP_MAXI3 = 9;      // i3 values a column tile may span: (3 + that) x 80 gathered A elements <= 1024 = two per thread
 
 struct LeftPass {
     const double *X;
@@ -256,33 +253,26 @@ extern "C" int ttsk_dense_left_pass(const double *X, int64_t n0, int64_t n1, int
 {
     TTSK_STREAM(st, stream);
     TTSK_ARG(X && A0 && A1t && A2t && A3p && Z0 && Z1 && Z2 && E3, "ttsk_dense_left_pass: NULL argument");
-    TTSK_ARG(n0 >= 1 && n1 >= 1 && n2 >= 1 && C >= 1 && n4 >= 1 && l >= 1, "ttsk_dense_left_pass: bad shape");
-    const bool ok = n0 % 4 == 0 && C % LP_CT == 0 && C % n4 == 0 && n4 % 16 == 0 && LP_CT % n4 == 0 && LP_CT / n4 <= LP_MAXI3 &&
-                    l <= 20 && n0 <= (1 << 20) && n1 <= (1 << 20) && n2 <= (1 << 16) && n2 * (C / LP_CT) < (1ll << 30) &&
-                    (double)l * n0 * n1 * n2 * (C / n4) * 8 < 4.0e9 && (double)4 * n1 * n2 * C * 8 < 4.0e9;      // 32-bit lane offsets
-    if (!ok) {
-        set_error("ttsk_dense_left_pass: shape (%lld, %lld, %lld, C = %lld, n4 = %lld), l = %d is outside the kernel's cover",
-                  (long long)n0, (long long)n1, (long long)n2, (long long)C, (long long)n4, l);
-        return TTSK_ERR_UNSUPPORTED;
+    DenseLeftPlan p;
+    if (const int prc = dense_left_plan(n0, n1, n2, C, n4, l, &p)) {
+        set_error("%s", p.msg);
+        return prc;
     }
     LeftPass a{};
     a.X = X; a.A0 = A0; a.A1t = A1t; a.A2t = A2t; a.A3p = A3p;
     a.Z0 = Z0; a.Z1 = Z1;
     a.n0 = (int)n0; a.n1 = (int)n1; a.n2 = (int)n2; a.n4 = (int)n4; a.l = l;
     a.C = C;
-    a.ni3 = (int)(LP_CT / n4);
-    a.nct = (int)(C / LP_CT);
-    a.xcd_map = (n2 % 8 == 0) ? 1 : 0;
+    a.ni3 = p.ni3;
+    a.nct = p.nct;
+    a.xcd_map = p.xcd_map;
     // the partial Z_2 / E_3 of the n2 workgroup rows: [i2][l][C] each, summed below
-    const size_t slab = (size_t)n2 * l * C;
-    double *ws = (double *)scratch(stream, SCRATCH_GEMM, 2 * slab * 8 + 64);
+    double *ws = (double *)scratch(stream, SCRATCH_GEMM, p.scratch_bytes);
     if (!ws) return TTSK_ERR_HIP;
     a.slab2 = ws;
-    a.slab3 = ws + slab;
-    const size_t lds = ((size_t)4 * 4 * LP_XP + (size_t)4 * (((3 + a.ni3) * 80 + 127) / 128 * 128 + 128)) * 8;
-    const unsigned grid = (unsigned)(n2 * a.nct);
-    ProfBracket prof(st, PROF_CURRENT, 8.0 * l * (double)n0 * n1 * n2 * C, "dense_left_pass_kernel");
-    int rc = launch(l > 16 ? dense_left_pass_kernel<true> : dense_left_pass_kernel<false>, dim3(grid), dim3(512), lds, st, a);
+    a.slab3 = ws + p.slab;
+    ProfBracket prof(st, PROF_CURRENT, p.flops, "dense_left_pass_kernel");
+    int rc = launch(p.strip ? dense_left_pass_kernel<true> : dense_left_pass_kernel<false>, dim3((unsigned)p.grid), dim3(512), p.lds, st, a);
     if (rc != TTSK_OK) return rc;
     // Z_2 = sum_{i2} slab2[i2], E_3 likewise: the slabs are [chunk = i2][M = l][N = C]
     ReduceOut r2{}, r3{};

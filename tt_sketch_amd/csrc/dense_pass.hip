@@ -36,6 +36,7 @@
 // accumulator registers at 4 + 0) -- a first mode of 64 is then two blocks, their partial Z summed as for longer modes.  An odd
 // r reads a copy of P padded to r + 1 columns (16-byte units need an even row).
 #include "common.h"
+#include "dense_pass_plan.h"
 #include "prof.h"
 #include <type_traits>
 
@@ -72,10 +73,6 @@ struct DensePass {
     int p_half, z_half;    //    rows [k z_half, ..) of Z -- each reads the tile (the second read from L2 / MALL); 0: one kind takes all
     int dbg;               // diagnostics (TTSK_DP_DBG): 1 = no tile loads after the first, 2 = no Z stores, 4 = no rotated start, 8 = loads and stores of a tile in one burst
 };
-
-// doubles per row of the P image: the columns in use rounded up to 16 mod 32 (rows kq, kq + 1 on disjoint halves of the banks):
-// 48 for 2 tiles + 2 strips (40 used) and for 3 tiles, 80 for 4 tiles
-constexpr int dp_prow(int TP, int SP) { return (16 * TP + 4 * SP + 15) / 32 * 32 + 16; }
 
 template <int NBW, int TP, int SP, int ZT, int ZS>
 __global__ __launch_bounds__(512) void dense_pass_kernel(DensePass a)
@@ -364,72 +361,39 @@ __global__ __launch_bounds__(256) void dense_pass_pad_p(const double *P, int64_t
 }
 
 template <int NBW, int TP, int SP, int ZT, int ZS>
-int dense_pass_launch(const DensePass &a, int64_t grid, hipStream_t st)
+int dense_pass_launch(const DensePass &a, const DenseFirstPlan &p, hipStream_t st)
 {
-    constexpr int NB = 8 * NBW;
-    const size_t lds = (size_t)(2 * NB * 128 + 2 * 8 * dp_prow(TP, SP) + NB * (16 * ZT + 4 * ZS)) * 8;
-    return launch(dense_pass_kernel<NBW, TP, SP, ZT, ZS>, dim3((unsigned)grid), dim3(512), lds, st, a);
+    return launch(dense_pass_kernel<NBW, TP, SP, ZT, ZS>, dim3((unsigned)p.grid), dim3(512), p.lds, st, a);
 }
 
 }  // namespace
 
 }  // namespace ttsk
 
+// What is launched is decided by dense_first_plan (dense_pass_plan.h): the cover, the instantiation, the grid, the scratch.
 extern "C" int ttsk_dense_first_pass(const double *X, int64_t n0, int64_t Q, int64_t T, const double *C, int64_t ll,
                                      const double *P, int64_t r, double *Z, double *U, int stream)
 {
     using namespace ttsk;
     TTSK_ARG(X && C && P && Z && U, "ttsk_dense_first_pass: NULL operand");
-    TTSK_ARG(n0 > 0 && Q > 0 && T > 0 && ll > 0 && r > 0, "ttsk_dense_first_pass: empty extent");
-    if ((n0 & 31) || n0 > 64 * 64 || (T & 15) || (Q & 7) || ll > 32 || r > 64 || Q * T >= (1ll << 27) ||
-        (((uintptr_t)X | (uintptr_t)P | (uintptr_t)Z) & 15)) {
-        set_error("ttsk_dense_first_pass: shape outside the kernel's cover (first mode a multiple of 32, last mode a multiple "
-                  "of 16, middle extent a multiple of 8, left rank <= 32, right rank <= 64)");
-        return TTSK_ERR_UNSUPPORTED;
-    }
+    DenseFirstPlan p;
+    const int prc = dense_first_plan(n0, Q, T, ll, r, (unsigned)(((uintptr_t)X | (uintptr_t)P | (uintptr_t)Z) & 15), &p);
+    // the order of the checks as it always was: extents and cover, the stream, then the 4 GB rule of the partial results
+    if (prc && !p.in_cover) { set_error("%s", p.msg); return prc; }
     TTSK_STREAM(st, stream);
-    const int nt = (int)(T / 16);
-    // accumulator shapes: U as TP tiles + SP strips of columns, Z as ZT tiles + ZS strips of rows.  Up to 40 / 20: one kind of
-    // workgroup, blocks of 64 values of b (the C2 shape).  Beyond, with whole blocks of 64: TWO kinds of workgroups, each with
-    // half the columns of U and half the rows of Z -- the accumulators of all 64 b fit, Z needs no partial sums over blocks
-    // of b, the matrix work stays proportional to the ranks, and the tile is read twice, the kinds of a (t range, q range) one
-    // dispatch round apart on one XCD.  Otherwise (first mode a multiple of 32 only): blocks of 32 with wider accumulators.
-    // just beyond 20 / 40 (r <= 44, ll <= 24): one more strip of either still fits one kind of workgroup (11 spilled registers, outside the step loop)
-    const bool one_kind = !(n0 & 63) && (r > 40 || ll > 20) && r <= 44 && ll <= 24;
-    const bool split = !one_kind && !(n0 & 63) && (r > 40 || ll > 20);
-    const int p_half = split ? (int)((r + 1) / 2 + 3) / 4 * 4 : 0, z_half = split ? (int)((ll + 1) / 2 + 3) / 4 * 4 : 0;
-    const int ushape = split ? (p_half <= 24 ? 3 : 4) : r <= 40 ? 0 : r <= 48 ? 1 : 2;
-    const int zshape = split ? (z_half <= 12 ? 2 : 3) : ll <= 20 ? 0 : 1;
-    const int TP = one_kind ? 2 : ushape == 0 ? 2 : ushape == 1 ? 3 : ushape == 2 ? 4 : ushape == 3 ? 1 : 2;
-    const int SP = one_kind ? 3 : ushape == 0 || ushape == 3 ? 2 : 0;
-    const int NB = (one_kind || split || (ushape == 0 && zshape == 0 && !(n0 & 63))) ? 64 : 32, nbb = (int)(n0 / NB);
-    const int kinds = split ? 2 : 1;
-    // q ranges: about 256 workgroups for one block of b, about 1024 over all blocks otherwise (several rounds over the CUs even
-    // out the ranges); a multiple of 8, and not more than there are tiles
-    int64_t nqc = 8 * std::max<int64_t>(1, (nbb == 1 ? 32 : (128 + nbb * nt / 2) / (nbb * nt)) / (nbb == 1 ? nt : 1));
-    nqc = std::min<int64_t>(nqc, 8 * cdiv(Q / 8, 8));          // at least one tile for most chunks
-    const int64_t grid1 = (int64_t)nbb * nt * nqc, grid = grid1 * kinds;
-    const int64_t sl64 = (4 * TP + SP) * 64;
-    // partial results beyond 4 GB (many blocks of a large operand): not this kernel's case -- the caller forms the products separately
-    if ((nbb > 1 && (int64_t)nbb * ll * Q * T * 8 > (4ll << 30)) || grid * NB * sl64 * 8 > (4ll << 30)) {
-        set_error("ttsk_dense_first_pass: %d blocks of rows would need more than 4 GB of partial results", nbb);
-        return TTSK_ERR_UNSUPPORTED;
-    }
-    const int64_t pr = r + (r & 1);
-    const size_t pad_bytes = (r & 1) ? (size_t)Q * pr * 8 + 64 : 0;
-    char *ws = (char *)scratch(stream, SCRATCH_MISC, (size_t)grid * NB * sl64 * 8 + pad_bytes);
+    if (prc) { set_error("%s", p.msg); return prc; }
+    char *ws = (char *)scratch(stream, SCRATCH_MISC, p.slab_bytes + p.pad_bytes);
     if (!ws) return TTSK_ERR_HIP;
     double *slab = (double *)ws;
     if (r & 1) {
-        double *pp = (double *)(ws + (size_t)grid * NB * sl64 * 8);
-        if (int rc = launch(dense_pass_pad_p, dim3((unsigned)cdiv(Q * pr, 256)), dim3(256), 0, st, P, Q, (int)r, pp)) return rc;
+        double *pp = (double *)(ws + p.slab_bytes);
+        if (int rc = launch(dense_pass_pad_p, dim3((unsigned)cdiv(Q * p.pr, 256)), dim3(256), 0, st, P, Q, (int)r, pp)) return rc;
         P = pp;
     }
     // blocks of b: each block's Z is a partial sum over its values of b
-    const int64_t zblock = ll * Q * T;
     double *zout = Z;
-    if (nbb > 1) {
-        zout = (double *)scratch(stream, SCRATCH_GEMM, (size_t)nbb * zblock * 8);
+    if (p.nbb > 1) {
+        zout = (double *)scratch(stream, SCRATCH_GEMM, p.zpart_bytes);
         if (!zout) return TTSK_ERR_HIP;
     }
 #ifdef TTSK_LAB
@@ -437,28 +401,34 @@ extern "C" int ttsk_dense_first_pass(const double *X, int64_t n0, int64_t Q, int
 #else
     constexpr int dbg = 0;
 #endif
-    DensePass a{X, Q * T, (int)Q, (int)T, C, (int)ll, P, (int)r, (int)pr, zout, slab, nt, (int)nqc, zblock, split ? 1 : 0, p_half, z_half, dbg};
+    DensePass a{X, Q * T, (int)Q, (int)T, C, (int)ll, P, (int)r, (int)p.pr, zout, slab, p.nt, p.nqc, p.zblock, p.split ? 1 : 0, p.p_half, p.z_half, dbg};
     ProfBracket prof(st, PROF_SOLVE, 0.0, "dense_pass");             // the whole sequence: pass, reduces, sum over the blocks
+    const int inst = (((p.NBW * 10 + p.TP) * 10 + p.SP) * 10 + p.ZT) * 10 + p.ZS;
     int rc;
-    if (one_kind) rc = dense_pass_launch<8, 2, 3, 1, 2>(a, grid, st);
-    else if (split) {
-        if (ushape == 3) rc = zshape == 2 ? dense_pass_launch<8, 1, 2, 0, 3>(a, grid, st) : dense_pass_launch<8, 1, 2, 1, 0>(a, grid, st);
-        else rc = zshape == 2 ? dense_pass_launch<8, 2, 0, 0, 3>(a, grid, st) : dense_pass_launch<8, 2, 0, 1, 0>(a, grid, st);
-    } else if (NB == 64) rc = dense_pass_launch<8, 2, 2, 1, 1>(a, grid, st);
-    else if (ushape == 0) rc = zshape == 0 ? dense_pass_launch<4, 2, 2, 1, 1>(a, grid, st) : dense_pass_launch<4, 2, 2, 2, 0>(a, grid, st);
-    else if (ushape == 1) rc = zshape == 0 ? dense_pass_launch<4, 3, 0, 1, 1>(a, grid, st) : dense_pass_launch<4, 3, 0, 2, 0>(a, grid, st);
-    else rc = zshape == 0 ? dense_pass_launch<4, 4, 0, 1, 1>(a, grid, st) : dense_pass_launch<4, 4, 0, 2, 0>(a, grid, st);
-    if (rc != TTSK_OK) { set_error("ttsk_dense_first_pass: launch failed"); return rc; }
-    const int64_t elems = (int64_t)NB * sl64 * nt * nbb;
-    for (int k = 0; k < kinds; ++k) {
-        const int p_off = k * p_half, pcount = split ? (k == 0 ? std::min<int>(p_half, (int)r) : (int)r - p_half) : (int)r;
-        if (pcount <= 0) continue;
-        if ((rc = launch(dense_pass_reduce, dim3((unsigned)cdiv(elems, 256)), dim3(256), 0, st, slab + (size_t)k * grid1 * NB * sl64, NB, TP, SP, nt,
-                         (int)nqc, nbb, (int)T, (int)r, U, p_off, pcount))) return rc;
+    switch (inst) {
+    case 82312: rc = dense_pass_launch<8, 2, 3, 1, 2>(a, p, st); break;
+    case 81203: rc = dense_pass_launch<8, 1, 2, 0, 3>(a, p, st); break;
+    case 81210: rc = dense_pass_launch<8, 1, 2, 1, 0>(a, p, st); break;
+    case 82003: rc = dense_pass_launch<8, 2, 0, 0, 3>(a, p, st); break;
+    case 82010: rc = dense_pass_launch<8, 2, 0, 1, 0>(a, p, st); break;
+    case 82211: rc = dense_pass_launch<8, 2, 2, 1, 1>(a, p, st); break;
+    case 42211: rc = dense_pass_launch<4, 2, 2, 1, 1>(a, p, st); break;
+    case 42220: rc = dense_pass_launch<4, 2, 2, 2, 0>(a, p, st); break;
+    case 43011: rc = dense_pass_launch<4, 3, 0, 1, 1>(a, p, st); break;
+    case 43020: rc = dense_pass_launch<4, 3, 0, 2, 0>(a, p, st); break;
+    case 44011: rc = dense_pass_launch<4, 4, 0, 1, 1>(a, p, st); break;
+    case 44020: rc = dense_pass_launch<4, 4, 0, 2, 0>(a, p, st); break;
+    default: set_error("ttsk_dense_first_pass: no instantiation <%d, %d, %d, %d, %d>", p.NBW, p.TP, p.SP, p.ZT, p.ZS); return TTSK_ERR_ARG;
     }
-    if (nbb > 1) {
-        const int64_t pairs = zblock / 2;               // Q T is a multiple of 128
-        if ((rc = launch(dense_pass_zsum, dim3((unsigned)cdiv(pairs, 256)), dim3(256), 0, st, (const double2 *)zout, nbb, pairs, (double2 *)Z))) return rc;
+    if (rc != TTSK_OK) { set_error("ttsk_dense_first_pass: launch failed"); return rc; }
+    for (int k = 0; k < p.kinds; ++k) {
+        if (p.pcount[k] <= 0) continue;
+        if ((rc = launch(dense_pass_reduce, dim3((unsigned)cdiv(p.elems, 256)), dim3(256), 0, st, slab + (size_t)k * p.grid1 * p.NB * p.sl64, p.NB, p.TP,
+                         p.SP, p.nt, p.nqc, p.nbb, (int)T, (int)r, U, p.p_off[k], p.pcount[k]))) return rc;
+    }
+    if (p.nbb > 1) {
+        const int64_t pairs = p.zblock / 2;             // Q T is a multiple of 128
+        if ((rc = launch(dense_pass_zsum, dim3((unsigned)cdiv(pairs, 256)), dim3(256), 0, st, (const double2 *)zout, p.nbb, pairs, (double2 *)Z))) return rc;
     }
     return TTSK_OK;
 }
