@@ -28,16 +28,13 @@
 #include <vector>
 #include "common.h"
 #include "linalg_int.h"
+#include "assemble_batch_plan.h"
 
 using namespace ttsk;
 
 namespace {
 
-constexpr int AB_TM = 32;            // rows of a tile
-constexpr int AB_THREADS = 256;
-constexpr int AB_MAXG = 16;          // groups per launch (kernel argument)
-constexpr int AB_TILES_PER_WG = 16;  // row tiles a workgroup sweeps (P', Omega' are loaded once for them)
-constexpr int AB_COVER_MIN = 56, AB_COVER_MAX = 112;
+// AB_TM, AB_THREADS, AB_MAXG, AB_TILES_PER_WG and the cover: assemble_batch_plan.h, with every launch decision below
 
 // one mode of `count` tensors whose operands are equally spaced (base + tensor * stride)
 struct AbGroup {
@@ -267,28 +264,20 @@ struct AbPair {
     int k, b;
 };
 
-// runs of equally spaced tensors within each mode; a group's `first`: the index of its first pair (= its place in the staging buffers)
-std::vector<AbGroup> make_groups(const std::vector<AbPair> &pairs)
+// the group table of one launch: the plan's groups [t.g0, t.g0 + t.ng) with the operands of their first pairs
+AbTable make_table(const std::vector<AbPair> &pairs, const std::vector<AbGroupPlan> &groups, const AbLaunchPlan &lp)
 {
-    std::vector<AbGroup> out;
-    for (size_t i = 0; i < pairs.size();) {
-        size_t j = i + 1;
-        const AbPair &p0 = pairs[i];
-        int64_t dpsi = 0, dom = 0, dc = 0, dw = 0;
-        if (j < pairs.size() && pairs[j].k == p0.k) {
-            dpsi = pairs[j].psi - p0.psi; dom = pairs[j].om - p0.om; dc = pairs[j].c - p0.c; dw = pairs[j].work - p0.work;
-        }
-        while (j < pairs.size() && pairs[j].k == p0.k && pairs[j].psi - pairs[j - 1].psi == dpsi && pairs[j].om - pairs[j - 1].om == dom &&
-               pairs[j].c - pairs[j - 1].c == dc && pairs[j].work - pairs[j - 1].work == dw)
-            ++j;
-        AbGroup g{};
+    AbTable t{};
+    t.ng = lp.ng;
+    for (int i = 0; i < lp.ng; ++i) {
+        const AbGroupPlan &gp = groups[lp.g0 + i];
+        const AbPair &p0 = pairs[gp.first];
+        AbGroup &g = t.g[i];
         g.psi = p0.psi; g.om = p0.om; g.pin = p0.work; g.pout = p0.work; g.c = p0.c;
-        g.s_psi = dpsi; g.s_om = dom; g.s_pin = dw; g.s_pout = dw; g.s_c = dc;
-        g.m = p0.m; g.count = (int)(j - i); g.chunks = 1; g.first = (int)i;
-        out.push_back(g);
-        i = j;
+        g.s_psi = gp.s_psi; g.s_om = gp.s_om; g.s_pin = gp.s_work; g.s_pout = gp.s_work; g.s_c = gp.s_c;
+        g.m = gp.m; g.count = gp.count; g.chunks = lp.chunks[i]; g.first = lp.first[i];
     }
-    return out;
+    return t;
 }
 
 int apply_fallback(const std::vector<AbPair> &pairs, int64_t l, int64_t r, int direction, int stream, hipStream_t st)
@@ -312,67 +301,54 @@ int apply_fallback(const std::vector<AbPair> &pairs, int64_t l, int64_t r, int d
     return TTSK_OK;
 }
 
-// the pairs of one Omega shape (l x r)
+// the pairs of one Omega shape (l x r): what is launched is decided by assemble_batch_plan.h
 int assemble_shape(const std::vector<AbPair> &pairs, int64_t l, int64_t r, int direction, int stream, hipStream_t st)
 {
     int rc;
-    const bool covered = std::min(l, r) <= AB_COVER_MIN && std::max(l, r) <= AB_COVER_MAX && pinv_batch_fast(l, r);
-    if (!covered) {
+    AbShapePlan sp;
+    ab_shape_plan(l, r, direction, (int)pairs.size(), pinv_batch_fast(l, r), &sp);
+    if (!sp.covered) {
         for (const AbPair &p : pairs) {
             if ((rc = ttsk_pinv_begin(p.om, l, r, -1.0, p.work, stream)) < 0) return rc;
             if ((rc = ttsk_pinv_end(p.om, l, r, -1.0, p.work, nullptr, stream)) < 0) return rc;
         }
         return apply_fallback(pairs, l, r, direction, stream, st);
     }
-    const int T = (int)pairs.size(), n = (int)std::min(l, r), K = (int)std::max(l, r);
-    const size_t lr = (size_t)l * r, nn = (size_t)n * n;
-    auto blk = [](size_t v) { return (v + 31) & ~(size_t)31; };
-    const size_t szO = blk(T * lr), szG = blk(T * nn);
-    double *ws = (double *)scratch(stream, SCRATCH_ORTH, (2 * szO + 3 * szG + blk((size_t)T)) * 8);
+    double *ws = (double *)scratch(stream, SCRATCH_ORTH, sp.bytes);
     if (!ws) return TTSK_ERR_HIP;
-    double *Os = ws, *Ps = Os + szO, *Gm = Ps + szO, *Rinv = Gm + szG, *Ginv = Rinv + szG;
-    int *status = (int *)(Ginv + szG);
-    const std::vector<AbGroup> groups = make_groups(pairs);
+    double *Os = ws + sp.off_Os, *Ps = ws + sp.off_Ps, *Gm = ws + sp.off_Gm, *Rinv = ws + sp.off_Rinv, *Ginv = ws + sp.off_Ginv;
+    int *status = (int *)(ws + sp.off_status);
+    // the grouping works on element offsets from the first pair's operands
+    std::vector<AbPairOff> offs(pairs.size());
+    for (size_t i = 0; i < pairs.size(); ++i)
+        offs[i] = AbPairOff{pairs[i].psi - pairs[0].psi, pairs[i].om - pairs[0].om, pairs[i].c - pairs[0].c, pairs[i].work - pairs[0].work,
+                            pairs[i].m, pairs[i].k};
+    const std::vector<AbGroupPlan> groups = ab_make_groups(offs);
+    char msg[200];
+    AbLaunchPlan lp;
     // ---- pseudo-inverses: gram, chol, solve, jacobi
     for (size_t g0 = 0; g0 < groups.size(); g0 += AB_MAXG) {
-        AbTable t{};
-        t.ng = (int)std::min<size_t>(AB_MAXG, groups.size() - g0);
-        for (int i = 0; i < t.ng; ++i) t.g[i] = groups[g0 + i];
-        const int wgs = t.g[t.ng - 1].first + t.g[t.ng - 1].count - t.g[0].first;
-        // (the pair index of a group's first tensor is its `first`: the groups of a launch follow one another)
-        const int base = t.g[0].first;
-        for (int i = 0; i < t.ng; ++i) t.g[i].first -= base;
-        if ((rc = launch(assemble_gram_kernel, dim3((unsigned)wgs), dim3(AB_THREADS), (size_t)K * n * 8, st, t, (int)l, (int)r,
-                         Os + (size_t)base * lr, Gm + (size_t)base * nn))) return rc;
+        ab_gram_launch(groups, g0, &lp);
+        if ((rc = launch(assemble_gram_kernel, dim3((unsigned)lp.wgs), dim3(AB_THREADS), sp.gram_lds, st, make_table(pairs, groups, lp), (int)l,
+                         (int)r, Os + (size_t)lp.base * sp.lr, Gm + (size_t)lp.base * sp.nn))) return rc;
     }
-    if ((rc = chol_inv_batch(Gm, n, Rinv, Ginv, status, T, st))) return rc;
-    if ((rc = launch(assemble_solve_kernel, dim3((unsigned)T), dim3(AB_THREADS), ((size_t)K * n + nn) * 8, st, (int)l, (int)r, Os, Ginv, Ps))) return rc;
-    rc = jacobi_pinv_spaced(T, Os, (int64_t)lr, l, r, Ps, (int64_t)lr, status, st);
+    if ((rc = chol_inv_batch(Gm, sp.n, Rinv, Ginv, status, sp.T, st))) return rc;
+    if ((rc = launch(assemble_solve_kernel, dim3((unsigned)sp.T), dim3(AB_THREADS), sp.solve_lds, st, (int)l, (int)r, Os, Ginv, Ps))) return rc;
+    rc = jacobi_pinv_spaced(sp.T, Os, (int64_t)sp.lr, l, r, Ps, (int64_t)sp.lr, status, st);
     if (rc < 0) return rc;
-    if (rc == 0) { set_error("ttsk_tt_assemble_batch: Jacobi kernel outside its LDS cover (%lld x %lld)", (long long)l, (long long)r); return TTSK_ERR_UNSUPPORTED; }
+    if (rc == 0) { ab_msg_jacobi(msg, sizeof(msg), l, r); set_error("%s", msg); return TTSK_ERR_UNSUPPORTED; }
     // ---- fused apply: P and Omega from the staging buffers, P copied out to the caller's work
-    const int a = (int)(direction == 0 ? r : l), b = (int)(direction == 0 ? l : r);
-    auto u4 = [](int x) { return (x + 3) & ~3; };
-    auto u16 = [](int x) { return (x + 15) & ~15; };
-    const size_t lds = (size_t)(u4(a) * u16(b) + u4(b) * u16(a) + AB_TM * (u16(a) + 2) + AB_TM * (u16(b) + 2)) * 8;
-    if (lds > 160 * 1024) { set_error("ttsk_tt_assemble_batch: LDS of the fused apply"); return TTSK_ERR_UNSUPPORTED; }
+    if (!sp.apply_lds_ok) { ab_msg_lds(msg, sizeof(msg)); set_error("%s", msg); return TTSK_ERR_UNSUPPORTED; }
     for (size_t g0 = 0; g0 < groups.size(); g0 += AB_MAXG) {
-        AbTable t{};
-        t.ng = (int)std::min<size_t>(AB_MAXG, groups.size() - g0);
-        int wgs = 0;
+        ab_apply_launch(groups, g0, &lp);
+        AbTable t = make_table(pairs, groups, lp);
         for (int i = 0; i < t.ng; ++i) {
-            AbGroup g = groups[g0 + i];
-            const int pair = g.first;
-            g.om = Os + (size_t)pair * lr; g.s_om = (int64_t)lr;
-            g.pin = Ps + (size_t)pair * lr; g.s_pin = (int64_t)lr;
-            const int64_t ntiles = (g.m + AB_TM - 1) / AB_TM;
-            g.chunks = (int)std::max<int64_t>(1, (ntiles + AB_TILES_PER_WG - 1) / AB_TILES_PER_WG);
-            g.first = wgs;
-            wgs += g.count * g.chunks;
-            t.g[i] = g;
+            const int pair = groups[g0 + i].first;
+            t.g[i].om = Os + (size_t)pair * sp.lr; t.g[i].s_om = (int64_t)sp.lr;
+            t.g[i].pin = Ps + (size_t)pair * sp.lr; t.g[i].s_pin = (int64_t)sp.lr;
         }
-        if ((rc = launch(direction == 0 ? assemble_apply_kernel<false> : assemble_apply_kernel<true>, dim3((unsigned)wgs), dim3(AB_THREADS),
-                         lds, st, t, a, b))) return rc;
+        if ((rc = launch(direction == 0 ? assemble_apply_kernel<false> : assemble_apply_kernel<true>, dim3((unsigned)lp.wgs), dim3(AB_THREADS),
+                         sp.apply_lds, st, t, sp.a, sp.b))) return rc;
     }
     return TTSK_OK;
 }
