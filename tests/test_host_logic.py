@@ -436,7 +436,7 @@ def test_every_launch_goes_through_the_one_checked_helper():
 
 
 def test_each_solver_decision_has_one_definition():
-    """common.h's builders are the only place a ttsk_gemm_desc is filled (gemm_kernel.h holds one as a launch argument), the
+    """common.h's builders are the only place a ttsk_gemm_desc is filled (gemm_plan.h holds one as a launch argument), the
     normal-equations pseudo-inverse is one list of stages (no TTSK_PB macros per entry point), the sign reconstruction of one
     matrix is the batched kernel's, and linalg.hip is split by solver."""
     import glob
@@ -444,7 +444,7 @@ def test_each_solver_decision_has_one_definition():
     csrc = os.path.join(os.path.dirname(nat.__file__), "csrc")
     src = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))}
     where = lambda pat: sorted(f for f, s in src.items() if re.search(pat, s))
-    assert where(r"\bttsk_gemm_desc\s+\w+\s*(\{\s*\}|;)") == ["common.h", "gemm_kernel.h"]
+    assert where(r"\bttsk_gemm_desc\s+\w+\s*(\{\s*\}|;)") == ["common.h", "gemm_plan.h"]
     assert where(r"\bTTSK_PB\b") == []
     assert where(r"\bqr_signs_kernel\b") == []
     assert "linalg.hip" not in src and {"jacobi.hip", "householder.hip", "cholesky.hip", "pinv.hip"} <= set(src)

@@ -511,9 +511,9 @@ inline double *chain_slab_request(int stream, const ChainLaunch &l) { return (do
 // ... and reduce it into Out[b] (J x A2 contiguous)
 inline int chain_slab_reduce(hipStream_t st, const double *slab, const ChainLaunch &l, const ChainStepArgs &c)
 {
-    ReduceOut ro{};
-    for (int b = 0; b < c.nb; ++b) ro.C[b] = c.Out[b];
-    return launch_r_reduce(st, slab, l.red_chunks, l.red_m, l.red_n, 1, (int64_t)c.J, ro, c.nb, (int64_t)c.A2, (int64_t)1, 1.0, 0);
+    RReduceArgs r{l.red_chunks, l.red_m, l.red_n, 1, c.nb, (int64_t)c.J, (int64_t)c.A2, 1, 1.0, 0, {}};
+    for (int b = 0; b < c.nb; ++b) r.out.C[b] = c.Out[b];
+    return launch_r_reduce(st, slab, r);
 }
 
 // 1 = launched (the slab reduce included), 0 = shape not covered, < 0 = error

@@ -275,10 +275,10 @@ extern "C" int ttsk_dense_left_pass(const double *X, int64_t n0, int64_t n1, int
     int rc = launch(p.strip ? dense_left_pass_kernel<true> : dense_left_pass_kernel<false>, dim3((unsigned)p.grid), dim3(512), p.lds, st, a);
     if (rc != TTSK_OK) return rc;
     // Z_2 = sum_{i2} slab2[i2], E_3 likewise: the slabs are [chunk = i2][M = l][N = C]
-    ReduceOut r2{}, r3{};
-    r2.C[0] = Z2;
-    r3.C[0] = E3;
-    rc = launch_r_reduce(st, a.slab2, (int)n2, l, (int)C, 1, (int64_t)l, r2, 1, C, 1, 1.0, 0);
-    if (rc == TTSK_OK) rc = launch_r_reduce(st, a.slab3, (int)n2, l, (int)C, 1, (int64_t)l, r3, 1, C, 1, 1.0, 0);
+    RReduceArgs r{(int)n2, l, (int)C, 1, 1, (int64_t)l, C, 1, 1.0, 0, {}};
+    r.out.C[0] = Z2;
+    rc = launch_r_reduce(st, a.slab2, r);
+    r.out.C[0] = E3;
+    if (rc == TTSK_OK) rc = launch_r_reduce(st, a.slab3, r);
     return rc;
 }

@@ -23,14 +23,7 @@ namespace ttsk {
 
 namespace {
 
-constexpr int RP_BROWS = 48;     // rows of the B tile (N <= 48; rows beyond N repeat the last one, their columns are not stored)
-
-struct RightPass {
-    const double *S, *B;
-    double *slab;                // [row block][K range][64][N]
-    int64_t rows, s_row, b_row, K;
-    int N, nrb, nkc;
-};
+// RP_BROWS and RightPass, the kernel's arguments: gemm_plan.h
 
 __global__ __launch_bounds__(512, 2) void rows_longk_kernel(RightPass a)
 {
@@ -126,45 +119,16 @@ __global__ __launch_bounds__(512, 2) void rows_longk_kernel(RightPass a)
         }
 }
 
-int rp_num_cu()
-{
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-        return v;
-    }();
-    return n;
-}
-
 }  // namespace
 
-// 1 = launched, 0 = shape not covered, < 0 = error.  C[m][n] (+)= alpha * sum_k S[m s_row + k] B[n b_row + k]
-int rows_longk_try(const double *S, int64_t rows, int64_t s_row, const double *B, int N, int64_t b_row, int64_t K, double *C,
-                   int64_t c_row, double alpha, int accumulate, int stream, hipStream_t st)
+// rows_longk_plan (gemm_plan.h) gets its slabs, its bracket and its launch, then the sum of the slabs.  1 = launched, < 0 = error
+int rows_longk_launch(RowsLongkPlan &p, int stream, hipStream_t st)
 {
-    if (rows < 1 || N < 1 || N > RP_BROWS || K < 4096 || (K & 63) || (s_row & 1) || (b_row & 1) || s_row < K || b_row < K) return 0;
-    if (((uintptr_t)S | (uintptr_t)B) & 15) return 0;
-    const int64_t nrb = (rows + 63) / 64;
-    if (nrb > (1 << 20)) return 0;
-    // K ranges: enough workgroups for two per CU, at least 8 stages each
-    const int64_t nst = K >> 6;
-    int64_t nkc = (2 * rp_num_cu() + nrb - 1) / nrb;
-    if (nkc > nst / 8) nkc = nst / 8;
-    if (nkc < 1) nkc = 1;
-    if (nrb * nkc >= (1ll << 30)) return 0;
-    RightPass a{};
-    a.S = S; a.B = B; a.rows = rows; a.s_row = s_row; a.b_row = b_row; a.K = K; a.N = N;
-    a.nrb = (int)nrb; a.nkc = (int)nkc;
-    a.slab = (double *)scratch(stream, SCRATCH_GEMM, (size_t)nrb * nkc * 64 * N * 8 + 64);
-    if (!a.slab) return TTSK_ERR_HIP;
-    ProfBracket prof(st, PROF_CURRENT, 2.0 * rows * (double)N * K, "rows_longk_kernel");
-    int rc = launch(rows_longk_kernel, dim3((unsigned)(nrb * nkc)), dim3(512), (size_t)2 * (64 + RP_BROWS) * 64 * 8, st, a);
-    if (rc == TTSK_OK) {
-        ReduceOut ro{};
-        ro.C[0] = C;
-        rc = launch_r_reduce(st, a.slab, (int)nkc, 64, N, (int)nrb, rows, ro, 1, c_row, 1, alpha, accumulate);
-    }
+    p.a.slab = (double *)scratch(stream, SCRATCH_GEMM, p.scratch_bytes);
+    if (!p.a.slab) return TTSK_ERR_HIP;
+    ProfBracket prof(st, PROF_CURRENT, p.work, "%s", p.name);
+    int rc = launch(rows_longk_kernel, dim3(p.grid), dim3(p.block), p.lds, st, p.a);
+    if (rc == TTSK_OK) rc = launch_r_reduce(st, p.a.slab, p.red);
     return rc == TTSK_OK ? 1 : rc;
 }
 

@@ -12,11 +12,13 @@
 // contiguous in global memory, so that both the global read and the LDS write are
 // conflict free and the MFMA fragment reads (ds_read_b64) hit 64 distinct banks:
 //   "m-fast": tile[k][m], ld = BM+16 (== 16 mod 32)   "k-fast": tile[m][k], ld = 18 (== 2 mod 32)
-// Split-K over (ko,ki) through gridDim.z with fp64 global atomics.
+// Split-K over (ko,ki) through gridDim.z into slabs that splitk_reduce_kernel sums.
+// Which kernel family takes a call, and with what, is decided in gemm_plan.h (gemm_route and the plans); this file holds the
+// entry point, the tile launcher and the split-K reduce.
 #include <cstdlib>
 #include "gemm_kernel.h"
 #include "prof.h"
-#include "skinny.h"
+#include "skinny.h"   // gemm_plan.h and the launchers of its plans
 
 namespace ttsk {
 
@@ -75,129 +77,35 @@ __global__ void fill3_kernel(double *C, int64_t batch, int64_t M, int64_t N, int
     }
 }
 
-struct CopyDesc {
-    int64_t shape[5], ds[5], ss[5];
-    int64_t total;
-};
-__global__ void copy_strided_kernel(double *dst, const double *src, CopyDesc c)
+static int launch_splitk_reduce(const GemmTilePlan &p, hipStream_t st)
 {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < c.total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t t = i, so = 0, dof = 0;
-#pragma unroll
-        for (int a = 4; a >= 0; --a) {
-            int64_t q = t / c.shape[a], r = t - q * c.shape[a];
-            so += r * c.ss[a];
-            dof += r * c.ds[a];
-            t = q;
-        }
-        dst[dof] = src[so];
+    const GemmLaunch &g = p.g;
+    return launch(splitk_reduce_kernel, dim3(p.red_grid), dim3(256), 0, st, g.d, g.partial, g.C, g.splits, p.tiles_m, p.tiles_n,
+                  p.rota);
+}
+
+// gemm_tile_plan gets its split-K slabs, its bracket and its launch, then the sum of the slabs
+static int gemm_tile_launch(GemmTilePlan &p, int stream, hipStream_t st)
+{
+    GemmLaunch &g = p.g;
+    if (p.partial_bytes) {
+        g.partial = (double *)scratch(stream, SCRATCH_GEMM, p.partial_bytes);
+        if (!g.partial) return TTSK_ERR_HIP;
     }
+    int rc;
+    // the tile kernel alone, not the split-K reduce: <waves along m, n, tiles per wave along m, n, layouts>
+    ProfBracket prof(st, PROF_CURRENT, p.work, "gemm_f64_kernel<%d, %d, %d, %d, %s, %s>", p.wm, p.wn, p.tm, p.tn,
+                     p.ak ? "true" : "false", p.bk ? "true" : "false");
+    if (p.ak && p.bk) rc = launch_gemm_layout<true, true>(g, st);
+    else if (p.ak) rc = launch_gemm_layout<true, false>(g, st);
+    else if (p.bk) rc = launch_gemm_layout<false, true>(g, st);
+    else rc = launch_gemm_layout<false, false>(g, st);
+    prof.close();
+    if (rc || !g.partial) return rc;
+    return launch_splitk_reduce(p, st);
 }
 
-__global__ void axpby_kernel(double *y, const double *x, double a, double b, size_t n)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (size_t)gridDim.x * blockDim.x)
-        y[i] = a * x[i] + (b == 0.0 ? 0.0 : b * y[i]);
-}
-
-// dst[i] (+)= sum_b src[b * stride + i]: the sketches of a batch summed into one (TensorSum)
-// (the slices are requested eight at a time and added in order: one load after the other, each waiting for the sum,
-// was 15 us for 32 slices of 6400 numbers -- a handful of workgroups, nothing to hide a round trip behind)
-__global__ __launch_bounds__(256) void sum_slices_kernel(double2 *dst, const double2 *src, int nb, size_t stride2,
-                                                         size_t n2, int accumulate)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (size_t)gridDim.x * blockDim.x) {
-        double2 acc = accumulate ? dst[i] : make_double2(0.0, 0.0);
-        const double2 *p = src + i;
-        int b = 0;
-        for (; b + 8 <= nb; b += 8, p += 8 * stride2) {
-            double2 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[(size_t)u * stride2];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { acc.x += v[u].x; acc.y += v[u].y; }
-        }
-        for (; b < nb; ++b, p += stride2) {
-            const double2 v = *p;
-            acc.x += v.x;
-            acc.y += v.y;
-        }
-        dst[i] = acc;
-    }
-}
-
-// the same for odd lengths / strides or bases that are not 16-byte aligned
-__global__ __launch_bounds__(256) void sum_slices_scalar_kernel(double *dst, const double *src, int nb, size_t stride, size_t n,
-                                                                int accumulate)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        double acc = accumulate ? dst[i] : 0.0;
-        const double *p = src + i;
-        int b = 0;
-        for (; b + 8 <= nb; b += 8, p += 8 * stride) {
-            double v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[(size_t)u * stride];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc += v[u];
-        }
-        for (; b < nb; ++b, p += stride) acc += *p;
-        dst[i] = acc;
-    }
-}
-
-// 512 threads = two waves per SIMD and at most 256 registers each: with __launch_bounds__(256) hipcc parks the
-// accumulators in AGPRs and copies them in and out around every instruction (32 v_accvgpr moves + s_nop per
-// 4 matrix instructions) -- round 1's "49 TF/s ceiling of the 16x16x4 form" was that code, not the pipe.
-__global__ __launch_bounds__(512) void mfma_probe_kernel(double *sink, int iters, double seed)
-{
-    v4d a0 = {0, 0, 0, 0}, a1 = a0, a2 = a0, a3 = a0;
-    double x = seed + threadIdx.x * 1e-3, y = seed - threadIdx.x * 1e-3;
-    for (int i = 0; i < iters; ++i) {
-        a0 = mfma16(x, y, a0);
-        a1 = mfma16(y, x, a1);
-        a2 = mfma16(x, x, a2);
-        a3 = mfma16(y, y, a3);
-    }
-    v4d t = a0 + a1 + a2 + a3;
-    if (t[0] + t[1] + t[2] + t[3] == 12345.678) sink[blockIdx.x] = t[0];
-}
-
-struct GemmPlan {
-    int family, tiles, bm, bn;
-};
-
-static GemmPlan plan_gemm(int64_t M, int64_t N)
-{
-    // Tiles per wave in the skinny families are capped at 4: smaller workgroups leave room
-    // for 3-4 of them per CU, and co-resident workgroups are what hides the load latency of these
-    // short-K products (one wave per SIMD cannot overlap its own loads with its MFMAs).
-    constexpr int cap = 4;
-    GemmPlan p;
-    auto split = [&](int64_t X) {            // tiles per wave so that rows*tiles covers ceil(X/16) evenly
-        const int need = (int)cdiv(X, 16);
-        const int rows = (int)cdiv(need, cap);
-        return (int)cdiv(need, rows);
-    };
-    if (M <= 128 && M <= N) { p.family = 1; p.tiles = split(M); p.bm = 16 * p.tiles; p.bn = 64; }
-    else if (N <= 128) { p.family = 2; p.tiles = split(N); p.bm = 64; p.bn = 16 * p.tiles; }
-    else { p.family = 0; p.tiles = 2; p.bm = 64; p.bn = 64; }
-    return p;
-}
-
-int launch_splitk_reduce(const ttsk_gemm_desc &d, const double *partial, double *C, int splits, int64_t tiles_m,
-                         int64_t tiles_n, int rota, hipStream_t st)
-{
-    const int64_t total = d.batch * tiles_m * tiles_n * 256;
-    int64_t blocks = cdiv(total, 64);
-    if (blocks > 4096) blocks = 4096;
-    return launch(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d, partial, C, splits,
-                  tiles_m, tiles_n, rota);
-}
-
-static bool even(int64_t v) { return (v & 1) == 0; }
+static int launched(int rs) { return rs < 0 ? rs : TTSK_OK; }     // of a plan's launcher: 1 = launched, < 0 = error
 
 }  // namespace ttsk
 
@@ -205,225 +113,64 @@ using namespace ttsk;
 
 extern "C" {
 
+// route (gemm_plan.h gemm_route: which family, with its plan), then scratch and launch
 int ttsk_gemm(const ttsk_gemm_desc *dp, const double *A, const double *B, double *C,
               const double *k_scale, int stream)
 {
     TTSK_STREAM(st, stream);
     TTSK_ARG(dp && A && B && C, "ttsk_gemm: NULL argument");
     ttsk_gemm_desc d = *dp;
-    TTSK_ARG(d.batch >= 0 && d.M >= 0 && d.N >= 0 && d.Ko >= 0 && d.Ki >= 0, "ttsk_gemm: negative size");
-    // every slice of a batch would write the same C (and the tiles of different slices would race): no caller means that
-    TTSK_ARG(d.batch <= 1 || d.c_b != 0, "ttsk_gemm: batch %lld with c_b == 0", (long long)d.batch);
-    if (d.batch == 0 || d.M == 0 || d.N == 0) return TTSK_OK;
-    const int64_t K = d.Ko * d.Ki;
+    const int n_cu = device_num_cu();
+    if (n_cu < 1) return TTSK_ERR_HIP;
+    GemmRoute r;
+    if (const int rc = gemm_route(d, A, B, C, k_scale, n_cu, &r)) {
+        set_error("%s", r.msg);
+        return rc;
+    }
     static int trace = [] { const char *e = getenv("TTSK_GEMM_TRACE"); return e ? atoi(e) : 0; }();
-    if (trace)
+    if (trace && r.kind != GEMM_EMPTY)
         fprintf(stderr, "ttsk_gemm b=%lld M=%lld N=%lld Ko=%lld Ki=%lld | a: b%lld m%lld ko%lld ki%lld | b: b%lld ko%lld ki%lld n%lld | c: b%lld m%lld n%lld acc=%d\n",
                 (long long)d.batch, (long long)d.M, (long long)d.N, (long long)d.Ko, (long long)d.Ki, (long long)d.a_b,
                 (long long)d.a_m, (long long)d.a_ko, (long long)d.a_ki, (long long)d.b_b, (long long)d.b_ko,
                 (long long)d.b_ki, (long long)d.b_n, (long long)d.c_b, (long long)d.c_m, (long long)d.c_n, d.accumulate);
-    if (K == 0) {
-        if (!d.accumulate) {
-            if (int rc = launch(fill3_kernel, dim3(256), dim3(256), 0, st, C, d.batch, d.M, d.N, d.c_b,
-                                d.c_m, d.c_n, 0.0)) return rc;
-        }
-        return TTSK_OK;
-    }
-    if (d.batch == 1 && !k_scale && d.c_n == 1) {
-        // rows of an unfolding against a DRM matrix, both contiguous along a long contracted index (the right-hand products
-        // of a dense sketch with Gaussian matrices): both operands through LDS by LDS-DMA (dense_right_pass.hip)
-        ttsk_gemm_desc n = d;
-        if (n.Ki == 1) { n.Ki = n.Ko; n.Ko = 1; n.a_ki = n.a_ko; n.b_ki = n.b_ko; }
-        else if (n.Ko > 1 && n.a_ko == n.Ki * n.a_ki && n.b_ko == n.Ki * n.b_ki) { n.Ki *= n.Ko; n.Ko = 1; }
-        if (n.Ko == 1 && n.a_ki == 1 && n.b_ki == 1 && n.N <= 48 && n.a_m >= n.Ki && n.b_n >= n.Ki) {
-            const int rs = rows_longk_try(A, n.M, n.a_m, B, (int)n.N, n.b_n, n.Ki, C, n.c_m, n.alpha, n.accumulate, stream, st);
-            if (rs < 0) return rs;
-            if (rs == 1) return TTSK_OK;
-        }
-    }
-    {
-        // the chain shapes (tall-skinny, K <= 128) have their own barrier-free kernels
-        ttsk_gemm_desc n = d;
-        if (n.Ki == 1) { n.Ki = n.Ko; n.Ko = 1; n.a_ki = n.a_ko; n.b_ki = n.b_ko; }
-        else if (n.Ko > 1 && n.a_ko == n.Ki * n.a_ki && n.b_ko == n.Ki * n.b_ki) { n.Ki *= n.Ko; n.Ko = 1; }
-        int rs = skinny_try(n, A, B, C, k_scale, stream, st);
-        if (rs == 0 && !k_scale) rs = small_try_batch(n, 1, &A, &B, &C, stream, st);
-        if (rs < 0) return rs;
-        if (rs == 1) return TTSK_OK;
-    }
-    if (d.batch >= 2 && K >= 32768 && !k_scale && d.c_b != 0) {
-        // a long contraction batched over an index that only one operand carries (the per-slice right products of
-        // dense_sketch.py: P^T X_b for every slice b of the tensor): up to SK_MAXB problems per launch of the long-K
-        // chain kernel instead of the generic tiles (C2's Psi_0 pass: 2.76 -> 2.59 ms)
-        ttsk_gemm_desc n = d;
-        n.batch = 1; n.a_b = n.b_b = n.c_b = 0;
-        if (n.Ki == 1) { n.Ki = n.Ko; n.Ko = 1; n.a_ki = n.a_ko; n.b_ki = n.b_ko; }
-        else if (n.Ko > 1 && n.a_ko == n.Ki * n.a_ki && n.b_ko == n.Ki * n.b_ki) { n.Ki *= n.Ko; n.Ko = 1; }
-        bool done = true;
-        for (int64_t b0 = 0; b0 < d.batch && done; b0 += SK_MAXB) {
+    int rs;
+    switch (r.kind) {
+    case GEMM_EMPTY: return TTSK_OK;
+    case GEMM_K0:
+        if (d.accumulate) return TTSK_OK;
+        return launch(fill3_kernel, dim3(256), dim3(256), 0, st, C, d.batch, d.M, d.N, d.c_b, d.c_m, d.c_n, 0.0);
+    case GEMM_ROWS_LONGK: return launched(rows_longk_launch(r.rl, stream, st));
+    case GEMM_SKINNY_R: return launched(skinny_r_launch(r.sr, stream, st));
+    case GEMM_SKINNY_S: return launched(skinny_s_launch(r.ss, st));
+    case GEMM_SMALL: return launched(small_gemm_launch(r.sm, st));
+    case GEMM_LONGK_BATCH:
+        // up to SK_MAXB slices per launch; the route planned the first group
+        for (int64_t b0 = 0; b0 < d.batch; b0 += SK_MAXB) {
             const int cnt = (int)(d.batch - b0 < SK_MAXB ? d.batch - b0 : SK_MAXB);
             const double *Ap[SK_MAXB], *Bp[SK_MAXB];
             double *Cp[SK_MAXB];
             for (int b = 0; b < cnt; ++b) {
                 Ap[b] = A + (b0 + b) * d.a_b; Bp[b] = B + (b0 + b) * d.b_b; Cp[b] = C + (b0 + b) * d.c_b;
             }
-            const int rs = skinny_try_batch(n, cnt, Ap, Bp, Cp, stream, st);
+            rs = b0 == 0 ? skinny_r_launch(r.sr, stream, st) : skinny_try_batch(r.n, cnt, Ap, Bp, Cp, stream, st);
             if (trace) fprintf(stderr, "  long-K batch slice %lld: rs = %d\n", (long long)b0, rs);
             if (rs < 0) return rs;
             if (rs == 0) {
                 // rejected (a slice's alignment / extent differs from the first ones'): the slices done so far stand, the
-                // rest go through the generic tiles below -- same result in both accumulate modes
+                // rest go through the generic tiles -- same result in both accumulate modes.  No input gets here
+                // (tests/test_gemm_plan.py, the sweep of slice groups); kept as the way out should a plan's rules change.
                 A += b0 * d.a_b; B += b0 * d.b_b; C += b0 * d.c_b;
                 d.batch -= b0;
-                done = false;
+                if (const int rc = gemm_tile_plan(d, A, B, C, k_scale, &r.g); rc < 0) {
+                    set_error("%s", r.g.msg);
+                    return rc;
+                }
+                return gemm_tile_launch(r.g, stream, st);
             }
         }
-        if (done) return TTSK_OK;
+        return TTSK_OK;
+    default: return gemm_tile_launch(r.g, stream, st);
     }
-    const GemmPlan p = plan_gemm(d.M, d.N);
-    const int64_t tiles = d.batch * cdiv(d.M, p.bm) * cdiv(d.N, p.bn);
-    int splits = d.split_k;
-    if (splits <= 0) {
-        splits = 1;
-        if (tiles < 192 && K >= 4 * BK) {
-            int64_t want = cdiv(512, tiles);
-            int64_t maxs = cdiv(K, K >= 32 * BK ? 4 * BK : BK);
-            splits = (int)(want < maxs ? want : maxs);
-            if (splits > 1024) splits = 1024;
-            if (splits < 1) splits = 1;
-        }
-    }
-    TTSK_ARG(d.batch * (int64_t)splits <= 65535, "ttsk_gemm: batch*split_k too large (%lld)",
-             (long long)(d.batch * splits));
-    int64_t kchunk = cdiv(cdiv(K, splits), BK) * BK;
-    splits = (int)cdiv(K, kchunk);
-    double *partial = nullptr;
-    const int64_t tiles_m = cdiv(d.M, p.bm) * (p.bm / 16), tiles_n = cdiv(d.N, p.bn) * (p.bn / 16);
-    if (splits > 1) {
-        partial = (double *)scratch(stream, SCRATCH_GEMM, (size_t)(d.batch * splits * tiles_m * tiles_n * 256) * 8 + 64);
-        if (!partial) return TTSK_ERR_HIP;
-    }
-    // normalise a single contracted index into the inner slot
-    if (d.Ki == 1) { d.Ki = d.Ko; d.Ko = 1; d.a_ki = d.a_ko; d.b_ki = d.b_ko; }
-    if (d.Ko == 1) { d.a_ko = 0; d.b_ko = 0; }
-    if (d.batch == 1) { d.a_b = 0; d.b_b = 0; }
-    // which index is contiguous in memory decides the staging layout; 16-byte loads when the
-    // contiguous index pairs up cleanly (even strides, pairs never straddle ko, aligned base)
-    const bool ak = d.a_m != 1 && d.a_ki == 1;
-    const bool bk = d.b_n != 1 && d.b_ki == 1;
-    const bool k_pairs = d.Ko == 1 || even(d.Ki);
-    int avec = ak ? (k_pairs && even(d.a_m) && even(d.a_ko) && even(d.a_b))
-                  : (d.a_m == 1 && even(d.a_ki) && even(d.a_ko) && even(d.a_b));
-    int bvec = bk ? (k_pairs && even(d.b_n) && even(d.b_ko) && even(d.b_b))
-                  : (d.b_n == 1 && even(d.b_ki) && even(d.b_ko) && even(d.b_b));
-    if (((uintptr_t)A & 15) != 0) avec = 0;
-    if (((uintptr_t)B & 15) != 0) bvec = 0;
-    // 16-byte loads additionally need whole pairs inside the extents
-    if (ak ? (K & 1) : (d.M & 1)) avec = 0;
-    if (bk ? (K & 1) : (d.N & 1)) bvec = 0;
-    // The fast staging path addresses a tile through a buffer resource: 32-bit byte offsets from the
-    // workgroup's first row / column, K offset in a scalar register.
-    const int64_t a_extent = (d.M - 1) * d.a_m + (d.Ko - 1) * d.a_ko + (d.Ki - 1) * d.a_ki + 1;
-    const int64_t b_extent = (d.N - 1) * d.b_n + (d.Ko - 1) * d.b_ko + (d.Ki - 1) * d.b_ki + 1;
-    const int64_t span_a = (int64_t)p.bm * d.a_m + d.Ko * d.a_ko + (d.Ki + BK) * d.a_ki;
-    const int64_t span_b = (int64_t)p.bn * d.b_n + d.Ko * d.b_ko + (d.Ki + BK) * d.b_ki;
-    const int fast_ok = d.a_m >= 0 && d.b_n >= 0 && d.a_ki >= 0 && d.b_ki >= 0 && d.a_ko >= 0 && d.b_ko >= 0 &&
-                        span_a * 8 < (1ll << 31) && span_b * 8 < (1ll << 31);
-    GemmLaunch g{d, A, B, k_scale, C, partial, p.family, p.tiles, splits, avec, bvec, fast_ok, kchunk, p.bm, p.bn,
-                 a_extent, b_extent};
-    int rc;
-    // the tile kernel alone, not the split-K reduce: <waves along m, n, tiles per wave along m, n, layouts>
-    const int wm = p.family == 0 ? 2 : (p.family == 1 ? 1 : 4), wn = p.family == 0 ? 2 : (p.family == 1 ? 4 : 1);
-    const int tm = p.family == 0 ? 2 : (p.family == 1 ? p.tiles : 1), tn = p.family == 0 ? 2 : (p.family == 1 ? 1 : p.tiles);
-    ProfBracket prof(st, PROF_CURRENT, 2.0 * (double)d.batch * (double)d.M * (double)d.N * (double)K,
-                     "gemm_f64_kernel<%d, %d, %d, %d, %s, %s>", wm, wn, tm, tn, ak ? "true" : "false", bk ? "true" : "false");
-    if (ak && bk) rc = launch_gemm_layout<true, true>(g, st);
-    else if (ak) rc = launch_gemm_layout<true, false>(g, st);
-    else if (bk) rc = launch_gemm_layout<false, true>(g, st);
-    else rc = launch_gemm_layout<false, false>(g, st);
-    prof.close();
-    if (rc || !partial) return rc;
-    return launch_splitk_reduce(d, partial, C, splits, tiles_m, tiles_n, p.family == 2 ? 1 : 0, st);
-}
-
-int ttsk_mfma_f64_peak_probe(double *tflops)
-{
-    TTSK_STREAM(st, 0);
-    TTSK_ARG(tflops, "ttsk_mfma_f64_peak_probe: NULL");
-    double *sink = (double *)scratch(0, SCRATCH_GEMM, 1 << 16);
-    if (!sink) return TTSK_ERR_HIP;
-    const int blocks = 256 * 4, iters = 2000;
-    hipEvent_t a, b;
-    TTSK_HIP(hipEventCreate(&a));
-    TTSK_HIP(hipEventCreate(&b));
-    double best = 0;
-    for (int rep = 0; rep < 4; ++rep) {
-        TTSK_HIP(hipEventRecord(a, st));
-        if (int rc = launch(mfma_probe_kernel, dim3(blocks), dim3(512), 0, st, sink, iters, 1.0 + rep)) return rc;
-        TTSK_HIP(hipEventRecord(b, st));
-        TTSK_HIP(hipEventSynchronize(b));
-        float ms = 0;
-        TTSK_HIP(hipEventElapsedTime(&ms, a, b));
-        double fl = (double)blocks * 8 /*waves*/ * iters * 4 /*mfma*/ * 2048.0;
-        double tf = fl / (ms * 1e-3) * 1e-12;
-        if (rep > 0 && tf > best) best = tf;
-    }
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    *tflops = best;
-    return TTSK_OK;
-}
-
-int ttsk_copy_strided(double *dst, const double *src, int ndim, const int64_t *shape,
-                      const int64_t *dst_strides, const int64_t *src_strides, int stream)
-{
-    TTSK_STREAM(st, stream);
-    TTSK_ARG(ndim >= 0 && ndim <= 5, "ttsk_copy_strided: ndim %d > 5", ndim);
-    CopyDesc c;
-    c.total = 1;
-    for (int a = 0; a < 5; ++a) {
-        int src_a = a - (5 - ndim);
-        if (src_a >= 0) {
-            c.shape[a] = shape[src_a];
-            c.ds[a] = dst_strides[src_a];
-            c.ss[a] = src_strides[src_a];
-        } else {
-            c.shape[a] = 1;
-            c.ds[a] = 0;
-            c.ss[a] = 0;
-        }
-        TTSK_ARG(c.shape[a] >= 0, "ttsk_copy_strided: negative extent");
-        c.total *= c.shape[a];
-    }
-    if (c.total == 0) return TTSK_OK;
-    int64_t blocks = cdiv(c.total, 256);
-    if (blocks > 4096) blocks = 4096;
-    return launch(copy_strided_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dst, src, c);
-}
-
-int ttsk_sum_slices(double *dst, const double *src, int nb, size_t stride, size_t n, int accumulate, int stream)
-{
-    TTSK_STREAM(st, stream);
-    TTSK_ARG(dst && src && nb >= 1, "ttsk_sum_slices: bad argument");
-    if (n == 0) return TTSK_OK;
-    if ((n & 1) || (stride & 1) || (((uintptr_t)dst | (uintptr_t)src) & 15)) {
-        size_t blocks = (n + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        return launch(sum_slices_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dst, src, nb, stride, n, accumulate);
-    }
-    size_t blocks = (n / 2 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    return launch(sum_slices_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (double2 *)dst, (const double2 *)src,
-                  nb, stride / 2, n / 2, accumulate);
-}
-
-int ttsk_axpby(double *y, const double *x, double a, double b, size_t n, int stream)
-{
-    TTSK_STREAM(st, stream);
-    if (n == 0) return TTSK_OK;
-    size_t blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    return launch(axpby_kernel, dim3((unsigned)blocks), dim3(256), 0, st, y, x, a, b, n);
 }
 
 }  // extern "C"

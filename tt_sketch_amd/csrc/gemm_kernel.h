@@ -3,6 +3,7 @@
 #include <cstdint>
 #include <type_traits>
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace ttsk {
 
@@ -14,10 +15,7 @@ __device__ long long g_stamps[256];
 #define TTSK_STAMP(i) do { } while (0)
 #endif
 
-constexpr int BK = 32;        // K depth of one staged tile
-constexpr int LDKF = BK + 2;  // "k-fast" LDS layout tile[x][k], ld == 2 (mod 32)
-
-__host__ __device__ constexpr int ldmf(int bx) { return (bx % 32 == 16) ? bx : bx + 16; }  // == 16 (mod 32)
+// BK, LDKF, ldmf: gemm_plan.h
 
 struct KMap {
     int64_t Ko, Ki, s_ko, s_ki;
@@ -383,26 +381,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(ttsk_gemm_desc d, cons
             }
 }
 
-// launcher generated per staging-layout pair in gemm_inst_*.hip
-struct GemmLaunch {
-    ttsk_gemm_desc d;
-    const double *A, *B, *ks;
-    double *C, *partial;
-    int family, tiles;      // tiles: 1..4; family 0: 2x2 waves of 2x2 tiles; 1: 1x4 waves of tiles x 1; 2: 4x1 waves of 1 x tiles
-    int splits, avec, bvec, fast_ok;
-    int64_t kchunk;
-    int bm, bn;
-    int64_t a_extent, b_extent;   // elements from the (per-batch) operand base to its last element + 1
-};
+// launcher generated per staging-layout pair in gemm_inst_*.hip (GemmLaunch: gemm_plan.h)
 template <bool AKF, bool BKF> int launch_gemm_layout(const GemmLaunch &g, hipStream_t st);
 
 template <int WM, int WN, int TMX, int TNX, bool AKF, bool BKF>
 static int launch_one(const GemmLaunch &g, hipStream_t st)
 {
-    constexpr int bm = WM * TMX * 16, bn = WN * TNX * 16;
-    dim3 grid((unsigned)cdiv(g.d.N, bn), (unsigned)cdiv(g.d.M, bm), (unsigned)(g.d.batch * g.splits));
-    const size_t lds = 8 * (size_t)((AKF ? bm * LDKF : BK * ldmf(bm)) + (BKF ? bn * LDKF : BK * ldmf(bn)));
-    return launch(gemm_f64_kernel<WM, WN, TMX, TNX, AKF, BKF>, grid, dim3(256), lds, st, g.d, g.A, g.B, g.C,
+    return launch(gemm_f64_kernel<WM, WN, TMX, TNX, AKF, BKF>, dim3(g.gx, g.gy, g.gz), dim3(256), g.lds, st, g.d, g.A, g.B, g.C,
                   g.ks, g.splits, g.kchunk, g.partial, g.avec, g.bvec, g.fast_ok, g.a_extent, g.b_extent);
 }
 

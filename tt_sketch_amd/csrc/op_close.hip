@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void op_close_batch_kernel(OpCloseBatchArgs
     op_close_body(t.a, (int)blockIdx.x - t.block0, t.ldw, oc_sm);
 }
 
-// out (+)= the jchunks slices of every pair, in the order and the association of sum_slices_kernel (gemm.hip): from out or
+// out (+)= the jchunks slices of every pair, in the order and the association of sum_slices_kernel (vector_ops.hip): from out or
 // from zero, the slices added one after the other in ascending order, eight loads in flight.
 __global__ __launch_bounds__(256) void op_close_batch_sum_kernel(OpCloseBatchArgs g)
 {

@@ -22,29 +22,7 @@ namespace ttsk {
 #define TTSK_S_M16 1
 #endif
 
-struct SkinnyS {
-    const double *W[SK_MAXB], *S[SK_MAXB];
-    double *C[SK_MAXB];
-    int nb, wpp;        // problems, workgroups per problem: workgroup x serves problem x / wpp
-    int64_t w_k, w_m;   // W[k][m]
-    int64_t s_j, s_k;   // S[j][k]
-    // Two-level streamed index j = u V + v (u < U at stride s_u, v < V at stride s_j; U = 1: plain).
-    // A 16-row block is then a (16 >> tvl) (u) x (1 << tvl) (v) tile.  tvl = 4 (16 consecutive v of
-    // one u: the right chain's GEMM1 reads X[p'', k, :] for 16 p'' of one k and writes whole 128-byte
-    // lines of T[q][k][p'']) measured best; 4 x 4 and 2 x 8 tiles read longer runs but write
-    // 32- / 64-byte pieces and were 5-10 % slower end to end.
-    int64_t s_u;
-    int U, V, nbv, tvl;
-    int64_t c_m, c_j;   // C[m][j]
-    int64_t c_u;        // two-level streamed index: C[m][u][v] at m c_m + u c_u + v c_j
-    int64_t J;
-    int P, K, groups;
-    int64_t s_extent, w_extent, c_extent;   // elements addressable from each base (all < 2^29)
-    double alpha;
-    int accumulate;
-    int big;            // 1: 64-bit origins per row block / k-block / output tile (operands beyond 4 GB)
-    long long *stamps;   // diagnostics (TTSK_SK_STAMPS): s_memtime at phase boundaries, 8 per workgroup
-};
+// SkinnyS, the arguments of skinny_s_kernel: gemm_plan.h
 
 #define SK_STAMP(i) do { if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #define SK_STAMP_RT(i) do { if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -423,26 +401,7 @@ __global__ __launch_bounds__(512) void skinny_s_kernel(SkinnyS a)
 #define TTSK_R_DEPTH 4     // kappa-blocks in flight per wave (8 measured no faster, 230 VGPRs)
 #endif
 
-struct SkinnyR {
-    const double *A[SK_MAXB], *B[SK_MAXB];
-    double *slab;       // [problem][chunk][m][n]
-    int nb, chunks;     // workgroup x serves chunk x % chunks of (problem, row tile) x / chunks
-    int64_t a_ko, a_ki, b_ko, b_ki;
-    int64_t Ki, K, chunk;
-    int64_t a_extent, b_extent;
-    int M, N;           // rows of one row tile (<= 128), columns (<= 128)
-    // A's row dimension may be longer than 128: m_tiles tiles of M rows, Mtot rows in all (the dense
-    // unfoldings: 20 x K times K x 4096 ... ).  With a single-level kappa (`rebase`) every workgroup
-    // addresses its operands from its own chunk / tile origin, so operands beyond 4 GB are fine.
-    int m_tiles, rebase;
-    int64_t Mtot;
-    // An operand whose rows are not contiguous, or not pairable (odd extent / stride, unaligned base),
-    // is "generic": plain 16-row tiles, one 8-byte load per tile and lane at row stride a_m / b_n,
-    // each tile through its own descriptor (the rows of a k-contiguous unfolding are 128 MB apart).
-    int a_gen, b_gen;
-    int64_t a_m, b_n;
-    long long *stamps;
-};
+// SkinnyR, the arguments of skinny_r_kernel: gemm_plan.h
 
 __device__ __forceinline__ void st16(double *p, double x, double y)
 {
@@ -672,9 +631,7 @@ __device__ __forceinline__ void skinny_r_wave(const SkinnyR &a, const int row0, 
     else skinny_r_wave_impl<PA, SA, PB, SB, D, 0, NSUB>(a, row0, col0, sub);
 }
 
-// outputs of at most SKR_KSPLIT_TILES tiles: kappa split over the 8 waves instead of the tiles
-constexpr int SKR_KSPLIT_TILES = 12;
-
+// (outputs of at most SKR_KSPLIT_TILES tiles, gemm_plan.h: kappa split over the 8 waves instead of the tiles)
 // 8 waves over the (<= 8) x (<= 8) tiles of the output: 2 row halves x 4 column strips, or -- when
 // there are at most 4 column tiles -- 4 row quarters x 2 column strips, which keeps all waves busy
 // and needs 2 instead of 3 loads per 4 tiles on the narrow shapes (left chain: 7 x 4 tiles).
@@ -726,25 +683,25 @@ __global__ __launch_bounds__(512) void skinny_r_kernel(SkinnyR a)
     }
 }
 
-// sum of the per-chunk partial results of the long-K kernel and of the fused chain step (skinny.hip)
-struct ReduceOut { double *C[SK_MAXB]; };
-// out[m, n] (+)= alpha sum_c slab[c][m][n] for nprob x m_tiles (problem, row tile) blocks of slabs behind one another
-int launch_r_reduce(hipStream_t st, const double *slab, int chunks, int M, int N, int m_tiles, int64_t Mtot, const ReduceOut &ro,
-                    int nprob, int64_t c_m, int64_t c_n, double alpha, int accumulate);
+// sum of the per-chunk partial results of the long-K kernels and of the fused chain step (skinny.hip): the kernel, the grid
+// and the block are r_reduce_plan's (gemm_plan.h)
+int launch_r_reduce(hipStream_t st, const double *slab, const RReduceArgs &r);
 
-// 1 = launched, 0 = shape not covered (caller falls through to the generic kernel), < 0 = error
-int skinny_try(const ttsk_gemm_desc &d, const double *A, const double *B, double *C, const double *k_scale,
-               int stream, hipStream_t st);
-// small products (small.hip): nb pointer triples, or one triple with a uniformly strided d.batch; small_batch_covers: whether
-// small_try_batch launches that shape (its answer depends on the descriptor and nb alone)
-bool small_batch_covers(const ttsk_gemm_desc &d, int nb);
+// A plan of gemm_plan.h gets its scratch, its bracket and its launch (skinny.hip, small.hip, dense_right_pass.hip).  1 = launched, < 0 = error
+int skinny_r_launch(SkinnyRPlan &p, int stream, hipStream_t st);
+int skinny_s_launch(SkinnySPlan &p, hipStream_t st);
+int small_gemm_launch(const SmallGemmPlan &p, hipStream_t st);
+int rows_longk_launch(RowsLongkPlan &p, int stream, hipStream_t st);        // dense_right_pass.hip
+// small products (small.hip): nb pointer triples, or one triple with a uniformly strided d.batch, where small_gemm_plan covers
+// the shape.  1 = launched, 0 = shape not covered, < 0 = error
 int small_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, const double *const *B, double *const *C,
                     int stream, hipStream_t st);
 // the same product for each of `count` problems: the batched chain kernel (skinny_try_batch) where it covers the shape, else
 // the batched small kernel, else one ttsk_gemm per problem (small.hip).  TTSK_OK or < 0.
 int gemm_each(const ttsk_gemm_desc &d, int count, const double *const *A, const double *const *B, double *const *C, int stream,
               hipStream_t st);
-// the same product for nb <= SK_MAXB problems of one shape (the tensors of a batch) in one launch
+// the same product for nb <= SK_MAXB problems of one shape (the tensors of a batch) in one launch: skinny_r_plan, then
+// skinny_s_plan.  1 = launched, 0 = shape not covered, < 0 = error
 int skinny_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, const double *const *B,
                      double *const *C, int stream, hipStream_t st);
 

@@ -15,16 +15,7 @@
 
 namespace ttsk {
 
-struct SmallG {
-    const double *A[SK_MAXB], *B[SK_MAXB];
-    double *C[SK_MAXB];
-    int nb, M, N, K, tiles_m, tiles_n;   // tiles_n counts 32-column tiles
-    int64_t a_m, a_k, b_k, b_n, c_m, c_n;
-    int64_t a_extent, b_extent, c_extent;
-    double alpha;
-    int accumulate;
-};
-
+// SmallG, the kernel's arguments: gemm_plan.h
 constexpr int SG_D = SMALL_DEPTH;
 
 __global__ __launch_bounds__(512) void small_gemm_kernel(SmallG a)
@@ -122,60 +113,19 @@ __global__ __launch_bounds__(512) void small_gemm_kernel(SmallG a)
         for (int t = 0; t < 4; ++t) st8(rc, off[q][t], acc[q][t]);
 }
 
-// elements from each operand's base to its last element + 1 (A, B, C)
-static void small_extents(const ttsk_gemm_desc &d, int64_t e[3])
+int small_gemm_launch(const SmallGemmPlan &p, hipStream_t st)
 {
-    e[0] = (d.M - 1) * d.a_m + (d.Ki - 1) * d.a_ki + 1;
-    e[1] = (d.N - 1) * d.b_n + (d.Ki - 1) * d.b_ki + 1;
-    e[2] = (d.M - 1) * d.c_m + (d.N - 1) * d.c_n + 1;
-}
-
-// d: single contracted index (Ko == 1); nb pointer triples, or one triple with a uniformly strided d.batch
-bool small_batch_covers(const ttsk_gemm_desc &d, int nb)
-{
-    if (d.Ko != 1) return false;
-    const int64_t K = d.Ki;
-    int64_t count = nb;
-    if (d.batch > 1) {
-        if (nb != 1) return false;
-        count = d.batch;
-    }
-    if (count < 1 || count > SK_MAXB) return false;
-    if (K < 1 || K > 1024 || d.M > 512 || d.N > 512) return false;
-    if (2.0 * d.M * d.N * K > 48e6) return false;        // beyond a few MFLOP the tiled kernels win
-    if (d.a_m < 0 || d.a_ki < 0 || d.b_ki < 0 || d.b_n < 0 || d.c_m < 0 || d.c_n < 0) return false;
-    if (d.batch > 1 && (d.a_b < 0 || d.b_b < 0 || d.c_b < 0)) return false;
-    int64_t e[3];
-    small_extents(d, e);
-    return (e[0] + 64 * d.a_ki) * 8 < (1ll << 32) - 64 && (e[1] + 64 * d.b_ki) * 8 < (1ll << 32) - 64 && e[2] * 8 < (1ll << 32) - 64;
+    ProfBracket prof(st, PROF_CURRENT, p.work, "%s", p.name);
+    const int rc = launch(small_gemm_kernel, dim3(p.grid), dim3(p.block), 0, st, p.g);
+    return rc == TTSK_OK ? 1 : rc;
 }
 
 int small_try_batch(const ttsk_gemm_desc &d, int nb, const double *const *A, const double *const *B, double *const *C,
                     int stream, hipStream_t st)
 {
     (void)stream;
-    if (!small_batch_covers(d, nb)) return 0;
-    const int64_t K = d.Ki, count = d.batch > 1 ? d.batch : nb;
-    SmallG g{};
-    g.nb = (int)count;
-    for (int b = 0; b < count; ++b) {
-        g.A[b] = d.batch > 1 ? A[0] + b * d.a_b : A[b];
-        g.B[b] = d.batch > 1 ? B[0] + b * d.b_b : B[b];
-        g.C[b] = d.batch > 1 ? C[0] + b * d.c_b : C[b];
-    }
-    g.M = (int)d.M; g.N = (int)d.N; g.K = (int)K;
-    g.tiles_m = (int)cdiv(d.M, 16);
-    g.tiles_n = (int)cdiv(d.N, 32);
-    g.a_m = d.a_m; g.a_k = d.a_ki; g.b_k = d.b_ki; g.b_n = d.b_n; g.c_m = d.c_m; g.c_n = d.c_n;
-    int64_t e[3];
-    small_extents(d, e);
-    g.a_extent = e[0]; g.b_extent = e[1]; g.c_extent = e[2];
-    g.alpha = d.alpha;
-    g.accumulate = d.accumulate;
-    ProfBracket prof(st, PROF_CURRENT, 2.0 * count * (double)d.M * (double)d.N * (double)K, "small_gemm_kernel");
-    const int ksplit = K >= 512 ? 8 : (K >= 256 ? 4 : (K >= 128 ? 2 : 1));
-    const int rc = launch(small_gemm_kernel, dim3((unsigned)(count * g.tiles_m * g.tiles_n)), dim3(64 * ksplit), 0, st, g);
-    return rc == TTSK_OK ? 1 : rc;
+    SmallGemmPlan p;
+    return small_gemm_plan(d, nb, A, B, C, &p) ? small_gemm_launch(p, st) : 0;
 }
 
 int gemm_each(const ttsk_gemm_desc &d, int count, const double *const *A, const double *const *B, double *const *C, int stream,

@@ -16,17 +16,6 @@ static int launch_ss(const StreamSmall &a, int nf, int str, int unr, size_t lds,
     return 1;
 }
 
-static int ss_num_cu()
-{
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-        return v;
-    }();
-    return n;
-}
-
 int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st)
 {
     (void)stream;
@@ -60,7 +49,9 @@ int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st)
     a.accumulate = c.accumulate;
     a.AP = 16 * nf + 4 * str;
     const int ntiles = (c.J + 15) / 16;
-    int wpp = ss_num_cu() / (c.nb * nac) > 0 ? ss_num_cu() / (c.nb * nac) : 1;
+    const int n_cu = device_num_cu();
+    if (n_cu < 1) return TTSK_ERR_HIP;
+    int wpp = n_cu / (c.nb * nac) > 0 ? n_cu / (c.nb * nac) : 1;
     if (wpp > (ntiles + 7) / 8) wpp = (ntiles + 7) / 8;
     a.wpp = wpp;
     a.s_extent = (int64_t)(c.J - 1) * c.s_j + c.K1;
@@ -103,7 +94,8 @@ int stream_small_sum_try(const StreamSmallSumArgs &c, int stream, hipStream_t st
     const int pad25 = (kb + 24) / 25 * 25, pad5 = (kb + 4) / 5 * 5;
     const int unr = pad25 <= pad5 + 1 ? 25 : 5;
     const int KB1 = unr == 25 ? pad25 : pad5;
-    const int ntiles = (c.J + 15) / 16, groups = (ntiles + 7) / 8, cus = ss_num_cu();
+    const int ntiles = (c.J + 15) / 16, groups = (ntiles + 7) / 8, cus = device_num_cu();
+    if (cus < 1) return TTSK_ERR_HIP;
     // column chunks: at least two (two W images of <= 6144 doubles), as many as fill the chip in one round
     int nac = 0, nf = 0, str = 0, need = 0;
     auto plan = [&](int t, int &nf_, int &str_, int &need_) {
