@@ -162,6 +162,21 @@ int ttsk_chain_step_sum(int nb, int n, int K1, int A, int A2, int J, const doubl
                         const double *const *X, int64_t x_j, int64_t x_k, int64_t x_c, int64_t x_extent,
                         const double *E, double *T, int64_t t_b, int64_t t_ld, int64_t t_extent,
                         double *const *Out, int stream);
+/* The Psi products of the one-call TT sketch on their own kernels (csrc/stream_small.h; tensor_train_sketch.py:28-34:
+ * Psi_mu = T_mu R_mu), reached directly:
+ *   ttsk_psi_stream:      C_b[j, a] (+)= sum_c S_b[j, c] W_b[c, a]          for nb <= 32 problems of one shape
+ *   ttsk_psi_stream_sum:  C[j, a]   (+)= sum_b sum_c S_b[j, c] W_b[c, a]    nb >= 2 terms, term b at S + b * s_b, W + b * w_b
+ * S_b (J x K1, row stride s_j), W_b (K1 x A, row stride w_c), C (J x A, row stride c_j), columns contiguous, all 8-byte
+ * aligned; accumulate != 0 adds to C.  The kernels stream J >= 1024 rows; A from 9 (17 for the sum) as far as the column
+ * chunks and the LDS reach.  TTSK_ERR_UNSUPPORTED outside the cover (csrc/psi_plan.h), nothing is written then.
+ * WHAT THE CALLER GUARANTEES: a row of S is read on to whole runs of k-blocks -- the elements S_b[j][K1 .. 4 KB1) behind
+ * it, which are the row's padding, the rows after it and, for the sum, the gap between two terms and the head of the
+ * next term -- and multiplied by exact zeros.  Every such element that lies inside the operand (before S_b[J-1][K1]; for
+ * the sum before S_{nb-1}[J-1][K1]) must be FINITE; what lies behind that is never read. */
+int ttsk_psi_stream(int nb, int J, int K1, int A, const double *const *S, int64_t s_j, const double *const *W,
+                    int64_t w_c, double *const *C, int64_t c_j, int accumulate, int stream);
+int ttsk_psi_stream_sum(int nb, int J, int K1, int A, const double *S, int64_t s_j, int64_t s_b, const double *W,
+                        int64_t w_c, int64_t w_b, double *C, int64_t c_j, int accumulate, int stream);
 /* A DRM core E (A, n, A2) is the same for every sketch it takes part in; ttsk_chain_step's kernel reads each slice
  * E[:, k, :] into LDS in one fixed permutation.  ttsk_drm_pack stores that permutation once (csrc/chain_pack.hip): an
  * image of n * eunits * 16 bytes -- at rank 100 as large as the core, so a packed core takes about twice the device

@@ -94,6 +94,8 @@ ENTRY_POINTS = {
     "ttsk_chain_step": Entry(_CHAIN + [POINTER(P), POINTER(P), I], QUEUE),
     "ttsk_chain_step_wide": Entry(_CHAIN + [POINTER(P), POINTER(P), I], QUEUE),
     "ttsk_chain_step_sum": Entry(_CHAIN + [P, I64, I64, I64, POINTER(P), I], QUEUE),
+    "ttsk_psi_stream": Entry([I, I, I, I, POINTER(P), I64, POINTER(P), I64, POINTER(P), I64, I, I], QUEUE),
+    "ttsk_psi_stream_sum": Entry([I, I, I, I, P, I64, I64, P, I64, I64, P, I64, I, I], QUEUE),
     "ttsk_drm_pack": Entry([P, I, I, I, I], DRAIN_LAST),
     "ttsk_drm_unpack": Entry([P]),
     "ttsk_dense_left_pass": Entry([P, I64, I64, I64, I64, I64, I, P, P, P, P, P, P, P, P, I], QUEUE),

@@ -9,23 +9,31 @@
 // mfma(A = S fragment, B = W fragment) a result register holds 16 consecutive a of one row: 128-byte stores.
 // No barrier after W is staged.  The older skinny_s_kernel (skinny.h) covers the same product for every
 // stride pattern; this one takes the contiguous case the TT sketch produces.
+//
+// WHAT IS READ OF S BEHIND COLUMN K1.  Neither kernel masks k: a wave reads, of every row j of its tile, the 4 KB1
+// elements S[j s_j + k], k = 0 .. 4 KB1 - 1 (KB1 = the k-blocks padded to whole runs, psi_plan.h: up to 99 elements
+// behind K1), and the elements with k >= K1 meet the zero rows of the W image (W is loaded masked: rows >= K1 and columns
+// >= the chunk's width are exact zeros whatever memory holds).  0 * x is 0 only for finite x, so the caller guarantees:
+//   every element S[j s_j + k], j < J, K1 <= k < 4 KB1, that lies inside the descriptor is FINITE.
+// stream_small_kernel bounds each problem with s_extent = (J - 1) s_j + K1: inside are the row's padding (s_j > K1) and the
+// rows after it -- for T interleaved over the terms another term's columns; behind the last row everything reads 0.
+// stream_small_sum_kernel has ONE descriptor over all terms, s_extent = (nb - 1) s_b + (J - 1) s_j + K1: inside are also,
+// behind the last row of every term but the last, the gap between two terms (s_b > J s_j) and the head of the next term.
+// Rows >= J of a ragged last tile and the look-ahead behind a wave's last tile / the last term are read too where they are
+// inside the descriptor, but never multiplied into a stored element.
+// The driver (tt_fused.hip) hands over chain matrices T it has just written, all finite with its input -- except one
+// double: the terms of a sum lie even(lt n s) apart, and where lt n s is odd the pad double behind a term is written by no
+// chain step; the scratch slot is reused and never cleared, so it held whatever the last call left there.  It is reached
+// (K1 = s odd never fills its k-blocks; the last row is visited when the left rank slice ends at lt) on the route c.sum &&
+// !t_inter[mu], s > 48, l n >= 1024, and a NaN or Inf there made that whole row of Psi NaN.  psi_omega now zeroes the pad
+// doubles of a mode before this kernel's launch when lt n s is odd (one memset node, nothing where the size is even: the
+// k-loop is unchanged).  Called directly (ttsk_psi_stream_sum) with a NaN in the gap the row IS NaN: tests/
+// test_gpu_psi_edges.py pins that as the documented contract.
 #pragma once
 #include "skinny.h"
+#include "psi_plan.h"
 
 namespace ttsk {
-
-struct StreamSmall {
-    const double *S[SK_MAXB];
-    const double *W[SK_MAXB];
-    double *C[SK_MAXB];
-    int nb, wpp;                 // problems, row-tile groups per problem
-    int nac, ac;                 // column chunks of A (one workgroup each: disjoint outputs), columns per chunk
-    int J, K1, A;
-    int64_t s_j, w_c, c_j;       // row strides (elements): S rows, W rows, C rows; columns contiguous
-    int64_t s_extent, c_extent;
-    int AP;
-    int accumulate;
-};
 
 template <int NF, int STR, int D, int UNR = 5 * D>
 __global__ __launch_bounds__(512) void stream_small_kernel(StreamSmall a)
@@ -152,18 +160,6 @@ __global__ __launch_bounds__(512) void stream_small_kernel(StreamSmall a)
 // operands are equally spaced in the driver's workspace: one descriptor, a term stride), the W image of term b + 1
 // is fetched into registers before the k-loop of term b and written to the other LDS buffer after it (one barrier
 // per term).  Column chunks (>= 2: two W images must fit) of a row group share an XCD, so S is read from HBM once.
-struct StreamSmallSum {
-    const double *S, *W;         // term 0; term b at + b * s_b / + b * w_b
-    double *C;
-    int nb, groups;              // terms, row-tile groups (8 tiles each)
-    int nac, ac;
-    int J, K1, A;
-    int64_t s_j, w_c, c_j, s_b, w_b;
-    int64_t s_extent, w_extent, c_extent;
-    int AP, xcd_map;
-    int accumulate;
-};
-
 template <int NF, int STR, int D, int UNR = 5 * D>
 __global__ __launch_bounds__(512) void stream_small_sum_kernel(StreamSmallSum a)
 {
@@ -287,34 +283,8 @@ __global__ __launch_bounds__(512) void stream_small_sum_kernel(StreamSmallSum a)
     }
 }
 
-// C (J x A) (+)= sum_b S_b W_b, the nb terms equally spaced: 1 = launched, 0 = shape not covered, < 0 = error
-struct StreamSmallSumArgs {
-    int nb, J, K1, A;
-    const double *S;             // term 0 (J x K1, row stride s_j); term b at S + b * s_b
-    int64_t s_j, s_b;
-    const double *W;             // term 0 (K1 x A, row stride w_c); term b at W + b * w_b
-    int64_t w_c, w_b;
-    double *C;
-    int64_t c_j;
-    int accumulate;
-};
+// The launchers (stream_small.hip) carry out the plans of psi_plan.h: 1 = launched, 0 = shape not covered, < 0 = error
 int stream_small_sum_try(const StreamSmallSumArgs &c, int stream, hipStream_t st);
-
-// 1 = launched, 0 = shape not covered, < 0 = error
-struct StreamSmallArgs {
-    int nb, J, K1, A;
-    const double *const *S;      // nb operands (J x K1), row stride s_j, columns contiguous
-    int64_t s_j;
-    const double *const *W;      // nb small operands (K1 x A), row stride w_c
-    int64_t w_c;
-    double *const *C;            // nb results (J x A), row stride c_j
-    int64_t c_j;
-    int accumulate;
-};
 int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st);
-
-// the fewest equal chunks (<= max_chunks, SK_MAXB) of whole k-blocks into which a contraction of length K splits so that
-// a chunk's W image (A columns) fits the kernel's LDS in one column chunk: the problems of one launch; 0 = none
-int stream_small_chunks(int64_t K, int64_t A, int max_chunks);
 
 }  // namespace ttsk

@@ -394,7 +394,14 @@ static int psi_omega(const Ctx &c, int mu, int q, bool do_psi, bool do_omega)
     } else {
         const int64_t l = c.lw(mu - 1), ldt = c.t_ld(mu);
         if (c.sum && !c.t_inter[mu]) {
-            // Psi_mu of the sum in ONE launch: every wave keeps its tile of the output over all terms (stream_small.h)
+            // Psi_mu of the sum in ONE launch: every wave keeps its tile of the output over all terms (stream_small.h).
+            // One descriptor spans all terms, and the kernel reads the last row of a term on to whole k-blocks against
+            // zero rows of R: where lt n s is odd that is the pad double of even() between two terms, which no chain
+            // step writes and which holds whatever the scratch slot held before -- it must be finite (stream_small.h:
+            // the caller's guarantee), so it is zeroed here, on the Psi stream.  Even sizes (no pad) queue nothing.
+            const size_t t_len = (size_t)c.lt[mu] * nn * sp;
+            if (c.szT[mu] != t_len)
+                TTSK_HIP(hipMemset2DAsync(c.Tp0(0, mu) + t_len, c.szT[mu] * 8, 0, 8, (size_t)nb, stq));
             const StreamSmallSumArgs sa{nb, 0 /* J: psi_stream */, (int)sp, (int)r, c.Tslice(0, mu), ldt, (int64_t)c.szT[mu],
                                         c.Rslice(0, jr), ldr, (int64_t)c.szR[jr], c.out + c.psi_at[mu], r, c.accumulate};
             CK(psi_stream(stream_small_sum_try, sa, l * nn, q, stq));
