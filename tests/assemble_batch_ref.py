@@ -54,16 +54,14 @@ from collections import namedtuple
 import numpy as np
 
 from tests import solve_ref as sr
+from tests.edge_kit import C_BOUND, SENT, SENT_F, assert_guards, assert_untouched  # noqa: F401
 
 LD, EPS = sr.LD, sr.EPS
-C_BOUND = 2.0
 MARGIN = 32.0                # the one rule of tests/test_gpu_solve_edges.py
 REFINE_MARGIN = 8.0
 KAPPA, KAPPA_REFINE, KAPPA_ILL = 10, 100, 10 ** 6
 INT_KAPPA = 4                # integer pass: the singular values of D S are 1/2, 1, 2
 PRE = POST = 16
-SENT = np.float64(-1.0 / 3.0).view(np.uint64)
-SENT_F = np.float64(-1.0 / 3.0)
 TM, TILES_PER_WG, MAXG, COVER_MIN, COVER_MAX = 32, 16, 16, 56, 112      # the cover test holds them against the header
 CHOL_GATE = 1.0 / 300.0
 POISON_SCALE = 2.0 ** 300
@@ -460,12 +458,7 @@ def float64_result(c, v, mode, refine=True):
 
 def check_guards(c, outs, what=""):
     for name, img in outs.items():
-        keep = np.ones(img.size, dtype=bool)
-        for b in range(c.count):
-            o, sz = place(c, name, b)
-            keep[o:o + sz] = False
-        bad = np.flatnonzero(img.view(np.uint64)[keep] != SENT)
-        assert bad.size == 0, "%s %s: %d guard words of %s overwritten" % (c.id, what, bad.size, name)
+        assert_guards(img, [(place(c, name, b)[0], (place(c, name, b)[1],), (1,)) for b in range(c.count)], "%s %s %s" % (c.id, what, name))
 
 
 def _accept(what, got, ref, lapack, kappa, worst, key, turn=False):
@@ -552,8 +545,7 @@ def check_results(c, v, outs, mode, what=""):
 
 
 def check_untouched(outs, what):
-    for name, img in outs.items():
-        assert np.all(img.view(np.uint64) == SENT), "%s: %s was written" % (what, name)
+    assert_untouched(outs, what)
 
 
 def gaussian_mode(c):

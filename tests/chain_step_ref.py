@@ -24,7 +24,7 @@ Integer pass: W, X, E hold integers in [-2, 2]; every partial sum is below 4 K1 
 in any order, slab reduce included: Out and T must EQUAL the int64 einsum (signed zeros are not told apart).
 Gaussian pass: standard normal operands, truth in np.longdouble,
     |T - ref|   <= C (K1 + 2) 2^-53 (|W|^T |X|)_akj             |Out - ref| <= C (K1 + A n + 4) 2^-53 (|W|^T |X| . |E|)_jb
-with C = 2 (the C_BOUND of tests/test_gpu_gemm_families.py): any order of the K1 and A n products, fused or not, cut into
+with C = 2 (C_BOUND, by the argument of tests/test_gpu_gemm_families.py): any order of the K1 and A n products, fused or not, cut into
 chunks and reduced or not, is within that bound up to second-order terms.  (The two magnitude products are formed in
 float64: they are sums of non-negative terms, right to a few 2^-53 of themselves, which moves the bound by less than
 1e-13 of itself.)  Then the Frobenius ratio against 1e-12."""
@@ -32,14 +32,12 @@ from collections import namedtuple
 
 import numpy as np
 
-C_BOUND = 2.0
+from tests.edge_kit import C_BOUND, LD, PAD, SENT, assert_guards, assert_untouched, bounded, exact, sentinel_buffer, strided  # noqa: F401
+
 PRE = POST = 64
-PAD = 1e300
-SENT = np.float64(-1.0 / 3.0).view(np.uint64)
 FROB = 1e-12
 CW = (16, 24, 32, 40, 48, 56, 64)        # columns of the wide kernel's chunk structures (chain_plan.h CW_NQ, CW_SQ); the cover test compares
 KINDS = {"fused": "ttsk_chain_step", "wide": "ttsk_chain_step_wide", "sum": "ttsk_chain_step_sum"}
-LD = np.longdouble
 
 Case = namedtuple("Case", "id kind nb n K1 A A2 J opts")
 
@@ -432,10 +430,6 @@ def truth(c, vals, integer):
                 Out_tol=[x[5] for x in r])
 
 
-def _strided(buf, off, shape, strides):
-    return np.lib.stride_tricks.as_strided(buf[off:], shape=shape, strides=tuple(8 * s for s in strides))
-
-
 def operands(c, layout, vals):
     """host images of the device buffers, guards included: ([W_b], [X_b], E) and the element offset of every base"""
     g = geometry(c, layout)
@@ -443,11 +437,11 @@ def operands(c, layout, vals):
     hW, hX, offX = [], [], []
     for b in range(c.nb):
         w = np.full(PRE + c.K1 * g["w_c"] + POST, PAD)
-        _strided(w, PRE, (c.K1, c.A), (g["w_c"], 1))[...] = W[b]
+        strided(w, PRE, (c.K1, c.A), (g["w_c"], 1))[...] = W[b]
         hW.append(w)
         off = PRE + (g["x_off"] if b == c.nb - 1 else 0)
         x = np.full(off + g["x_extent"] + POST, PAD)
-        _strided(x, off, (c.J, c.n, c.K1), (g["x_j"], g["x_k"], g["x_c"]))[...] = X[b]
+        strided(x, off, (c.J, c.n, c.K1), (g["x_j"], g["x_k"], g["x_c"]))[...] = X[b]
         hX.append(x)
         offX.append(off)
     e = np.full(PRE + g["e_off"] + E.size + POST, PAD)
@@ -458,7 +452,7 @@ def operands(c, layout, vals):
 def sentinels(c, layout, wt):
     """host images of Out_b and T: every element the sentinel.  T: None, nb buffers (fused, wide) or one (stacked terms)"""
     g = geometry(c, layout, wt)
-    new = lambda m: np.full(PRE + m + POST, SENT, dtype=np.uint64).view(np.float64)
+    new = lambda m: sentinel_buffer(m, PRE, POST)
     out = [new(c.J * c.A2) for _ in range(c.nb)]
     if not wt:
         return out, None
@@ -468,27 +462,17 @@ def sentinels(c, layout, wt):
 def t_views(c, layout, wt, bufs):
     """T_b (A, n, J) of every tensor as a view of the buffers"""
     if c.kind != "sum":
-        return [_strided(t, PRE, (c.A, c.n, c.J), (c.n * c.J, c.J, 1)) for t in bufs]
+        return [strided(t, PRE, (c.A, c.n, c.J), (c.n * c.J, c.J, 1)) for t in bufs]
     g = geometry(c, layout, wt)
-    return [_strided(bufs[0], PRE + b * g["t_b"], (c.A, c.n, c.J), (c.n * g["t_ld"], g["t_ld"], 1)) for b in range(c.nb)]
+    return [strided(bufs[0], PRE + b * g["t_b"], (c.A, c.n, c.J), (c.n * g["t_ld"], g["t_ld"], 1)) for b in range(c.nb)]
 
 
 # ------------------------------------------------------------------------------------------------ the checks
-def _inside_mask(size, views):
-    idx = np.arange(size, dtype=np.int64)
-    mark = np.zeros(size, dtype=bool)
-    for off, shape, strides in views:
-        mark[_strided(idx, off, shape, strides).reshape(-1)] = True
-    return mark
-
-
 def check_guards(c, layout, wt, out, tb, what):
     """every element of the Out and T buffers outside the results still holds the sentinel"""
     g = geometry(c, layout, wt)
     for b, o in enumerate(out):
-        m = _inside_mask(o.size, [(PRE, (c.J * c.A2,), (1,))])
-        bad = np.flatnonzero(~m & (o.view(np.uint64) != SENT))
-        assert bad.size == 0, "%s: %d guard elements of Out[%d] overwritten, first at buffer index %s" % (what, bad.size, b, bad[:8].tolist())
+        assert_guards(o, [(PRE, (c.J * c.A2,), (1,))], "%s Out[%d]" % (what, b))
     if tb is None:
         return
     if c.kind == "sum":
@@ -496,36 +480,13 @@ def check_guards(c, layout, wt, out, tb, what):
     else:
         views = [[(PRE, (c.A * c.n * c.J,), (1,))] for _ in tb]
     for b, (t, v) in enumerate(zip(tb, views)):
-        bad = np.flatnonzero(~_inside_mask(t.size, v) & (t.view(np.uint64) != SENT))
-        assert bad.size == 0, "%s: %d guard / padding elements of T[%d] overwritten, first at buffer index %s" % (what, bad.size, b, bad[:8].tolist())
+        assert_guards(t, v, "%s T[%d]" % (what, b))
 
 
 def check_untouched(c, out, tb, what):
     """a refused call: nothing written at all"""
-    for name, bufs in (("Out", out), ("T", tb or [])):
-        for b, x in enumerate(bufs):
-            assert (x.view(np.uint64) == SENT).all(), "%s: %s[%d] was written by a refused call" % (what, name, b)
-
-
-def _exact(got, want, what):
-    if not np.array_equal(got, want):
-        diff = np.argwhere(~(got == want))
-        i = tuple(diff[0])
-        raise AssertionError("%s: %d of %d elements differ from the exact result, first at %s: got %r, exact %r" % (what, len(diff), got.size, i, got[i], want[i]))
-
-
-def _bounded(got, hi, lo, tol, what):
-    err = np.abs((got - hi) - lo)
-    over = ~(err <= tol)
-    if over.any():
-        i = tuple(np.argwhere(over)[0])
-        raise AssertionError("%s: %d of %d elements outside the bound, first at %s: got %r, ref %r, |err| %.3e > %.3e"
-                             % (what, int(over.sum()), got.size, i, got[i], hi[i], err[i], tol[i]))
-    rn = float(np.linalg.norm(hi))
-    if rn > 0:
-        r = float(np.linalg.norm(err)) / rn
-        assert r <= FROB, "%s: Frobenius ratio %.3e" % (what, r)
-    return float(np.max(err / np.where(tol > 0, tol, 1.0), initial=0.0))
+    assert_untouched(out, what + " Out")
+    assert_untouched(tb or [], what + " T")
 
 
 def check_results(c, layout, wt, out, tb, tr, integer, what=""):
@@ -540,9 +501,9 @@ def check_results(c, layout, wt, out, tb, tr, integer, what=""):
             if got is None:
                 continue
             if integer:
-                _exact(got, tr[name][b], "%s %s[%d]" % (what, name, b))
+                exact(got, tr[name][b], "%s %s[%d]" % (what, name, b))
             else:
-                worst[name] = max(worst[name], _bounded(got, tr[name][b], tr[name + "_lo"][b], tr[name + "_tol"][b], "%s %s[%d]" % (what, name, b)))
+                worst[name] = max(worst[name], bounded(got, tr[name][b], tr[name + "_lo"][b], tr[name + "_tol"][b], "%s %s[%d]" % (what, name, b), FROB))
     return worst
 
 

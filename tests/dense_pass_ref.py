@@ -34,11 +34,10 @@ from collections import namedtuple
 
 import numpy as np
 
-C_BOUND = 2.0
+from tests.edge_kit import C_BOUND, LD, SENT, assert_guards, assert_untouched, bounded, exact, guarded, sentinel_buffer  # noqa: F401
+
 PRE = POST = 64
-SENT = np.float64(-1.0 / 3.0).view(np.uint64)
 FROB = 1e-13
-LD = np.longdouble
 ENTRY = {"first": "ttsk_dense_first_pass", "left": "ttsk_dense_left_pass"}
 
 First = namedtuple("First", "id n0 Q T ll r opts")
@@ -314,9 +313,7 @@ def truth(c, v, integer):
 
 
 def _guarded(arr, off=0):
-    b = np.full(PRE + off + arr.size + POST, SENT, dtype=np.uint64).view(np.float64)
-    b[PRE + off:PRE + off + arr.size] = arr.reshape(-1)
-    return b
+    return guarded(arr, PRE, POST, off)
 
 
 def operands(c, v):
@@ -331,7 +328,7 @@ def operands(c, v):
 
 def sentinels(c):
     """host images of the output buffers before a call: every element the sentinel"""
-    return {n: np.full(PRE + offset(c, n) + int(np.prod(s)) + POST, SENT, dtype=np.uint64).view(np.float64) for n, s in out_shapes(c).items()}
+    return {n: sentinel_buffer(offset(c, n) + int(np.prod(s)), PRE, POST) for n, s in out_shapes(c).items()}
 
 
 def view(c, name, buf):
@@ -351,38 +348,12 @@ def float64_result(c, v):
 # ------------------------------------------------------------------------------------------------ the checks
 def check_guards(c, out, what):
     for n, b in out.items():
-        inside = np.zeros(b.size, dtype=bool)
-        o = PRE + offset(c, n)
-        inside[o:o + int(np.prod(out_shapes(c)[n]))] = True
-        bad = np.flatnonzero(~inside & (b.view(np.uint64) != SENT))
-        assert bad.size == 0, "%s: %d guard elements of %s overwritten, first at buffer index %s" % (what, bad.size, n, bad[:8].tolist())
+        assert_guards(b, [(PRE + offset(c, n), (int(np.prod(out_shapes(c)[n])),), (1,))], "%s %s" % (what, n))
 
 
 def check_untouched(out, what):
     """a refused call: nothing written at all"""
-    for n, b in out.items():
-        assert (b.view(np.uint64) == SENT).all(), "%s: %s was written by a refused call" % (what, n)
-
-
-def _exact(got, want, what):
-    if not np.array_equal(got, want):
-        diff = np.argwhere(~(got == want))
-        i = tuple(diff[0])
-        raise AssertionError("%s: %d of %d elements differ from the exact result, first at %s: got %r, exact %r" % (what, len(diff), got.size, i, got[i], want[i]))
-
-
-def _bounded(got, hi, lo, tol, what):
-    err = np.abs((got - hi) - lo)
-    over = ~(err <= tol)
-    if over.any():
-        i = tuple(np.argwhere(over)[0])
-        raise AssertionError("%s: %d of %d elements outside the bound, first at %s: got %r, ref %r, |err| %.3e > %.3e"
-                             % (what, int(over.sum()), got.size, i, got[i], hi[i], err[i], tol[i]))
-    rn = float(np.linalg.norm(hi))
-    if rn > 0:
-        r = float(np.linalg.norm(err)) / rn
-        assert r <= FROB, "%s: Frobenius ratio %.3e" % (what, r)
-    return float(np.max(err / np.where(tol > 0, tol, 1.0), initial=0.0))
+    assert_untouched(out, what)
 
 
 def check_results(c, out, tr, integer, what=""):
@@ -394,8 +365,8 @@ def check_results(c, out, tr, integer, what=""):
     for n in OUT_NAMES[c.kind]:
         got, (hi, lo, tol) = view(c, n, out[n]), tr[n]
         if integer:
-            _exact(got, hi, "%s %s" % (what, n))
+            exact(got, hi, "%s %s" % (what, n))
             worst[n] = 0.0
         else:
-            worst[n] = _bounded(got, hi, lo, tol, "%s %s" % (what, n))
+            worst[n] = bounded(got, hi, lo, tol, "%s %s" % (what, n), FROB)
     return worst

@@ -31,12 +31,10 @@ from collections import namedtuple
 
 import numpy as np
 
-C_BOUND = 2.0
+from tests.edge_kit import C_BOUND, LD, PAD, SENT, assert_guards, assert_untouched, bounded, exact, sentinel_buffer, strided  # noqa: F401
+
 PRE = POST = 64
-PAD = 1e300
-SENT = np.float64(-1.0 / 3.0).view(np.uint64)
 FROB = 1e-12
-LD = np.longdouble
 KINDS = {"ss": "ttsk_psi_stream", "sss": "ttsk_psi_stream_sum"}
 BUDGET = 5e8            # multiply-adds of a case: about 3 s of long-double arithmetic on one core
 W_MORE = 4              # rows of NaN behind the last W view
@@ -307,10 +305,6 @@ def truth(c, vals, integer):
 
 
 # ------------------------------------------------------------------------------------------------ buffers
-def _strided(buf, off, shape, strides):
-    return np.lib.stride_tricks.as_strided(buf[off:], shape=shape, strides=tuple(8 * s for s in strides))
-
-
 def operands(c, vals):
     """host images of the S and W buffers, guards included: ([S buffers], [W buffers]); every base sits at PRE.  ss: one
     buffer per problem, sss: one buffer holding all terms"""
@@ -321,9 +315,9 @@ def operands(c, vals):
         hS, hW = [], []
         for b in range(c.nb):
             s = np.full(PRE + c.J * sj + POST, PAD)
-            _strided(s, PRE, (c.J, c.K1), (sj, 1))[...] = S[b]
+            strided(s, PRE, (c.J, c.K1), (sj, 1))[...] = S[b]
             w = np.full(PRE + (c.K1 + W_MORE) * wc + POST, np.nan)
-            _strided(w, PRE, (c.K1, c.A), (wc, 1))[...] = W[b]
+            strided(w, PRE, (c.K1, c.A), (wc, 1))[...] = W[b]
             hS.append(s); hW.append(w)
         return hS, hW
     sb, wb = max(g["s_b"], 0), g["w_b"]
@@ -333,21 +327,21 @@ def operands(c, vals):
         for b in range(c.nb - 1):
             s[PRE + b * sb + c.J * sj:PRE + (b + 1) * sb] = np.nan
     for b in range(c.nb):
-        _strided(s, PRE + b * sb, (c.J, c.K1), (sj, 1))[...] = S[b]
-        _strided(w, PRE + b * wb, (c.K1, c.A), (wc, 1))[...] = W[b]
+        strided(s, PRE + b * sb, (c.J, c.K1), (sj, 1))[...] = S[b]
+        strided(w, PRE + b * wb, (c.K1, c.A), (wc, 1))[...] = W[b]
     return [s], [w]
 
 
 def c_views(c, bufs):
     g = geometry(c)
-    return [_strided(x, PRE, (c.J, c.A), (g["c_alloc"], 1)) for x in bufs]
+    return [strided(x, PRE, (c.J, c.A), (g["c_alloc"], 1)) for x in bufs]
 
 
 def sentinels(c, vals=None):
     """host images of the C buffers before a call: the sentinel everywhere, the prior values in the window of an accumulating call"""
     g = geometry(c)
     nres = max(c.nb, 1) if c.kind == "ss" else 1
-    out = [np.full(PRE + c.J * g["c_alloc"] + POST, SENT, dtype=np.uint64).view(np.float64) for _ in range(min(nres, 33))]
+    out = [sentinel_buffer(c.J * g["c_alloc"], PRE, POST) for _ in range(min(nres, 33))]
     if vals is not None and vals[2] is not None:
         for v, p in zip(c_views(c, out), vals[2]):
             v[...] = p
@@ -358,39 +352,13 @@ def sentinels(c, vals=None):
 def check_guards(c, out, what):
     """every element of the C buffers outside the J x A windows still holds the sentinel"""
     g = geometry(c)
-    idx = np.arange(out[0].size, dtype=np.int64)
-    inside = np.zeros(out[0].size, dtype=bool)
-    inside[_strided(idx, PRE, (c.J, c.A), (g["c_alloc"], 1)).reshape(-1)] = True
     for b, o in enumerate(out):
-        bad = np.flatnonzero(~inside & (o.view(np.uint64) != SENT))
-        assert bad.size == 0, "%s: %d guard / padding elements of C[%d] overwritten, first at buffer index %s" % (what, bad.size, b, bad[:8].tolist())
+        assert_guards(o, [(PRE, (c.J, c.A), (g["c_alloc"], 1))], "%s C[%d]" % (what, b))
 
 
 def check_untouched(c, out, what):
     """a refused call: nothing written at all"""
-    for b, x in enumerate(out):
-        assert (x.view(np.uint64) == SENT).all(), "%s: C[%d] was written by a refused call" % (what, b)
-
-
-def _exact(got, want, what):
-    if not np.array_equal(got, want):
-        diff = np.argwhere(~(got == want))
-        i = tuple(diff[0])
-        raise AssertionError("%s: %d of %d elements differ from the exact result, first at %s: got %r, exact %r" % (what, len(diff), got.size, i, got[i], want[i]))
-
-
-def _bounded(got, hi, lo, tol, what):
-    err = np.abs((got - hi) - lo)
-    over = ~(err <= tol)
-    if over.any():
-        i = tuple(np.argwhere(over)[0])
-        raise AssertionError("%s: %d of %d elements outside the bound, first at %s: got %r, ref %r, |err| %.3e > %.3e"
-                             % (what, int(over.sum()), got.size, i, got[i], hi[i], err[i], tol[i]))
-    rn = float(np.linalg.norm(hi))
-    if rn > 0:
-        r = float(np.linalg.norm(err)) / rn
-        assert r <= FROB, "%s: Frobenius ratio %.3e" % (what, r)
-    return float(np.max(err / np.where(tol > 0, tol, 1.0), initial=0.0))
+    assert_untouched(out, what + " C")
 
 
 def check_results(c, out, tr, integer, what=""):
@@ -405,9 +373,9 @@ def check_results(c, out, tr, integer, what=""):
         if rows < c.J:
             assert np.isnan(got[rows:, :]).all(), "%s: row %d of C[%d] is not NaN throughout: the gap behind a term was not read as documented" % (what, rows, r)
         if integer:
-            _exact(got[:rows], tr["C"][r][:rows], "%s C[%d]" % (what, r))
+            exact(got[:rows], tr["C"][r][:rows], "%s C[%d]" % (what, r))
         else:
-            worst = max(worst, _bounded(got[:rows], tr["C"][r][:rows], tr["C_lo"][r][:rows], tr["C_tol"][r][:rows], "%s C[%d]" % (what, r)))
+            worst = max(worst, bounded(got[:rows], tr["C"][r][:rows], tr["C_lo"][r][:rows], tr["C_tol"][r][:rows], "%s C[%d]" % (what, r), FROB))
     return worst
 
 

@@ -7,18 +7,13 @@
     must dominate every case, and the two refusal messages are as the driver states them.
 (b) The checker itself: from the truth of three small cases, "kernel results" with one seeded defect each.  The integer
     and the Gaussian check must reject every one and accept the float64 restatement of the kernel."""
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import assemble_batch_ref as ref
+from tests.host_driver import compile_driver, run_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
 LDS_MAX = 160 * 1024
 
 DRIVER = r"""
@@ -131,15 +126,10 @@ def parse(text):
 
 @pytest.fixture(scope="module")
 def plans(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("assemble_batch_plan")
-    src, exe, cases = d / "driver.cpp", d / "driver", d / "cases.txt"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "assemble_batch_plan", DRIVER)
+    cases = exe.parent / "cases.txt"
     cases.write_text("".join(ref.plan_input(c) for c in ref.cases() + [ref.POISON]))
-    return parse(subprocess.run([str(exe), str(cases)], check=True, capture_output=True, text=True).stdout)
+    return parse(run_driver(exe, [cases]))
 
 
 def check_shape(c, s):

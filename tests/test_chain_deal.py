@@ -1,14 +1,10 @@
 """The host-side deal of the fused chain step's work over a workgroup's waves (csrc/chain_deal.h, plain C++): a few
 lines of driver compiled with the host compiler print the table -- for the tile structures and the k-blocks the plan
 (csrc/chain_plan.h) itself derives from the ranks -- and the table is checked here, before any kernel reads it."""
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
+from tests.host_driver import compile_driver, run_driver
 
 DRIVER = r"""
 #include <cstdio>
@@ -48,17 +44,10 @@ JS = (4, 16, 17, 96, 100, 112)
 
 @pytest.fixture(scope="module")
 def deal(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("chain_deal")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "chain_deal", DRIVER)
 
     def run(J, A, A2, K1):
-        out = subprocess.run([str(exe)] + [str(x) for x in (J, A, A2, K1)], check=True, capture_output=True,
-                             text=True).stdout.splitlines()
+        out = run_driver(exe, (J, A, A2, K1)).splitlines()
         nqf, strq, nnf, strn, kb1 = (int(x) for x in out[0].split()[1:])
         h = out[1].split()
         head = dict(waves=int(h[1]), npieces=int(h[3]), useful=float(h[5]), cap=float(h[7]), simd=[int(x) for x in h[9:13]],

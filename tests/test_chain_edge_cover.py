@@ -7,14 +7,12 @@
     branch list; every case meant to be refused must be refused with force = 1.
 (b) The checker itself: from the truth of three small cases, "kernel results" with one defect each.  The integer and the
     Gaussian check must reject every one and accept the float64 einsum result."""
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 from tests import chain_step_ref as ref
-from tests.test_chain_plan import CALL_KEYS, CSRC, DRIVER, INCLUDE, check_fused, check_sum, check_wide, parse
+from tests.host_driver import compile_driver, run_driver
+from tests.test_chain_plan import CALL_KEYS, DRIVER, check_fused, check_sum, check_wide, parse
 
 N_CU = 256
 BUDGET = 5e8                       # multiply-adds of the two products of a case: about 3 s of long-double arithmetic on one core
@@ -25,20 +23,15 @@ OVER_BUDGET = {"f-lv-K100"}
 
 @pytest.fixture(scope="module")
 def plans(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("chain_edges")
-    src, exe, cases = d / "driver.cpp", d / "driver", d / "cases.txt"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "chain_edges", DRIVER)
+    cases = exe.parent / "cases.txt"
     lines = []
     for c in ref.all_cases() + ref.refusals():
         for layout in ref.layouts(c):
             for wt in ref.T_MODES[c.kind][1:]:
                 lines.append("%s|%s|%d %s\n" % (c.id, layout, wt, " ".join(str(x) for x in ref.plan_call(c, layout, wt))))
     cases.write_text("".join(lines))
-    return parse(subprocess.run([str(exe), str(N_CU), str(cases)], check=True, capture_output=True, text=True).stdout)
+    return parse(run_driver(exe, [N_CU, cases]))
 
 
 def records(res, c):

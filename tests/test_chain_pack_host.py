@@ -16,15 +16,10 @@ For every (A, A2) of the list: the verdict of chain_fused_plan, and where chain_
 
 A second driver does the same for the image chain_wide_kernel's loader gathers with e_image_unit_from: a chunk of rows from
 a row origin on, and odd A2 (WIDE_CASES below)."""
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
+from tests.host_driver import compile_driver, run_driver
 
 RANKS = ((100, 100), (50, 50), (52, 50), (112, 112), (16, 16), (18, 2), (4, 100))
 # what chain_fused_plan says (force = 1, K1 = 32, J = 40): A2 = 2 is below the kernel's 4, A = 4 has no full tile
@@ -222,17 +217,10 @@ int main(int argc, char **argv)
 
 
 def _run_driver(tmp_path_factory, name, text, args):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp(name)
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(text)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
-    r = subprocess.run([str(exe)] + [str(x) for x in args], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return [dict(x.split("=") for x in line.split()) for line in r.stdout.splitlines()]
+    exe = compile_driver(tmp_path_factory, name, text)
+    out = run_driver(exe, args)
+    print(out)
+    return [dict(x.split("=") for x in line.split()) for line in out.splitlines()]
 
 
 @pytest.fixture(scope="module")

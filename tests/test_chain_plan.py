@@ -11,14 +11,11 @@ checked here -- before any kernel reads it.
     the kernels rely on."""
 import json
 import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
+from tests.host_driver import ROOT, compile_driver, run_driver
+
 FIXTURE = os.path.join(ROOT, "tests", "golden", "chain_plan_cases.json")
 
 LIM32 = (1 << 32) - 64
@@ -224,20 +221,15 @@ def fixture_file():
 @pytest.fixture(scope="module")
 def plans(tmp_path_factory, fixture_file):
     """every case of the fixture and of the edge list through the three plan functions, at both compute-unit counts"""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("chain_plan")
-    src, exe, cases = d / "driver.cpp", d / "driver", d / "cases.txt"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "chain_plan", DRIVER)
+    cases = exe.parent / "cases.txt"
     todo = {c[0]: c[1] for c in fixture_file["cases"]}
     for name, c in edge_list():
         assert todo.setdefault(name, c) == c, name
     cases.write_text("".join("%s %s\n" % (k, " ".join(str(x) for x in v)) for k, v in todo.items()))
     res, head = {}, None
     for n_cu in N_CU:
-        r, head = parse(subprocess.run([str(exe), str(n_cu), str(cases)], check=True, capture_output=True, text=True).stdout)
+        r, head = parse(run_driver(exe, [n_cu, cases]))
         res.update(r)
     return res, head, todo
 

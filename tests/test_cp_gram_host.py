@@ -3,18 +3,12 @@ C++) compiled with the host compiler and checked before any kernel reads it -- t
 total weight N M, the grid, partial and tile counts are those tests/cp_gram_ref.py restates, every refusal is listed; that
 float64 NumPy stays inside the derived bounds of that module against np.longdouble (so the bounds can be relied on in the
 GPU test); the host paths of ``CPTensor.dot`` / ``norm`` against dense evaluations and against runs of the reference."""
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import cp_gram_ref as cr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
+from tests.host_driver import compile_driver, run_driver
 
 ARG, UNSUPPORTED = -2, -3
 
@@ -87,16 +81,10 @@ int main(int argc, char **argv)
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("cp_gram_plan")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "cp_gram_plan", DRIVER)
 
     def run(*args):
-        return subprocess.run([str(exe)] + [str(x) for x in args], check=True, capture_output=True, text=True).stdout.splitlines()
+        return run_driver(exe, args).splitlines()
     return run
 
 

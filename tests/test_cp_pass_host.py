@@ -4,17 +4,13 @@ entries (csrc/cp_pass_plan.h, plain C++) compiled with the host compiler -- once
 behaviour sanitizers, as a stand-alone program -- the oracle against the recorded runs of the reference
 (tests/golden/cp_cases.npz), and the routing switch of ``cp_fused``."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import cp_pass_ref as ref
+from tests.host_driver import ROOT, compile_driver, run_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
 ERR_ARG, UNSUPPORTED = -2, -3
 
 
@@ -129,25 +125,15 @@ int main()
 
 
 def _compile(tmp_path_factory, name, extra):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    if "clang" in os.path.basename(cxx):                   # links its sanitizer runtimes statically as it is
-        extra = [x for x in extra if not x.startswith("-static-lib")]
-    d = tmp_path_factory.mktemp(name)
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", *extra, "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
-    return str(exe)
+    return compile_driver(tmp_path_factory, name, DRIVER, ["-g", *extra])
 
 
 def _ask(exe, requests, env=None):
     """requests: ("chain", flags, ldl, v_k, v_j, ldo, N, rho, n, rho1) or ("psi", flags, ldl, ldr, v_k, v_j, ld_om, r_om, N, l, n, r)"""
     text = "\n".join(" ".join(str(x) for x in (q if q[0] == "chain" else q + (0,))) for q in requests) + "\n"
-    done = subprocess.run([exe], input=text, capture_output=True, text=True, env=env)
-    assert done.returncode == 0, done.stderr[-2000:]
-    assert done.stderr == "", done.stderr[-2000:]                        # a sanitizer report goes there
-    lines = done.stdout.splitlines()
+    stdout, stderr = run_driver(exe, stdin=text, env=env, with_stderr=True)
+    assert stderr == "", stderr[-2000:]                                  # a sanitizer report goes there
+    lines = stdout.splitlines()
     assert len(lines) == len(requests) + 1
     const = [int(x) for x in lines[0].split()[1:]]
     out = []

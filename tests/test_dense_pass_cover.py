@@ -7,18 +7,13 @@
     must be refused with its message; no case asks for more scratch than its poison shape.
 (b) The checker itself: from the truth of three small cases, "kernel results" with one defect each.  The integer and the
     Gaussian check must reject every one and accept the float64 result."""
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import dense_pass_ref as ref
+from tests.host_driver import compile_driver, run_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
 TTSK_ERR_UNSUPPORTED = -3
 LDS_MAX = 160 * 1024
 
@@ -78,16 +73,11 @@ def parse(text):
 
 @pytest.fixture(scope="module")
 def plans(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("dense_pass_plan")
-    src, exe, cases = d / "driver.cpp", d / "driver", d / "cases.txt"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "dense_pass_plan", DRIVER)
+    cases = exe.parent / "cases.txt"
     todo = ref.all_cases() + ref.refusals() + [ref.POISON_FIRST, ref.POISON_LEFT]
     cases.write_text("".join("%s %s\n" % (c.id, ref.plan_call(c)) for c in todo))
-    return parse(subprocess.run([str(exe), str(cases)], check=True, capture_output=True, text=True).stdout)
+    return parse(run_driver(exe, [cases]))
 
 
 def check_first(c, f):

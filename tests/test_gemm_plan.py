@@ -20,16 +20,12 @@ import itertools
 import json
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from tests import gemm_families_ref as fam
+from tests.host_driver import ROOT, compile_driver, run_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
 DRIVER = os.path.join(ROOT, "tests", "gemm_plan_driver.cpp")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "gemm_plan_cases.json")
 
@@ -258,17 +254,12 @@ def parse(text):
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("gemm_plan")
-    exe = d / "driver"
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), DRIVER])
+    exe = compile_driver(tmp_path_factory, "gemm_plan", DRIVER)
 
     def run(lines):
-        f = d / "cases.txt"
+        f = exe.parent / "cases.txt"
         f.write_text("\n".join(lines) + "\n")
-        return subprocess.run([str(exe), str(f)], check=True, capture_output=True, text=True).stdout
+        return run_driver(exe, [f])
 
     return run
 

@@ -21,19 +21,13 @@ import numpy as np
 import pytest
 
 from tests import assemble_batch_ref as ref
+from tests.edge_kit import assert_bits_equal, nat, run_entry, same_bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 P = ctypes.c_void_p
 CASES = ref.cases()
 WORST = {}
-
-
-@pytest.fixture(scope="module")
-def nat():
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return _native
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -54,14 +48,7 @@ def entry_args(c, ptr, **change):
 
 
 def run(nat, what, args):
-    nat.call("ttsk_sync", -1)
-    try:
-        nat.call("ttsk_tt_assemble_batch", *args)
-        nat.call("ttsk_sync", -1)
-    except (ValueError, nat.TtskUnsupported):
-        raise
-    except nat.TtskError as e:               # a HIP error: the device may have faulted, nothing more is started on it
-        pytest.exit("%s: %s" % (what, e), returncode=3)
+    run_entry(nat, "ttsk_tt_assemble_batch", args, what)
 
 
 class Device:
@@ -84,7 +71,7 @@ class Device:
 
     def operands_untouched(self, what):
         for n, h in self.host.items():
-            assert np.array_equal(self.dev[n].get().view(np.uint64), h.view(np.uint64)), "%s: %s was written" % (what, n)
+            assert_bits_equal(self.dev[n], h, "%s: %s" % (what, n))
 
 
 @pytest.fixture(scope="module")
@@ -100,10 +87,6 @@ def poison(nat):
     return call
 
 
-def same_bits(a, b):
-    return np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
 def one_pass(nat, poison, c, mode, seed):
     """poison, call, check, call again, compare; -> (the check's worst ratios, the output arenas)"""
     what = "%s %s" % (c.id, mode)
@@ -113,8 +96,7 @@ def one_pass(nat, poison, c, mode, seed):
     out = dev.call()
     worst = ref.check_results(c, vals, out, mode, what)
     again = dev.call()
-    for n in out:
-        assert same_bits(out[n], again[n]), "%s: %s differs in its bits on a second call" % (what, n)
+    same_bits(again, out, what + ", second call")
     dev.operands_untouched(what)
     return worst, out
 
@@ -144,7 +126,7 @@ def test_assemble_batch_edge_case(nat, poison, c):
         for name in out:
             for b in (0, 3):
                 o, sz = ref.place(c, name, b)
-                assert same_bits(out[name][o:o + sz], other[name][o:o + sz]), "%s: tensor %d of %s changes with its neighbours' route" % (c.id, b, name)
+                same_bits(out[name][o:o + sz], other[name][o:o + sz], "%s: tensor %d of %s changes with its neighbours' route:" % (c.id, b, name))
 
 
 @pytest.mark.parametrize("what", ref.ARG_ERRORS)

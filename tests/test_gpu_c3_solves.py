@@ -14,20 +14,14 @@ import pytest
 
 from oracle import ttsk_oracle as orc
 
+from tests.edge_kit import tsa  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 SHAPE, S_IN, L, R = (200,) * 6, 100, 50, 100
 TENSOR_TOL = 1e-10         # tensor-level bar for cores that went through a pseudo-inverse / QR: SURVEY section 8c's bar for full-rank
                            # Omega (measured since the refinement step of the assembly: 5e-14 median, 4e-11 max)
 ORTH_TOL = 1e-11           # || Q^T Q - I ||_F of every left unfolding
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def tt_norm(cores):

@@ -17,34 +17,17 @@ the C entry point, in both layouts of X and with every way of storing T:
 The far side of every cover limit must raise TtskUnsupported and write nothing."""
 import ctypes
 
-import numpy as np
 import pytest
 
 from tests import chain_step_ref as ref
+from tests.edge_kit import PROF_OTHER, assert_bits_equal, nat, num_cu, run_entry, same_bits  # noqa: F401
 from tests.test_chain_plan import bracket_name
 
 pytestmark = pytest.mark.gpu
 
 P = ctypes.c_void_p
-PROF_CLS = 11                       # csrc/prof.h PROF_OTHER: the chain entry points called directly
 CASES = ref.all_cases()
 REFUSED = ref.refusals()
-
-
-@pytest.fixture(scope="module")
-def nat():
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return _native
-
-
-@pytest.fixture(scope="module")
-def num_cu(nat):
-    cu, hbm, name = ctypes.c_int(), ctypes.c_size_t(), ctypes.create_string_buffer(128)
-    nat.call("ttsk_device_info", name, ctypes.c_size_t(len(name)), ctypes.byref(cu), ctypes.byref(hbm))
-    if cu.value != 256:
-        print("note: %d compute units, the tags assume 256: the kernel names are not compared" % cu.value)
-    return cu.value
 
 
 def expected_name(c, wt):
@@ -81,25 +64,10 @@ class Device:
         else:
             args += [arr(dT, [ref.PRE] * c.nb) if dT else None]
         args += [arr(dO, [ref.PRE] * c.nb), 0]
-        nat.call("ttsk_sync", -1)
         name = None
-        if profile:
-            nat.call("ttsk_prof_enable", 1)
         try:
-            try:
-                nat.call(ref.KINDS[c.kind], *args)
-                nat.call("ttsk_sync", -1)
-            except nat.TtskUnsupported:
-                raise
-            except nat.TtskError as e:           # a HIP error: the device may have faulted, nothing more is started on it
-                pytest.exit("%s: %s" % (c.id, e), returncode=3)
-            if profile:
-                buf = ctypes.create_string_buffer(160)
-                nat.call("ttsk_prof_kernel_name", PROF_CLS, buf, ctypes.c_size_t(len(buf)))
-                name = buf.value.decode()
+            name = run_entry(nat, ref.KINDS[c.kind], args, c.id, PROF_OTHER if profile else None)
         finally:
-            if profile:
-                nat.call("ttsk_prof_enable", 0)
             self.out = [d.get() for d in dO]
             self.T = [d.get() for d in dT] if dT else None
         return self.out, self.T, name
@@ -113,14 +81,7 @@ class Device:
     def operands_untouched(self, what):
         for name, host, dev in (("W", self.hW, self.dW), ("X", self.hX, self.dX), ("E", [self.hE], [self.dE])):
             for b, (h, d) in enumerate(zip(host, dev)):
-                assert np.array_equal(d.get().view(np.uint64), h.view(np.uint64)), "%s: %s[%d] was written" % (what, name, b)
-
-
-def same_bits(a, b, what):
-    for name, x, y in (("Out", a[0], b[0]), ("T", a[1] or [], b[1] or [])):
-        assert len(x) == len(y)
-        for i, (p, q) in enumerate(zip(x, y)):
-            assert np.array_equal(p.view(np.uint64), q.view(np.uint64)), "%s: %s[%d] differs in its bits" % (what, name, i)
+                assert_bits_equal(d, h, "%s: %s[%d]" % (what, name, b))
 
 
 @pytest.mark.parametrize("c", CASES, ids=[c.id for c in CASES])

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests.golden_io import rel
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -24,14 +25,6 @@ BATCHES = ((32, 19, 100), (1, 600, 52))
 # test_fused_chain_step_against_einsum)
 CASES = [(seed, J, A, A2, wt, right, nb, n, min(K1, 60) if A == 112 else K1) for seed, (J, (A, A2), wt, right, (nb, n, K1)) in
          enumerate(itertools.product(JS, RANKS, (False, True), (False, True), BATCHES))]
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "s%d-J%d-A%d-%d-%s-%s-nb%d" % (c[0], c[1], c[2], c[3], "T" if c[4] else "noT",

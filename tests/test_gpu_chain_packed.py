@@ -9,6 +9,8 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests.edge_kit import nat  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 P = ctypes.c_void_p
@@ -16,13 +18,6 @@ BATCHES = ((32, 19, 100), (1, 600, 52))      # (nb, n, K1) of test_gpu_chain_lev
 CASES = [(J, A, A2, right, wt, nb, n, K1) for (J, A, A2, right, wt) in ((100, 100, 100, True, False), (100, 50, 50, False, True),
                                                                          (97, 52, 50, False, True))
          for (nb, n, K1) in BATCHES] + [(48, 100, 100, True, False, 1, 40, 100)]
-
-
-@pytest.fixture(scope="module")
-def nat():
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return _native
 
 
 class Step:

@@ -15,20 +15,13 @@ import pytest
 from tests import cp_gram_ref as cr
 from tests import gather_ref
 from tests import tt_gram_ref
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED = -3
 SENTINEL = 12345.678
 U = 2.0 ** -53
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 @pytest.fixture(scope="module")

@@ -14,20 +14,13 @@ import numpy as np
 import pytest
 
 from tests import cp_pass_ref as ref
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ERR_ARG, UNSUPPORTED = -2, -3
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 8
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _ptr(x):

@@ -15,20 +15,13 @@ import numpy as np
 import pytest
 
 from tests import dense_error_ref as dr
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED = -3
 EXTENTS = (1, 15, 16, 17, 63, 64, 65, 200)
 RHOS = (1, 3, 4, 5, 16, 100, 130)
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _ptr(a, off=0):

@@ -16,23 +16,16 @@ poison shape.  Here every accepted case runs through the C entry point:
 The far side of every cover limit must raise TtskUnsupported and write nothing."""
 import ctypes
 
-import numpy as np
 import pytest
 
 from tests import dense_pass_ref as ref
+from tests.edge_kit import assert_bits_equal, nat, run_entry, same_bits, sentinel_buffer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 P = ctypes.c_void_p
 CASES = ref.all_cases()
 REFUSED = ref.refusals()
-
-
-@pytest.fixture(scope="module")
-def nat():
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return _native
 
 
 def entry_args(c, ptr):
@@ -43,14 +36,7 @@ def entry_args(c, ptr):
 
 
 def run(nat, c, args):
-    nat.call("ttsk_sync", -1)
-    try:
-        nat.call(ref.ENTRY[c.kind], *args)
-        nat.call("ttsk_sync", -1)
-    except nat.TtskUnsupported:
-        raise
-    except nat.TtskError as e:               # a HIP error: the device may have faulted, nothing more is started on it
-        pytest.exit("%s: %s" % (c.id, e), returncode=3)
+    run_entry(nat, ref.ENTRY[c.kind], args, c.id)
 
 
 class Device:
@@ -79,7 +65,7 @@ class Device:
 
     def operands_untouched(self, what):
         for n, h in self.host.items():
-            assert np.array_equal(self.dev[n].get().view(np.uint64), h.view(np.uint64)), "%s: %s was written" % (what, n)
+            assert_bits_equal(self.dev[n], h, "%s: %s" % (what, n))
 
 
 @pytest.fixture(scope="module")
@@ -109,8 +95,7 @@ def test_dense_pass_edge_case(nat, poison, c):
         out = dev.call()
         worst = ref.check_results(c, out, tr, integer)
         again = dev.call()
-        for n in out:
-            assert np.array_equal(out[n].view(np.uint64), again[n].view(np.uint64)), "%s: %s differs in its bits on a second call" % (what, n)
+        same_bits(again, out, what + ", second call")
         dev.operands_untouched(what)
     print("[dense pass edges] %s: largest |err| / bound, Gaussian pass: %s" % (c.id, ", ".join("%s %.3g" % kv for kv in worst.items())))
 
@@ -119,7 +104,7 @@ def test_dense_pass_edge_case(nat, poison, c):
 def test_outside_the_cover_is_refused_and_nothing_written(nat, c):
     from tt_sketch_amd.device import DevArray
     if c.opts.get("dummy"):              # refused before anything is touched: no operand of that size for this
-        host = np.full(ref.PRE + 64 + ref.POST, ref.SENT, dtype=np.uint64).view(np.float64)
+        host = sentinel_buffer(64, ref.PRE, ref.POST)
         d = DevArray.from_host(host)
         ptr = {n: d.ptr + 8 * ref.PRE for n in ref.IN_NAMES[c.kind] + ref.OUT_NAMES[c.kind]}
         with pytest.raises(nat.TtskUnsupported):

@@ -4,15 +4,9 @@ out-of-range index, d = 7, the classical TT-SVD at d = 2 and with a unit mode.""
 import numpy as np
 import pytest
 
+from tests.edge_kit import tsa  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _recovers(tsa, T, X, l, r, tol=1e-12):

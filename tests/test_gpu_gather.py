@@ -10,19 +10,12 @@ import numpy as np
 import pytest
 
 from tests import gather_ref as gr
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED = -3
 MAX_RANK = 256          # the widest TT rank ttsk_tt_gather covers
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _ptr(a):

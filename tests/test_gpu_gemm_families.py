@@ -34,26 +34,19 @@ import numpy as np
 import pytest
 
 from tests.gemm_families_ref import CASES, POST, PRE, REQUIRED, V, Case, _derived_tags, _family, _sizes
+from tests.edge_kit import C_BOUND, LD, PAD, PROF_OTHER, assert_guards, exact, sentinel_buffer, strided, tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-C_BOUND = 2.0
-PAD = 1e300                         # operand elements outside the view
-# C guards and, with accumulate off, C itself before the call: finite and not a multiple of 1/2, so an unwritten
-# element fails the integer pass and a stray accumulating store changes it (NaN + x would give the NaN back)
-SENT = np.float64(-1.0 / 3.0).view(np.uint64)
-PROF_CLS = 11                       # untagged ttsk_gemm calls (csrc/prof.h PROF_OTHER)
+# Operand elements outside the view are PAD.  C guards and, with accumulate off, C itself before the call are the sentinel:
+# finite and not a multiple of 1/2, so an unwritten element fails the integer pass and a stray accumulating store changes
+# it (NaN + x would give the NaN back)
+PROF_CLS = PROF_OTHER               # untagged ttsk_gemm calls
 
 
 # ------------------------------------------------------------------ host side of one case
 def _view(buf, v: V):
-    item = buf.itemsize
-    return np.lib.stride_tricks.as_strided(buf[PRE + v.off:], shape=v.shape, strides=tuple(s * item for s in v.strides))
-
-
-def _positions(v: V, n):
-    idx = np.arange(n, dtype=np.int64)
-    return _view(idx, v).reshape(-1)
+    return strided(buf, PRE + v.off, v.shape, v.strides)
 
 
 def _operand(rng, v: V, integer):
@@ -69,7 +62,7 @@ def _run(tsa, c: Case, integer: bool, seed: int):
     rng = np.random.default_rng(seed)
     size, K = _sizes(c)
     hA, hB = _operand(rng, c.A, integer), _operand(rng, c.B, integer)
-    hC = np.full(PRE + c.C.nelem + POST, SENT, dtype=np.uint64).view(np.float64)
+    hC = sentinel_buffer(c.C.nelem, PRE, POST)
     if c.acc:
         _view(hC, c.C)[...] = rng.integers(-4, 5, size=c.C.shape) if integer else rng.standard_normal(c.C.shape)
     ko_ki = (c.A.shape[2], c.A.shape[3]) if c.via == "desc" else None
@@ -122,10 +115,7 @@ def _run(tsa, c: Case, integer: bool, seed: int):
     assert np.array_equal(gB.view(np.uint64), hB.view(np.uint64)), f"{what}: B was written"
     if gS is not None:
         assert np.array_equal(gS.view(np.uint64), hS.view(np.uint64)), f"{what}: k_scale was written"
-    inside = np.zeros(hC.size, dtype=bool)
-    inside[_positions(c.C, hC.size)] = True
-    bad = np.flatnonzero(~inside & (gC.view(np.uint64) != SENT))
-    assert bad.size == 0, f"{what}: {bad.size} guard elements of C overwritten, first at buffer index {bad[:8].tolist()}"
+    assert_guards(gC, [(PRE + c.C.off, c.C.shape, c.C.strides)], what + " C")
     # 3. values
     got = _view(gC, c.C).copy()
     C0 = _view(hC, c.C).copy() if c.acc else np.zeros(c.C.shape)
@@ -138,13 +128,8 @@ def _run(tsa, c: Case, integer: bool, seed: int):
         s = np.einsum(spec, Ai, Bv.astype(np.int64)) if got.size else np.zeros(c.C.shape, np.int64)
         assert np.abs(s).max(initial=0) < 2 ** 50
         ref = c.alpha * s.astype(np.float64) + C0
-        if not np.array_equal(got, ref):
-            diff = np.argwhere(~(got == ref))
-            i = tuple(diff[0])
-            pytest.fail(f"{what}: {len(diff)} of {got.size} elements differ from the exact result, first at {i}: "
-                        f"got {got[i]!r}, exact {ref[i]!r}")
+        exact(got, ref, what)
         return
-    LD = np.longdouble
     Al = Av.astype(LD)
     Aa = np.abs(Al)
     if hS is not None:
@@ -166,14 +151,6 @@ def _run(tsa, c: Case, integer: bool, seed: int):
     rn = float(np.linalg.norm(ref.astype(np.float64)))
     if rn > 0:
         assert float(np.linalg.norm((got - ref.astype(np.float64)))) <= 1e-13 * rn, what
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])

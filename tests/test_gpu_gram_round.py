@@ -14,20 +14,13 @@ import numpy as np
 import pytest
 
 from tests import gram_round_ref as gr
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED = -3
 GUARD = 32                     # doubles on either side of every output
 SENTINEL = 12345.678
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 # ---------------------------------------------------------------- 1. the bond kernel alone

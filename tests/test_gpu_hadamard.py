@@ -15,24 +15,13 @@ import pytest
 
 from oracle import ttsk_oracle as orc
 from tests import hadamard_ref as ref
+from tests.edge_kit import rel_fro as rel, tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED = -3
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROUTES = ("kernel", "composed")
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
-
-
-def rel(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / np.linalg.norm(b)
 
 
 def _upload(a):

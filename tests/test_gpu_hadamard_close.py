@@ -17,6 +17,7 @@ import pytest
 from oracle import ttsk_oracle as orc
 from tests import hadamard_close_ref as ref
 from tests import hadamard_ref as apply_ref
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -24,14 +25,6 @@ UNSUPPORTED = -3
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROUTES = ("kernel", "composed")
 PAD = 8                        # doubles past the plan's slab that must stay untouched
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _upload(a):

@@ -9,6 +9,7 @@ import pytest
 
 from oracle import ttsk_oracle as orc
 from tests.golden_io import rel
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -17,14 +18,6 @@ SHAPE, TT_RANK, NB = (6, 7, 5, 9), (3, 5, 4), 3
 LEFT, RIGHT = (4, 6, 5), (5, 7, 6)
 # (left rank_min, left rank_max): the whole ranks, and a slice whose last entry -- the rows of Psi_{d-1} -- starts above 0
 SLICES = {"whole": ((0, 0, 0), LEFT), "sliced": ((1, 0, 2), (4, 5, 5))}
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 @pytest.fixture(scope="module", params=sorted(SLICES))

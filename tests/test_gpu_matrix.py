@@ -11,15 +11,9 @@ import itertools
 import numpy as np
 import pytest
 
+from tests.edge_kit import tsa  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _drm_types(kind):

@@ -16,20 +16,13 @@ import pytest
 
 from tests import hadamard_close_ref
 from tests import op_close_ref as ref
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED = -3
 ROUTES = ("kernel", "composed")
 PAD = 8                        # doubles past the plan's slab that must stay untouched
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _upload(a):

@@ -13,20 +13,13 @@ import numpy as np
 import pytest
 
 from tests import op_close_ref as ref
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED = -3
 GUARD = 16                     # doubles of NaN on both sides of every output and of the slab
 ROUTES = ("kernel", "composed", None)
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 @pytest.fixture(scope="module")

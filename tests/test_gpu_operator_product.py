@@ -14,22 +14,11 @@ import pytest
 
 from oracle import ttsk_oracle as orc
 from tests import op_apply_ref as ref
+from tests.edge_kit import rel_fro as rel, tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED = -3
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
-
-
-def rel(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / np.linalg.norm(b)
 
 
 def _upload(a):

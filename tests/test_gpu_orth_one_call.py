@@ -13,20 +13,14 @@ import pytest
 
 from oracle import ttsk_oracle as orc
 
+from tests.edge_kit import tsa  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 import os
 
 ONE_CALL = os.environ.get("TTSK_ORTH_ONE_CALL", "1") != "0"      # (the diagnostic switch sends everything mode by mode)
 CORE_TOL = 1e-9            # entrywise, relative to the largest entry of the core (cores went through pinv and QR)
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _case(shape, s_in, l, r, seed):

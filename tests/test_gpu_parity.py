@@ -15,20 +15,13 @@ import pytest
 
 from oracle import ttsk_oracle as orc
 from tests.golden_io import GOLDEN, Cases, rel
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 CASES = Cases()
 TOL = 1e-12
 ULP_BAR = 8      # hash Gaussians, device vs oracle / reference fixtures: the ONE stated bar (measured max 6)
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 # ------------------------------------------------------------------ contraction engine

@@ -19,18 +19,12 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests.edge_kit import tsa  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 NCLS = 12
 V = ctypes.c_void_p
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def read_classes():

@@ -25,29 +25,13 @@ import numpy as np
 import pytest
 
 from tests import psi_stream_ref as ref
+from tests.edge_kit import PROF_OTHER, assert_bits_equal, nat, num_cu, rel_fro, run_entry, same_bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 P = ctypes.c_void_p
-PROF_CLS = 11                       # csrc/prof.h PROF_OTHER: the entry points called directly
 CASES = ref.all_cases()
 REFUSED = ref.refusals()
-
-
-@pytest.fixture(scope="module")
-def nat():
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return _native
-
-
-@pytest.fixture(scope="module")
-def num_cu(nat):
-    cu, hbm, name = ctypes.c_int(), ctypes.c_size_t(), ctypes.create_string_buffer(128)
-    nat.call("ttsk_device_info", name, ctypes.c_size_t(len(name)), ctypes.byref(cu), ctypes.byref(hbm))
-    if cu.value != 256:
-        print("note: %d compute units, the tags assume 256: the kernel names are not compared" % cu.value)
-    return cu.value
 
 
 class Device:
@@ -75,38 +59,17 @@ class Device:
         else:
             args = [c.nb, c.J, c.K1, c.A, P(self.dS[0].ptr + 8 * ref.PRE), g["s_j"], g["s_b"], P(self.dW[0].ptr + 8 * ref.PRE), g["w_c"], g["w_b"],
                     P(dC[0].ptr + 8 * ref.PRE), g["c_j"], acc, 0]
-        nat.call("ttsk_sync", -1)
         name = None
-        if profile:
-            nat.call("ttsk_prof_enable", 1)
         try:
-            try:
-                nat.call(ref.KINDS[c.kind], *args)
-                nat.call("ttsk_sync", -1)
-            except nat.TtskUnsupported:
-                raise
-            except nat.TtskError as e:           # a HIP error: the device may have faulted, nothing more is started on it
-                pytest.exit("%s: %s" % (c.id, e), returncode=3)
-            if profile:
-                buf = ctypes.create_string_buffer(160)
-                nat.call("ttsk_prof_kernel_name", PROF_CLS, buf, ctypes.c_size_t(len(buf)))
-                name = buf.value.decode()
+            name = run_entry(nat, ref.KINDS[c.kind], args, c.id, PROF_OTHER if profile else None)
         finally:
-            if profile:
-                nat.call("ttsk_prof_enable", 0)
             self.out = [d.get() for d in dC]
         return self.out, name
 
     def operands_untouched(self, what):
         for name, host, dev in (("S", self.hS, self.dS), ("W", self.hW, self.dW)):
             for b, (h, d) in enumerate(zip(host, dev)):
-                assert np.array_equal(d.get().view(np.uint64), h.view(np.uint64)), "%s: %s[%d] was written" % (what, name, b)
-
-
-def same_bits(a, b, what):
-    assert len(a) == len(b)
-    for i, (p, q) in enumerate(zip(a, b)):
-        assert np.array_equal(p.view(np.uint64), q.view(np.uint64)), "%s: C[%d] differs in its bits" % (what, i)
+                assert_bits_equal(d, h, "%s: %s[%d]" % (what, name, b))
 
 
 @pytest.mark.parametrize("c", CASES, ids=[c.id for c in CASES])
@@ -138,10 +101,6 @@ def test_outside_the_cover_is_refused_and_nothing_written(nat, c):
 
 
 # ------------------------------------------------------------------------------------------------ through the driver
-def rel(a, b):
-    return float(np.linalg.norm(np.asarray(a) - b) / np.linalg.norm(b))
-
-
 def _sum_sketch(nat, shape, ranks, lr, rr, nb, seed, kernel, poison=None):
     """The sketch of the sum of nb random TTs -- ttsk_tt_sketch_sum through its plan object, then tsa.stream_sketch of the
     TensorSum -- against the sum of the oracle's sketches, at the bar of tests/test_gpu_parity.py; the Psi bracket (class 4)
@@ -205,7 +164,7 @@ def _sum_sketch(nat, shape, ranks, lr, rr, nb, seed, kernel, poison=None):
         assert buf.value.decode().startswith(kernel + "<"), (shape, run.__name__, buf.value.decode())
         for i, (a, w) in enumerate(zip(got, want)):
             assert a.shape == w.shape and np.isfinite(a).all(), (shape, run.__name__, i, "a non-finite element")
-            assert rel(a, w) < 1e-12, (shape, run.__name__, i, rel(a, w))
+            assert rel_fro(a, w) < 1e-12, (shape, run.__name__, i, rel_fro(a, w))
 
 
 def test_driver_hands_the_kernels_the_same_arguments(nat):

@@ -7,17 +7,10 @@ import pytest
 
 from oracle import ttsk_oracle as orc
 from tests.golden_io import rel
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _check(sk, oP, oO, tol=TOL):

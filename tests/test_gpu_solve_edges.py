@@ -24,6 +24,7 @@ import pytest
 import scipy.linalg
 
 from tests import solve_ref as sr
+from tests.edge_kit import same_bits, tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -91,14 +92,6 @@ S2, S1 = last_square(2), last_square(1)                           # 100, 142: th
 
 
 # ------------------------------------------------------------------ plumbing
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
-
-
 WORST = {}        # route -> (worst err / e_lapack, case)
 
 
@@ -139,10 +132,6 @@ def dev_nan(shape):
 
 def sync():
     nat().call("ttsk_sync", -1)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def accept(route, case, got, ref, lapack, kappa=None, extra=0.0):
@@ -282,7 +271,7 @@ def pinv_both(A, rcond, true_rank):
     """ttsk_pinv with host_rank and with host_rank == NULL (the predicated Jacobi launch): bit-identical, the rank right"""
     P, rk = c_pinv(A, rcond, True)
     P0, _ = c_pinv(A, rcond, False)
-    assert same_bits(P, P0), "host_rank == NULL must give the same bits as the read-back form"
+    same_bits(P, P0, "host_rank == NULL must give the same bits as the read-back form: P")
     assert rk == true_rank
     return P
 
@@ -397,7 +386,7 @@ def test_pinv_begin_end_on_two_streams(tsa):
                 nat().call("ttsk_pinv_end", d_om[i], *mats[i].shape, -1.0, d_p[i], ctypes.byref(rk[i]) if with_rank else None, s)
             sync()
             for i in range(2):
-                assert same_bits(d_p[i].get(), single[i]), (with_rank, order, i)
+                same_bits(d_p[i].get(), single[i], str((with_rank, order, i)))
                 if with_rank:
                     assert rk[i].value == min(mats[i].shape)
 
@@ -517,7 +506,8 @@ def test_orth_step(tsa, l):
     nat().call("ttsk_orth_step", d_psi, m, r2, d_om, l, d_q, 0)
     assert deferred_flag() == 0
     accept("orth_step", (m, r2, l), d_q.get(), Qref, Qs, ORTH_KAPPA)
-    assert same_bits(d_psi.get(), Psi) and same_bits(d_om.get(), Om)
+    same_bits(d_psi.get(), Psi, "Psi")
+    same_bits(d_om.get(), Om, "Omega")
 
 
 @pytest.mark.parametrize("l", ORTH_L)
@@ -546,7 +536,7 @@ def test_orth_step_without_omega(tsa, k):
     accept("orth_step, no Omega", (m, k), Q, Qref, Qs, ORTH_KAPPA)
     nat().call("ttsk_orth_step", d_psi, m, k, None, 0, d_psi, 0)
     assert deferred_flag() == 0
-    assert same_bits(d_psi.get(), Q)
+    same_bits(d_psi.get(), Q, "Psi")
 
 
 def test_orth_step_limits(tsa):
@@ -626,4 +616,4 @@ def test_triu_is_bit_exact(tsa, m, n):
     A = rng_for(m, n).standard_normal((m, n))
     d = dev(A)
     nat().call("ttsk_triu", d, m, n, 0)
-    assert same_bits(d.get(), np.triu(A))
+    same_bits(d.get(), np.triu(A), "R")

@@ -14,6 +14,7 @@ import pytest
 
 from tests import sparse_cases as sc
 from tests import sparse_chain_ref as ref
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -33,14 +34,6 @@ Cfg = namedtuple("Cfg", "name A B C c_left", defaults=(None, 0))
 
 def chain(rows, r0, *steps, lo=0, w=None):
     return Chain(rows, r0, steps, lo, steps[-1][1] - lo if w is None and steps else (r0 - lo if w is None else w))
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _packed(a, dtype):

@@ -23,20 +23,13 @@ import numpy as np
 import pytest
 
 from tests import sparse_cases as sc
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SPARE = float(2 ** 40)
 STRUCTURES = sc.structures()
 P_LEFT, P_RIGHT = 11, 13          # distinct prefixes / suffixes of the hand-made streams
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _packed(a, dtype):

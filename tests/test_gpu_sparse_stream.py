@@ -14,19 +14,12 @@ import numpy as np
 import pytest
 
 from tests import sparse_cases as sc
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 M64 = (1 << 64) - 1
 STRUCTURES = sc.structures()
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 # ------------------------------------------------------------------ the restatement

@@ -6,19 +6,13 @@ import pytest
 
 from oracle import ttsk_oracle as orc
 
+from tests.edge_kit import tsa  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-12            # the project's tolerance for TT-DRM cases (no ndtri is involved)
 TOL_HASHED = 1e-11     # of the existing hashed-DRM tests
 C4 = (200, 150, 100, 120, 300)
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def rel(a, b):

@@ -12,20 +12,14 @@ import pytest
 
 from oracle import ttsk_oracle as orc
 
+from tests.edge_kit import tsa  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TENSOR_TOL = 1e-10          # full-rank Omega (tests/test_gpu_c3_solves.py)
 ROBUST_TOL = 1e-9           # rank-deficient / ill-conditioned Omega (the Jacobi path)
 TILE = 32                   # rows of a tile of the fused apply (AB_TM in assemble_batch.hip)
 COVER_MIN, COVER_MAX = 56, 112
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def tt_norm(cores):

@@ -12,20 +12,13 @@ import numpy as np
 import pytest
 
 from tests import tucker_ref as tr
+from tests.edge_kit import tsa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ARG, UNSUPPORTED = -2, -3
 GUARD = 16
 SENTINEL = -123.25
-
-
-@pytest.fixture(scope="module")
-def tsa():
-    import tt_sketch_amd
-    from tt_sketch_amd import _native
-    _native.call("ttsk_init", 0)
-    return tt_sketch_amd
 
 
 def _ptr(a):

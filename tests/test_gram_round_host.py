@@ -2,19 +2,13 @@
 ``TensorTrain.round`` and against the dense truths of a bond, with the figures the GPU test takes its tolerances from; the
 plan of ttsk_gram_round_bonds (csrc/gram_round_plan.h, plain C++) compiled with the host compiler and driven over the edges
 of the working set; and what ``method="gram"`` does before it reaches a device."""
-import os
-import shutil
-import subprocess
 import typing
 
 import numpy as np
 import pytest
 
 from tests import gram_round_ref as gr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
+from tests.host_driver import ROOT, compile_driver, run_driver
 
 ARG, UNSUPPORTED = -2, -3
 
@@ -162,17 +156,11 @@ int main(int argc, char **argv)
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("gram_round_plan")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "gram_round_plan", DRIVER)
 
     def run(bonds, eps=0.0, variant="ok"):
         args = [variant, repr(float(eps))] + [str(v) for rc in bonds for v in rc]
-        out = subprocess.run([str(exe)] + args, check=True, capture_output=True, text=True).stdout.splitlines()
+        out = run_driver(exe, args).splitlines()
         p = dict(rc=int(out[0].split()[1]), msg=out[1][4:], bonds=[], layouts=[])
         for line in out[2:]:
             key, *v = line.split()

@@ -2,23 +2,15 @@
 ``ttsk_hadamard_apply`` (tests/hadamard_ref.py) against the explicit Kronecker core and against np.longdouble,
 ``HadamardProduct`` on host cores, its registration in the dispatch tables, and the host-side plan of the entry
 (csrc/hadamard_plan.h, plain C++) compiled with the host compiler."""
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import hadamard_ref as ref
+from tests.edge_kit import rel_fro as rel
+from tests.host_driver import compile_driver, run_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
 ERR_ARG, UNSUPPORTED = -2, -3
-
-
-def rel(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / np.linalg.norm(b)
 
 
 # ---- 1. the restatement
@@ -194,18 +186,12 @@ int main(int argc, char **argv)
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("hadamard_plan")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "hadamard_plan", DRIVER)
 
     def run(dims, w_cols, w_off=0, null=0):
         """dims: (R, R', r, r', n, l)"""
         args = list(dims) + [w_cols, w_off, null]
-        out = subprocess.run([str(exe)] + [str(x) for x in args], check=True, capture_output=True, text=True).stdout.splitlines()
+        out = run_driver(exe, args).splitlines()
         p = dict(rc=int(out[0].split()[1]), msg=out[1][4:])
         for line in out[2:]:
             key, *v = line.split()

@@ -3,19 +3,14 @@
 single call plans it, the table that maps a workgroup to its pair, the slab, every refusal -- and ``operator_gram.op_gram``
 on host factors against dense NumPy with the device, ``to_tt`` and the operators' ``__call__`` forbidden."""
 import itertools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import hadamard_ref
 from tests import op_close_ref as ref
+from tests.host_driver import compile_driver, run_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
 ERR_ARG, UNSUPPORTED = -2, -3
 ARRAYS = ("Wl", "N", "Y", "dims", "strides", "ldw", "out", "work")      # the bits of `null`
 ELEMENTS = ("Wl", "N", "Y", "out")                                     # the arrays of pointers
@@ -86,13 +81,7 @@ def _packed_strides(d):
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("op_close_batch_plan")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "op_close_batch_plan", DRIVER)
 
     def run(dims, strides=None, ldw=None, npairs=None, accumulate=0, work=2 ** 62, null=(), null_element=None, enumerate_=False):
         """dims: a list of (S, S', s, s', n_in, n_out, P); strides: per pair those of N and Y, of packed cores unless given;
@@ -104,7 +93,7 @@ def plan(tmp_path_factory):
                  int(enumerate_)]
         for d, s, l in zip(dims, strides, ldw):
             words += list(d) + list(s) + [l]
-        out = subprocess.run([str(exe)], input=" ".join(str(w) for w in words), check=True, capture_output=True, text=True).stdout.splitlines()
+        out = run_driver(exe, stdin=" ".join(str(w) for w in words)).splitlines()
         p = dict(rc=int(out[0].split()[1]), msg=out[1][4:], pair=[], blk=[], sum=[])
         for line in out[2:]:
             key, *v = line.split()

@@ -3,22 +3,15 @@
 the reference's recorded MPO product, its registration in the dispatch tables, and the host-side plan of the entry
 (csrc/op_apply_plan.h, plain C++) compiled with the host compiler."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import op_apply_ref as ref
+from tests.edge_kit import rel_fro as rel
+from tests.host_driver import ROOT, compile_driver, run_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
 ERR_ARG, UNSUPPORTED = -2, -3
-
-
-def rel(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / np.linalg.norm(b)
 
 
 # ---- 1. the restatement
@@ -154,18 +147,12 @@ int main(int argc, char **argv)
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("op_apply_plan")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "op_apply_plan", DRIVER)
 
     def run(l, w_cols, terms, K=None):
         """terms: rows (R, R', r, r', n_in, n_out, w_off, flags)"""
         args = [len(terms) if K is None else K, len(terms), l, w_cols] + [x for row in terms for x in row]
-        out = subprocess.run([str(exe)] + [str(x) for x in args], check=True, capture_output=True, text=True).stdout.splitlines()
+        out = run_driver(exe, args).splitlines()
         p = dict(rc=int(out[0].split()[1]), msg=out[1][4:], terms=[])
         for line in out[2:]:
             key, *v = line.split()

@@ -14,17 +14,13 @@ returns, and that is checked here -- before any kernel reads it.
     is tagged with, the refusals are refused, and the tags cover both launch tables completely."""
 import json
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import psi_stream_ref as ref
+from tests.host_driver import ROOT, compile_driver, run_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "psi_plan_cases.json")
 
 LIM32 = (1 << 32) - 64
@@ -178,18 +174,14 @@ def parse(text):
     return out, head
 
 
-def run_driver(tmp, cases, n_cus):
+def run_plans(tmp_path_factory, cases, n_cus):
     """cases {id: call} through the plans at each compute-unit count"""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    src, exe, txt = tmp / "driver.cpp", tmp / "driver", tmp / "cases.txt"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "psi_plan", DRIVER)
+    txt = exe.parent / "cases.txt"
     txt.write_text("".join("%s %s\n" % (k, " ".join(str(x) for x in v)) for k, v in cases.items()))
     res, head = {}, None
     for n_cu in n_cus:
-        r, head = parse(subprocess.run([str(exe), str(n_cu), str(txt)], check=True, capture_output=True, text=True).stdout)
+        r, head = parse(run_driver(exe, [n_cu, txt]))
         res.update(r)
     return res, head
 
@@ -206,7 +198,7 @@ def plans(tmp_path_factory, fixture_file):
     todo = {c[0]: c[1] for c in fixture_file["cases"]}
     for name, c in edge_list() + ref.plan_calls():
         assert todo.setdefault(name, c) == c, name
-    res, head = run_driver(tmp_path_factory.mktemp("psi_plan"), todo, N_CU + (0,))
+    res, head = run_plans(tmp_path_factory, todo, N_CU + (0,))
     return res, head, todo
 
 

@@ -2,17 +2,11 @@
 compiled with the host compiler prints the plan and the digits sg_chain_digits extracts, and both are checked here -- the LDS
 layout before any kernel reads it, the multiply-shift division against Python's divmod.  Plans without a chain factor are
 tests/test_sparse_plan.py's."""
-import os
-import shutil
-import subprocess
 
 import pytest
 
 from tests import sparse_chain_ref as ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
+from tests.host_driver import compile_driver, run_driver
 
 DRIVER = r"""
 #include <cstdio>
@@ -81,15 +75,8 @@ int main(int argc, char **argv)
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("sparse_chain_plan")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
-    return lambda args, stdin="": subprocess.run([str(exe)] + [str(x) for x in args], input=stdin, check=True, capture_output=True,
-                                                 text=True).stdout.splitlines()
+    exe = compile_driver(tmp_path_factory, "sparse_chain_plan", DRIVER)
+    return lambda args, stdin="": run_driver(exe, args, stdin=stdin).splitlines()
 
 
 def chain_args(w, lo, rows, rank0, steps):

@@ -4,17 +4,13 @@ refusal; the restated two-level search (tests/sparse_join_ref.py) against np.sea
 the float64 dot in the stated order inside the derived bound of the long-double truth; the restatement and the host paths
 of ``SparseTensor.dot`` / ``gather`` against runs of the reference; the argument checks that come before any device call."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from tests import sparse_join_ref as sj
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
+from tests.host_driver import ROOT, compile_driver, run_driver
 
 ARG, UNSUPPORTED = -2, -3
 
@@ -82,16 +78,10 @@ int main(int argc, char **argv)
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("sparse_join_plan")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "sparse_join_plan", DRIVER)
 
     def run(*args):
-        return subprocess.run([str(exe)] + [str(x) for x in args], check=True, capture_output=True, text=True).stdout.splitlines()
+        return run_driver(exe, args).splitlines()
     return run
 
 

@@ -2,17 +2,11 @@
 compiler print what sg_gauss_pass (csrc/sparse_fused.hip) launches sg_pass_kernel (csrc/sparse_pass.h) with, and that is
 checked here -- before any kernel reads it.  tests/sparse_cases.py restates the choice of instantiation and assumes a
 stretch of 256 records per wave; both are held against the launcher's own code."""
-import os
-import shutil
-import subprocess
 
 import pytest
 
 from tests import sparse_cases as sc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
+from tests.host_driver import compile_driver, run_driver
 
 DRIVER = r"""
 #include <cstdio>
@@ -57,14 +51,8 @@ ABSENT = sc.Spec(-1, 0, 0, 0)
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("sparse_plan")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
-    return lambda *args: subprocess.run([str(exe)] + [str(x) for x in args], check=True, capture_output=True, text=True).stdout.splitlines()
+    exe = compile_driver(tmp_path_factory, "sparse_plan", DRIVER)
+    return lambda *args: run_driver(exe, args).splitlines()
 
 
 @pytest.fixture(scope="module")

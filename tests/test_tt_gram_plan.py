@@ -2,18 +2,12 @@
 with the host compiler print what ttsk_tt_gram (csrc/tt_gram.hip) launches its kernels with, and that is checked here --
 before any kernel reads it.  Also held here: the chunk rule tests/tt_gram_ref.py restates, and that float64 NumPy stays
 inside the derived bound of that module against np.longdouble (so the bound can be relied on in the GPU test)."""
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import tt_gram_ref as gr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
+from tests.host_driver import compile_driver, run_driver
 
 DRIVER = r"""
 #include <cstdio>
@@ -52,18 +46,12 @@ MODE_KEYS = ("chunks", "body", "S", "TA", "pitch", "acc_rows", "t_rows", "acc_do
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("tt_gram_plan")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "tt_gram_plan", DRIVER)
 
     def run(shape, ranks_a, ranks_b, n_cu):
         """ranks_*: full rank rows (d + 1 numbers) of each train"""
         args = [len(shape), len(ranks_a), len(ranks_b), n_cu, *shape, *[r for row in ranks_a for r in row], *[r for row in ranks_b for r in row]]
-        out = subprocess.run([str(exe)] + [str(x) for x in args], check=True, capture_output=True, text=True).stdout.splitlines()
+        out = run_driver(exe, args).splitlines()
         p = dict(rc=int(out[0].split()[1]), msg=out[1][4:], modes=[])
         for line in out[2:]:
             key, *v = line.split()

@@ -4,18 +4,12 @@ the chunks, the LDS bytes, the grid as a function of N and the CU count, every r
 branch; that float64 NumPy stays inside the derived bars of that module against np.longdouble (so the bars can be relied
 on in the GPU test); the restatement against runs of the reference; and what the Python layer does before it touches the
 device."""
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import tucker_ref as tr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tt_sketch_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
+from tests.host_driver import compile_driver, run_driver
 
 ARG, UNSUPPORTED = -2, -3
 
@@ -81,16 +75,10 @@ int main(int argc, char **argv)
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler")
-    d = tmp_path_factory.mktemp("tucker_gather_plan")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, "-I", INCLUDE, "-o", str(exe), str(src)])
+    exe = compile_driver(tmp_path_factory, "tucker_gather_plan", DRIVER)
 
     def run(*args):
-        return subprocess.run([str(exe)] + [str(x) for x in args], check=True, capture_output=True, text=True).stdout.splitlines()
+        return run_driver(exe, args).splitlines()
     return run
 
 
