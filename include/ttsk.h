@@ -79,15 +79,29 @@ typedef struct {
 int ttsk_gemm(const ttsk_gemm_desc *desc, const double *A, const double *B, double *C,
               const double *k_scale /* NULL or length Ko*Ki, multiplies A along k */,
               int stream);
-/* strided copy / permute (<= 5 dims): dst[i0..i4] = src[i0..i4]; Tensor.T materialisation */
+/* The three vector entry points; their checks, routes and grids are the host plans of csrc/vector_plan.h.
+ *
+ * strided copy / permute (<= 5 dims): dst[i0..i4] = src[i0..i4], strides in elements; Tensor.T materialisation.
+ * The 8 bytes of an element are moved unchanged (NaN payloads, signalling NaNs, -0.0, subnormals).  A source stride of 0 is
+ * a broadcast read.  dst must not overlap src and must address each element once: elements are written in no stated order.
+ * Nothing but the addressed elements of dst is written.  TTSK_ERR_ARG: ndim outside 0 .. 5; shape or strides NULL with
+ * ndim > 0; a negative extent; dst or src NULL with elements to copy.  TTSK_ERR_UNSUPPORTED: a product of the extents that
+ * int64_t cannot hold (with one grid stride of 2^20 to spare).  An extent of 0 is TTSK_OK with no launch, NULL dst and src
+ * allowed.  A refused call launches nothing and writes nothing. */
 int ttsk_copy_strided(double *dst, const double *src, int ndim, const int64_t *shape,
                       const int64_t *dst_strides, const int64_t *src_strides, int stream);
 /* y[i] = a*x[i] + b*y[i] on contiguous buffers: SketchContainer.__add__
- * (sketch_container.py:61-69) and the TensorSum accumulators (sketch_dispatch.py:93-136) */
+ * (sketch_container.py:61-69) and the TensorSum accumulators (sketch_dispatch.py:93-136).
+ * b == 0 (either sign) does not read y: y[i] = a*x[i] whatever y held, NaN and inf included, so y may be uninitialised.
+ * x == y is allowed (an element is read and written by one thread); any other overlap is not.  a*x + b*y may or may not be
+ * contracted into a fused multiply-add.  TTSK_ERR_ARG: y or x NULL with n > 0; n == 0 is TTSK_OK with no launch. */
 int ttsk_axpby(double *y, const double *x, double a, double b, size_t n, int stream);
 /* dst[i] (+)= sum_{b<nb} src[b*stride + i], i < n: the partial sketches of a batch summed into one
  * (the `+=` loop of sum_sketch, sketch_dispatch.py:141-147); 16-byte loads when n and stride are even and the
- * bases 16-byte aligned */
+ * bases 16-byte aligned, 8-byte loads otherwise -- the same sums either way.
+ * The order is fixed: the accumulator starts from dst[i] with accumulate = 1 and from +0.0 with accumulate = 0 (dst is then
+ * not read), and the slices are added one at a time in ascending b, each sum rounded: the same bits on every call and on
+ * both routes.  TTSK_ERR_ARG: dst or src NULL, nb < 1, accumulate not 0 or 1; n == 0 is TTSK_OK with no launch. */
 int ttsk_sum_slices(double *dst, const double *src, int nb, size_t stride, size_t n, int accumulate, int stream);
 
 /* ---- TT input x TT DRMs: the whole streaming sketch in one call ---------------

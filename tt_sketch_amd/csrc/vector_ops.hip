@@ -1,13 +1,11 @@
 // Strided copies, axpby, the sum of the slices of a batch, and the probe of the fp64 matrix rate: the entry points that
 // move or add vectors without a contraction.
+// What each launch gets -- the checks, the copy's CopyDesc, the route of the slice sum, the grids -- is decided in vector_plan.h.
 #include "common.h"
+#include "vector_plan.h"
 
 namespace ttsk {
 
-struct CopyDesc {
-    int64_t shape[5], ds[5], ss[5];
-    int64_t total;
-};
 __global__ void copy_strided_kernel(double *dst, const double *src, CopyDesc c)
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < c.total;
@@ -132,52 +130,31 @@ int ttsk_copy_strided(double *dst, const double *src, int ndim, const int64_t *s
                       const int64_t *dst_strides, const int64_t *src_strides, int stream)
 {
     TTSK_STREAM(st, stream);
-    TTSK_ARG(ndim >= 0 && ndim <= 5, "ttsk_copy_strided: ndim %d > 5", ndim);
-    CopyDesc c;
-    c.total = 1;
-    for (int a = 0; a < 5; ++a) {
-        int src_a = a - (5 - ndim);
-        if (src_a >= 0) {
-            c.shape[a] = shape[src_a];
-            c.ds[a] = dst_strides[src_a];
-            c.ss[a] = src_strides[src_a];
-        } else {
-            c.shape[a] = 1;
-            c.ds[a] = 0;
-            c.ss[a] = 0;
-        }
-        TTSK_ARG(c.shape[a] >= 0, "ttsk_copy_strided: negative extent");
-        c.total *= c.shape[a];
-    }
-    if (c.total == 0) return TTSK_OK;
-    int64_t blocks = cdiv(c.total, 256);
-    if (blocks > 4096) blocks = 4096;
-    return launch(copy_strided_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dst, src, c);
+    CopyPlan p;
+    if (const int rc = copy_strided_plan(dst, src, ndim, shape, dst_strides, src_strides, &p)) { set_error("%s", p.msg); return rc; }
+    if (!p.blocks) return TTSK_OK;
+    return launch(copy_strided_kernel, dim3((unsigned)p.blocks), dim3(VEC_THREADS), 0, st, dst, src, p.c);
 }
 
 int ttsk_sum_slices(double *dst, const double *src, int nb, size_t stride, size_t n, int accumulate, int stream)
 {
     TTSK_STREAM(st, stream);
-    TTSK_ARG(dst && src && nb >= 1, "ttsk_sum_slices: bad argument");
-    if (n == 0) return TTSK_OK;
-    if ((n & 1) || (stride & 1) || (((uintptr_t)dst | (uintptr_t)src) & 15)) {
-        size_t blocks = (n + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        return launch(sum_slices_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dst, src, nb, stride, n, accumulate);
-    }
-    size_t blocks = (n / 2 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    return launch(sum_slices_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (double2 *)dst, (const double2 *)src,
-                  nb, stride / 2, n / 2, accumulate);
+    SumSlicesPlan p;
+    if (const int rc = sum_slices_plan(dst, src, nb, stride, n, accumulate, &p)) { set_error("%s", p.msg); return rc; }
+    if (!p.blocks) return TTSK_OK;
+    if (!p.vector)
+        return launch(sum_slices_scalar_kernel, dim3((unsigned)p.blocks), dim3(VEC_THREADS), 0, st, dst, src, nb, p.stride, p.n, accumulate);
+    return launch(sum_slices_kernel, dim3((unsigned)p.blocks), dim3(VEC_THREADS), 0, st, (double2 *)dst, (const double2 *)src,
+                  nb, p.stride, p.n, accumulate);
 }
 
 int ttsk_axpby(double *y, const double *x, double a, double b, size_t n, int stream)
 {
     TTSK_STREAM(st, stream);
-    if (n == 0) return TTSK_OK;
-    size_t blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    return launch(axpby_kernel, dim3((unsigned)blocks), dim3(256), 0, st, y, x, a, b, n);
+    AxpbyPlan p;
+    if (const int rc = axpby_plan(y, x, a, b, n, &p)) { set_error("%s", p.msg); return rc; }
+    if (!p.blocks) return TTSK_OK;
+    return launch(axpby_kernel, dim3((unsigned)p.blocks), dim3(VEC_THREADS), 0, st, y, x, a, b, n);
 }
 
 }  // extern "C"

@@ -243,6 +243,8 @@ class DevArray:
         if not isinstance(key, tuple):
             key = (key,)
         if any(k is Ellipsis for k in key):
+            if sum(k is Ellipsis for k in key) > 1:
+                raise IndexError("an index can only have a single ellipsis ('...')")
             i = [k is Ellipsis for k in key].index(True)
             fill = (slice(None),) * (self.ndim - (len(key) - 1 - sum(k is None for k in key)))
             key = key[:i] + fill + key[i + 1:]
