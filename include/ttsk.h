@@ -146,6 +146,16 @@ int ttsk_tt_sketch_sum(int nb, int d, const int64_t *n, const int64_t *s, const 
                        const int64_t *l_hi, const int64_t *rt, const int64_t *r_lo, const int64_t *r_hi,
                        const double *const *X, const double *const *DL, const double *const *DR,
                        double *out, int accumulate, int stream);
+/* Compute-unit budgets of the batched launches of the three calls above (csrc/sketch_split.h): the right chain steps, the
+ * left chain steps and the Psi products are each planned for a share of the device, so that the kernels of the call's two
+ * streams run beside each other on disjoint CUs instead of taking the chip in turns.  Per class: -1 = the library's policy
+ * (the default: a split only for a caller that keeps batched sketches in flight on more than one stream pair, known by
+ * consecutive calls going to different streams; the whole device otherwise), 0 = the whole device, > 0 = that many CUs
+ * (more than the device has: the whole device; fewer than nb: one workgroup per tensor).  Process-wide until changed;
+ * takes effect with the next call; queues nothing.  A budget changes
+ * how many partial sums a result is added up from: sketches under different budgets agree to rounding, not bit for bit;
+ * under one setting they are the same bits on every call.  For tests and measurements.  TTSK_ERR_ARG: a value below -1. */
+int ttsk_tt_sketch_split(int right_cus, int left_cus, int psi_cus);
 /* One interior step of a TensorTrainDRM chain for nb tensors of one signature, both products in one launch
  * with the intermediate kept on chip (csrc/chain_fused.h):
  *   Out_b[j, a'] = sum_{c, a, k} W_b[c, a] X_b(j, k, c) E[a, k, a']        (tensor_train_drm.py:81-87)

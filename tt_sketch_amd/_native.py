@@ -91,6 +91,7 @@ ENTRY_POINTS = {
     "ttsk_tt_sketch": Entry([I] + [POINTER(I64)] * 8 + [POINTER(P)] * 3 + [P, I, I], FORK_NEXT),
     "ttsk_tt_sketch_batch": Entry([I, I] + [POINTER(I64)] * 8 + [POINTER(P)] * 3 + [P, I64, I, I], FORK_NEXT),
     "ttsk_tt_sketch_sum": Entry([I, I] + [POINTER(I64)] * 8 + [POINTER(P)] * 3 + [P, I, I], FORK_NEXT),
+    "ttsk_tt_sketch_split": Entry([I, I, I]),
     "ttsk_chain_step": Entry(_CHAIN + [POINTER(P), POINTER(P), I], QUEUE),
     "ttsk_chain_step_wide": Entry(_CHAIN + [POINTER(P), POINTER(P), I], QUEUE),
     "ttsk_chain_step_sum": Entry(_CHAIN + [P, I64, I64, I64, POINTER(P), I], QUEUE),

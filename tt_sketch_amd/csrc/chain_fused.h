@@ -517,7 +517,8 @@ inline int chain_slab_reduce(hipStream_t st, const double *slab, const ChainLaun
 }
 
 // 1 = launched (the slab reduce included), 0 = shape not covered, < 0 = error
-int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force = false);
+// cus: the CU budget the launch is planned for (sketch_split.h); 0 = the whole device
+int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force = false, int cus = 0);
 
 // chain_pack.hip: the packed image registered for core E with exactly these extents and image layout, or nullptr
 const double *drm_packed_lookup(const double *E, int A, int n, int A2, int A2P, int eunits);

@@ -22,12 +22,12 @@ static int launch_chain_step(const ChainStep &a, int nf, int str, bool wt, int e
     return launch_chain_step_e(a, nf, str, wt, ebuf, unr, waves, lds, grid, st);
 }
 
-int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force)
+int chain_fused_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force, int cus)
 {
     const int n_cu = device_num_cu();
     if (n_cu < 1) return TTSK_ERR_HIP;
     ChainFusedPlan p;
-    if (!chain_fused_plan(c, n_cu, force, p)) return 0;
+    if (!chain_fused_plan(c, cus > 0 ? cus : n_cu, force, p)) return 0;
     ChainStep &a = p.a;
     a.slab = chain_slab_request(stream, p.l);
     if (!a.slab) return TTSK_ERR_HIP;

@@ -542,7 +542,8 @@ __global__ __launch_bounds__(512, 2) void chain_sum_kernel(ChainSum a)
 }
 
 // 1 = launched (the slab reduce included), 0 = shape not covered, < 0 = error (the call: ChainSumArgs, chain_plan.h)
-int chain_sum_try(const ChainSumArgs &c, int stream, hipStream_t st, bool force = false);
+// cus: the CU budget the launch is planned for (sketch_split.h); 0 = the whole device
+int chain_sum_try(const ChainSumArgs &c, int stream, hipStream_t st, bool force = false, int cus = 0);
 int launch_chain_sum_2(const ChainSum &a, bool wt, size_t lds, int grid, hipStream_t st);
 int launch_chain_sum_4(const ChainSum &a, bool wt, size_t lds, int grid, hipStream_t st);
 

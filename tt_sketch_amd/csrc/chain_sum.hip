@@ -8,13 +8,13 @@
 
 namespace ttsk {
 
-int chain_sum_try(const ChainSumArgs &cc, int stream, hipStream_t st, bool force)
+int chain_sum_try(const ChainSumArgs &cc, int stream, hipStream_t st, bool force, int cus)
 {
     const ChainStepArgs &c = cc.s;
     const int n_cu = device_num_cu();
     if (n_cu < 1) return TTSK_ERR_HIP;
     ChainSumPlan p;
-    if (!chain_sum_plan(cc, n_cu, force, p)) return 0;
+    if (!chain_sum_plan(cc, cus > 0 ? cus : n_cu, force, p)) return 0;
     ChainSum &ka = p.ka;
     ChainSumS &a = ka.s;
     a.slab = chain_slab_request(stream, p.l);
@@ -32,7 +32,6 @@ int chain_sum_try(const ChainSumArgs &cc, int stream, hipStream_t st, bool force
     }
 #endif
     int rc = p.na_run <= 2 ? launch_chain_sum_2(ka, p.wt, p.l.lds, p.l.grid, st) : launch_chain_sum_4(ka, p.wt, p.l.lds, p.l.grid, st);
-    if (rc != TTSK_OK) set_error("chain_sum_kernel launch failed");
 #ifdef TTSK_LAB
     if (stamps_on) {
         long long h[8 * 8 * 8];

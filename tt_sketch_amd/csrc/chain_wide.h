@@ -313,6 +313,7 @@ __global__ __launch_bounds__(512, 2) void chain_wide_kernel(ChainWide a)
     cw_compute<NQF, STRQ, NNF, STRN, WT, UNR, 1>(a, Wmine, El, myprob, unit, a0, cnt, k_beg, k_end, t0, -1);
 }
 
-int chain_wide_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force = false);
+// cus: the CU budget the launch is planned for (sketch_split.h); 0 = the whole device
+int chain_wide_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force = false, int cus = 0);
 
 }  // namespace ttsk

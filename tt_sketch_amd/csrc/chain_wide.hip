@@ -26,12 +26,12 @@ static int launch_chain_wide(int ci, const ChainWide &a, int nn, int sn, bool wt
     }
 }
 
-int chain_wide_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force)
+int chain_wide_try(const ChainStepArgs &c, int stream, hipStream_t st, bool force, int cus)
 {
     const int n_cu = device_num_cu();
     if (n_cu < 1) return TTSK_ERR_HIP;
     ChainWidePlan p;
-    if (!chain_wide_plan(c, n_cu, force, p)) return 0;
+    if (!chain_wide_plan(c, cus > 0 ? cus : n_cu, force, p)) return 0;
     ChainWide &a = p.a;
     a.slab = chain_slab_request(stream, p.l);
     if (!a.slab) return TTSK_ERR_HIP;

@@ -284,7 +284,8 @@ __global__ __launch_bounds__(512) void stream_small_sum_kernel(StreamSmallSum a)
 }
 
 // The launchers (stream_small.hip) carry out the plans of psi_plan.h: 1 = launched, 0 = shape not covered, < 0 = error
-int stream_small_sum_try(const StreamSmallSumArgs &c, int stream, hipStream_t st);
-int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st);
+// cus: the CU budget the launch is planned for (sketch_split.h); 0 = the whole device
+int stream_small_sum_try(const StreamSmallSumArgs &c, int stream, hipStream_t st, int cus = 0);
+int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st, int cus = 0);
 
 }  // namespace ttsk

@@ -14,11 +14,11 @@ static int launch_ss(const StreamSmall &a, int nf, int str, int unr, size_t lds,
     return 1;
 }
 
-int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st)
+int stream_small_try(const StreamSmallArgs &c, int stream, hipStream_t st, int cus)
 {
     (void)stream;
     PsiStreamPlan p;
-    const int ok = psi_stream_plan(c, device_num_cu(), p);
+    const int ok = psi_stream_plan(c, cus > 0 ? cus : device_num_cu(), p);
     if (ok != 1) return ok;
     ProfBracket prof(st, PROF_CURRENT, p.l.flops, "%s", p.l.name);
     const int rc = launch_ss(p.a, p.nf, p.str, p.unr, p.l.lds, p.l.grid, st);
@@ -33,11 +33,11 @@ static int launch_sss(const StreamSmallSum &a, int nf, int str, int unr, size_t 
     return 1;
 }
 
-int stream_small_sum_try(const StreamSmallSumArgs &c, int stream, hipStream_t st)
+int stream_small_sum_try(const StreamSmallSumArgs &c, int stream, hipStream_t st, int cus)
 {
     (void)stream;
     PsiStreamSumPlan p;
-    const int ok = psi_stream_sum_plan(c, device_num_cu(), p);
+    const int ok = psi_stream_sum_plan(c, cus > 0 ? cus : device_num_cu(), p);
     if (ok != 1) return ok;
     ProfBracket prof(st, PROF_CURRENT, p.l.flops, "%s", p.l.name);
     const int rc = launch_sss(p.a, p.nf, p.str, p.unr, p.l.lds, p.l.grid, st);

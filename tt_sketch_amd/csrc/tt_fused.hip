@@ -1,6 +1,7 @@
 // TT input x TT DRMs: the whole streaming sketch (both chains, Omega, Psi) as one C call.
 // See include/ttsk.h (ttsk_tt_sketch) for the contract and the reference lines it replaces.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <vector>
 #include "common.h"
@@ -11,6 +12,7 @@
 #include "chain_sum.h"
 #include "tt_chain.h"
 #include "stream_small.h"
+#include "sketch_split.h"
 
 namespace ttsk {
 
@@ -49,14 +51,20 @@ static int gemm_batch(int cls, int nb, ttsk_gemm_desc d, const BatchPtrs &p, int
 
 // A Psi product on the streamed kernel (stream_small.h), profiling class 4, with a.J set here from J: the kernel's row
 // count is an int, taller products are not covered.  1 = launched, 0 = not covered, < 0 = error.
+// cus: the CU budget of the Psi products of this call (sketch_split.h).
 template <class Args>
-static int psi_stream(int (*try_launch)(const Args &, int, hipStream_t), Args a, int64_t J, int q, hipStream_t st)
+static int psi_stream(int (*try_launch)(const Args &, int, hipStream_t, int), Args a, int64_t J, int q, hipStream_t st, int cus)
 {
     if (J >= (1ll << 30)) return 0;
     a.J = (int)J;
     ProfClass pc(4);
-    return try_launch(a, q, st);
+    return try_launch(a, q, st, cus);
 }
+
+// The process-wide setting of ttsk_tt_sketch_split: per class -1 = the policy's budget, 0 = the whole device, > 0 = that many CUs
+static std::atomic<int> split_set[3] = {{-1}, {-1}, {-1}};
+// The stream of the one-call sketch queued last in this process (run_chains: how a pipelining caller is known)
+static std::atomic<int> last_sketch_stream{-1};
 
 // Where Psi_mu and Omega_mu sit in one sketch (when psi_at / om_at are given), and the sketch's size
 static int64_t sketch_offsets(int d, const int64_t *n, const int64_t *l_lo, const int64_t *l_hi, const int64_t *r_lo,
@@ -155,6 +163,7 @@ struct Ctx : SketchWs {
     hipStream_t st;
     bool keep_t;              // keep the left chain's T for the Psi phase (false: the chains only)
     int aux = 0; hipStream_t st_aux = nullptr;   // the helper stream (set by run_chains, with the workspace)
+    SketchSplit cus = SKETCH_SPLIT_FULL;         // the CU budgets of this call (set by run_chains, asked once per call)
     const double *Xc(int b, int mu) const { return X[(size_t)b * d + mu]; }
     double *outb(int b) const { return out + (size_t)b * out_stride; }
 };
@@ -175,14 +184,28 @@ static int check_ranks(const char *who, int d, const int64_t *s, const int64_t *
 // One chain step in one launch, first choice first: the fused kernel (every extent <= 128, chain_fused.h); many
 // low-rank tensors (the terms of a sum): rows of several terms stacked into full tiles (chain_sum.h); then the wide
 // kernel (chain_wide.h).  2 = launched by the stacked-terms kernel (its T went to ca.Tint), 1 = launched by another,
-// 0 = no kernel covers the shape, < 0 = error.
-static int chain_step_try(int cls, const ChainSumArgs &ca, int stream, hipStream_t st)
+// 0 = no kernel covers the shape, < 0 = error.  cus: the CU budget of this chain's steps (sketch_split.h); the stacked-terms
+// kernel keeps its own grid rule (it leaves a quarter of the CUs to the other chain itself).
+static bool chain_step_fits_fused(int64_t K1, int64_t J, int64_t A, int64_t A2) { return K1 <= 128 && J <= 128 && A <= 128 && A2 <= 128; }
+
+// Whether chain_fused_plan will take an unforced step of these extents, as far as the extents alone decide it (its rules on
+// J, the parity of A2, the depth of phase A and the tile structures, chain_plan.h): what the split policy is asked with.
+static bool step_on_fused(int64_t K1, int64_t J, int64_t A, int64_t A2)
+{
+    if (!chain_step_fits_fused(K1, J, A, A2) || J > 112 || A < 4 || A2 < 4 || (A2 & 1) || 2 * K1 < A) return false;
+    int nq, sq, nn, sn;
+    chain_tile_split((int)A, nq, sq);
+    chain_tile_split((int)A2, nn, sn);
+    return nq == nn && sq == sn && nq >= 1 && nq + (sq ? 1 : 0) <= 7;
+}
+
+static int chain_step_try(int cls, const ChainSumArgs &ca, int stream, hipStream_t st, int cus)
 {
     const ChainStepArgs &cs = ca.s;
     ProfClass pc(cls);
-    int fz = (cs.K1 <= 128 && cs.J <= 128 && cs.A <= 128 && cs.A2 <= 128) ? chain_fused_try(cs, stream, st) : 0;
+    int fz = chain_step_fits_fused(cs.K1, cs.J, cs.A, cs.A2) ? chain_fused_try(cs, stream, st, false, cus) : 0;
     if (fz == 0 && (fz = chain_sum_try(ca, stream, st)) == 1) return 2;
-    if (fz == 0) fz = chain_wide_try(cs, stream, st);
+    if (fz == 0) fz = chain_wide_try(cs, stream, st, false, cus);
     return fz;
 }
 
@@ -203,7 +226,7 @@ static int right_step(const Ctx &c, int j)
     for (int b = 0; b < nb; ++b) { p.A[b] = c.Rp(b, j - 1); p.B[b] = c.Xc(b, mu); p.C[b] = c.Rp(b, j); }
     const ChainStepArgs cs{nb, (int)nn, (int)sp, (int)rho, (int)rhop, (int)sn, p.A, rho, p.B, nn * sp, sp, 1, sn * nn * sp,
                            c.DR[j], nullptr, p.C};
-    CK(chain_step_try(1, ChainSumArgs{cs, nullptr, 0, 0, 0}, c.stream, c.st));
+    CK(chain_step_try(1, ChainSumArgs{cs, nullptr, 0, 0, 0}, c.stream, c.st, c.cus.right));
     if (rc) return TTSK_OK;
     // otherwise two launches.  T[q, k, b, p''] = sum_p Rc_b[p,q] X_b[p'',k,p]: a product batched over k whose
     // batch index joins the streamed index, written interleaved over the tensors (row (q,k), columns (b,p'')) ...
@@ -263,7 +286,7 @@ static int left_step(Ctx &c, int mu)
         const ChainSumArgs ca = c.keep_t ? ChainSumArgs{cs, c.Tp0(0, mu), inter ? sp : (int64_t)c.szT[mu], inter ? (int64_t)nb * sp : sp,
                                                         (int64_t)nb * (int64_t)c.szT[mu]}
                                          : ChainSumArgs{cs, nullptr, 0, 0, 0};
-        CK(chain_step_try(3, ca, c.aux, c.st_aux));
+        CK(chain_step_try(3, ca, c.aux, c.st_aux, c.cus.left));
         if (rc == 2 && inter) c.t_inter[mu] = 1;
         if (rc) return TTSK_OK;
     }
@@ -316,10 +339,29 @@ static int left_step(Ctx &c, int mu)
 // host to have queued the other: 335 -> 319 us for one C3 tensor).  (Starting Psi_mu / Omega_mu on a third stream as
 // soon as left step mu and right step d-2-mu are done was measured too: 325 us eager, 377 us replayed from a hipGraph,
 // slower for 6-8 tensors -- the early products compete with the chain steps for the CUs.  Not kept.)
+// The CU budgets (sketch_split.h) are asked here once per call: the right steps, the left steps and the Psi products of the
+// tails all plan for them.
 static int run_chains(Ctx &c, bool left)
 {
     const char *single = getenv("TTSK_SINGLE_STREAM");
     c.aux = (single && single[0] == '1') ? c.stream : (c.stream + 1) % TTSK_NUM_STREAMS;
+    const int n_cu = device_num_cu();
+    if (n_cu < 1) return TTSK_ERR_HIP;
+    bool fused = true;
+    for (int mu = 1; mu < c.d - 1 && fused; ++mu) {
+        const int j = c.d - 1 - mu;
+        fused = step_on_fused(c.s[mu + 1], c.s[mu], c.rt[j], c.rt[j + 1]) && (!left || step_on_fused(c.s[mu], c.s[mu + 1], c.lt[mu], c.lt[mu + 1]));
+    }
+    const int set[3] = {split_set[0].load(), split_set[1].load(), split_set[2].load()};
+    // A caller that queues its sketches on one stream pair has one step in flight, and a split only lengthens that step
+    // (sketch_split.h); one that keeps several in flight hands consecutive calls to different stream pairs -- that is what
+    // the stream argument is for -- and is known by it: the call before this one went to another stream.
+    const int before = last_sketch_stream.exchange(c.stream);
+    const bool pipelined = before >= 0 && before != c.stream;
+    // (the chains-only calls of tt_orth.hip, T not kept, were not measured with budgets: the whole device)
+    if (c.keep_t)
+        c.cus = sketch_split_resolve(SketchSplitIn{n_cu, c.nb, c.d, c.n, c.s, c.lt, c.rt, left && c.aux != c.stream, pipelined,
+                                                   fused ? SKETCH_FUSED : SKETCH_OTHER}, set);
     if (!(c.st_aux = stream_of(c.aux))) return TTSK_ERR_ARG;
     if (!(c.ws0 = (double *)scratch(c.stream, SCRATCH_DRIVER, c.bytes))) return TTSK_ERR_HIP;
     int rc;
@@ -359,7 +401,7 @@ static int psi_sum_one_product(const Ctx &c, int mu, int q)
                 p.C[cidx] = nch == 1 ? psi : blk0 + (size_t)cidx * c.szPs;
             }
             const StreamSmallArgs ss{nch, 0 /* J: psi_stream */, (int)Kc, (int)r, p.A, ldt, p.B, ldr, p.C, r, nch == 1 ? c.accumulate : 0};
-            CK(psi_stream(stream_small_try, ss, l * nn, q, stream_of(q)));
+            CK(psi_stream(stream_small_try, ss, l * nn, q, stream_of(q), c.cus.psi));
             if (rc == 1) return nch > 1 ? ttsk_sum_slices(psi, blk0, nch, c.szPs, (size_t)(l * nn * r), c.accumulate, q) : TTSK_OK;
         }
     }
@@ -404,7 +446,7 @@ static int psi_omega(const Ctx &c, int mu, int q, bool do_psi, bool do_omega)
                 TTSK_HIP(hipMemset2DAsync(c.Tp0(0, mu) + t_len, c.szT[mu] * 8, 0, 8, (size_t)nb, stq));
             const StreamSmallSumArgs sa{nb, 0 /* J: psi_stream */, (int)sp, (int)r, c.Tslice(0, mu), ldt, (int64_t)c.szT[mu],
                                         c.Rslice(0, jr), ldr, (int64_t)c.szR[jr], c.out + c.psi_at[mu], r, c.accumulate};
-            CK(psi_stream(stream_small_sum_try, sa, l * nn, q, stq));
+            CK(psi_stream(stream_small_sum_try, sa, l * nn, q, stq, c.cus.psi));
         }
         if (rc == 0) {
             // Psi[q,k,c] = sum_{p'} T[q,k,p'] R[p',c]   (M=(q,k), N=c, K=p') per tensor; of a sum into the workspace,
@@ -415,7 +457,7 @@ static int psi_omega(const Ctx &c, int mu, int q, bool do_psi, bool do_omega)
             }
             const int acc = c.sum ? 0 : c.accumulate;
             const StreamSmallArgs ss{nb, 0 /* J: psi_stream */, (int)sp, (int)r, p.A, ldt, p.B, ldr, p.C, r, acc};
-            CK(psi_stream(stream_small_try, ss, l * nn, q, stq));
+            CK(psi_stream(stream_small_try, ss, l * nn, q, stq, c.cus.psi));
             if (rc == 0) CK(gemm_batch(4, nb, gemm_desc2(l * nn, r, 1, sp, ldt, 0, 1, 0, ldr, 1, r, 1, acc), p, q, stq));
             if (c.sum) CK(ttsk_sum_slices(c.out + c.psi_at[mu], blk0, nb, c.szPs, (size_t)(l * nn * r), c.accumulate, q));
         }
@@ -458,7 +500,7 @@ static int tail_grouped(const Ctx &c, bool ends_early)
             p.A[cnt] = c.Tslice(b, mu); p.B[cnt] = c.Rslice(b, d - 2 - mu); p.C[cnt] = c.outb(b) + c.psi_at[mu];
         }
     const StreamSmallArgs ss{cnt, 0 /* J: psi_stream */, (int)sp, (int)r, p.A, c.t_ld(1), p.B, ldr, p.C, r, c.accumulate};
-    CK(psi_stream(stream_small_try, ss, l * nn, c.stream, c.st));
+    CK(psi_stream(stream_small_try, ss, l * nn, c.stream, c.st, c.cus.psi));
     if (rc == 0) return 0;                 // shape outside the streamed kernel's cover: mode by mode
     BatchPtrs o{};
     cnt = 0;
@@ -516,7 +558,7 @@ static int tail_sum(const Ctx &c, bool &om_batched, bool &psi_batched)
         }
     }
     const StreamSmallArgs ss{cnt, 0 /* J: psi_stream */, (int)Kc, (int)r, p.A, ldt, p.B, ldr, p.C, r, 0};
-    CK(psi_stream(stream_small_try, ss, l * nn, c.stream, c.st));
+    CK(psi_stream(stream_small_try, ss, l * nn, c.stream, c.st, c.cus.psi));
     if (rc == 0) return TTSK_OK;
     psi_batched = true;
     CK(ttsk_stream_wait(c.aux, c.stream));
@@ -536,6 +578,14 @@ int64_t ttsk_tt_sketch_size(int d, const int64_t *n, const int64_t *l_lo, const 
                             const int64_t *r_lo, const int64_t *r_hi)
 {
     return sketch_offsets(d, n, l_lo, l_hi, r_lo, r_hi);
+}
+
+int ttsk_tt_sketch_split(int right_cus, int left_cus, int psi_cus)
+{
+    TTSK_ARG(right_cus >= -1 && left_cus >= -1 && psi_cus >= -1, "ttsk_tt_sketch_split: budgets (%d, %d, %d) must be >= -1", right_cus,
+             left_cus, psi_cus);
+    split_set[0] = right_cus; split_set[1] = left_cus; split_set[2] = psi_cus;
+    return TTSK_OK;
 }
 
 int ttsk_tt_sketch(int d, const int64_t *n, const int64_t *s, const int64_t *lt, const int64_t *l_lo,
