@@ -291,6 +291,15 @@ int ttsk_fill_normal_many(int count, double *const *dev_outs, const size_t *ns, 
 int ttsk_sparse_ttdrm_step(const double *dev_vin, int64_t rho, const double *dev_core,
                            int64_t n, int64_t rhop, const int64_t *dev_idx_row, size_t N,
                            double *dev_vout, int stream);
+/* ---- Khatri-Rao DRM (csrc/khatri_rao.hip): every step is an elementwise product of rows of width w ----
+ * the rows of all prefixes of one level from the level before:
+ *   out[i * P + p, c] = prev[p, c] * g[i, c],  prev (P, w) or NULL (P = 1, ones), g (n, w), out (n * P, w) row-major
+ * (the row order of the sparse pass's tables: the first mode the fastest digit; the caller allocates one spare row) */
+int ttsk_kr_rows(const double *dev_prev, int64_t P, const double *dev_g, int64_t n, int64_t w, double *dev_out, int stream);
+/* one step of the panels: out[e, c] = (v ? v[e, c] : 1) * g[idx ? idx[e] : e, c], v and out (N, w), g (n, w) row-major;
+ * out may be v; without idx N <= n; an index outside [0, n) is clamped */
+int ttsk_kr_step(const double *dev_v, const double *dev_g, int64_t n, int64_t w, const int64_t *dev_idx, size_t N,
+                 double *dev_out, int stream);
 /* DenseGaussianDRM.sketch_sparse (dense_gaussian_drm.py:59-66): C-order ravel of the
  * first m index rows, then column gather of mat (rank, cols): out (N, rank) row-major */
 int ttsk_sparse_densedrm_gather(const double *dev_mat, int64_t rank, int64_t cols,
@@ -626,7 +635,13 @@ int ttsk_sparse_mode_stream_u32(const int64_t *dev_idx, int64_t row_stride, cons
  * front of core[0] (`rows` rows of rank[0] doubles and one spare row), or, with table == NULL, the vector (1): rank[0] = 1,
  * core[0] is the DRM's first core.  steps = 0 with a table copies columns [rank_min, rank_min + w) of the start row.  Ranks
  * <= 32, steps <= TTSK_SG_CHAIN_MAX, rows and every n[s] below 2^31; the 32-bit entry point only (the digits of a flat index
- * that wrapped are not those of the record).  seed, full and nnz are not read. */
+ * that wrapped are not those of the record).  seed, full and nnz are not read.
+ *
+ * kind 5 = a row of a Khatri-Rao DRM, formed in the pass: a kind-4 chain whose steps are diagonal, with the same descriptor,
+ *     row(e)[b] = t(e)[rank_min + b] core[0][i_0(e), rank_min + b] ... core[steps - 1][i_{steps-1}(e), rank_min + b],  b < w,
+ * the products taken in this order, one rounding each.  core[s] is a contiguous (n[s], rho) device array and every rank[s]
+ * is rho <= 32.  The start: t(e) = table[row(e)][0 : rho] (`rows` rows of rho doubles and one spare row), or, with
+ * table == NULL, the vector of rho ones.  The digits, steps = 0, the limits and the 32-bit entry point are those of kind 4. */
 #define TTSK_SG_CHAIN_MAX 8
 typedef struct {
     int steps;
@@ -640,7 +655,7 @@ typedef struct {
     uint64_t mul, seed;
     const double *table;
     int full, nnz;          /* kind 3 only: length of the whole sign row, its +-1 entries (sparse_sign_drm.py:34-51) */
-    const ttsk_sg_chain *chain;      /* kind 4 only (host memory, read during the call); not read for any other kind */
+    const ttsk_sg_chain *chain;      /* kinds 4 and 5 only (host memory, read during the call); not read for any other kind */
 } ttsk_sg_factor;
 /* Psi[a, j, c] (+)= sum_{e: j_e = j} val_e A[e, a] B[e, c]   (dev_psi (wA, n, wB), zero-initialised by the caller)
  * and, with C != NULL, Omega += sum_e val_e C[e, a] B[e, c] (c_left) or sum_e val_e A[e, a] C[e, c]  (dev_omega,

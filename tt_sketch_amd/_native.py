@@ -117,6 +117,8 @@ ENTRY_POINTS = {
     "ttsk_fill_normal": Entry([P, S, U64, c_double, I], QUEUE),
     "ttsk_fill_normal_many": Entry([I, POINTER(P), POINTER(S), POINTER(U64), POINTER(c_double), I], QUEUE),
     "ttsk_sparse_ttdrm_step": Entry([P, I64, P, I64, I64, P, S, P, I], QUEUE),
+    "ttsk_kr_rows": Entry([P, I64, P, I64, I64, P, I], QUEUE),
+    "ttsk_kr_step": Entry([P, P, I64, I64, P, S, P, I], QUEUE),
     "ttsk_sparse_densedrm_gather": Entry([P, I64, I64, P, I64, POINTER(I), POINTER(I64), I, S, P, I], QUEUE),
     "ttsk_sparse_psi": Entry([P, P, P, S, P, I64, P, I64, I64, P, I], QUEUE),
     "ttsk_tt_gather": Entry([POINTER(P), POINTER(I64), POINTER(I64), I, P, I64, POINTER(I), S, P, P, P, I], QUEUE),

@@ -12,7 +12,8 @@ namespace ttsk {
 
 struct SgF {
     int kind;            // 0: ones (width 1), 1: table gathered by flat index, 2: normals sampled in the pass, 3: sign rows sampled in the pass,
-                         // 4: rows of a tensor-train DRM formed in the pass (SgPass::ch; `table`, `units`, `rcp`: its start rows)
+                         // 4: rows of a tensor-train DRM formed in the pass (SgPass::ch; `table`, `units`, `rcp`: its start rows), and,
+                         //    with SgPlanCh::diag, of a Khatri-Rao DRM (kind 5 of ttsk_sg_factor, restated by sg_plan)
     int w;               // columns of the factor (<= 16 NT)
     int rank_min;
     int src;             // flat index: 0 = prefix, 1 = suffix, 2 = prefix + j * mul, 3 = suffix + j * mul
@@ -427,11 +428,57 @@ template <int NT, int NS, int T, bool CH> struct SgWave {
         }
     }
 
+    // (2b') the rows of a Khatri-Rao DRM (kind 5 of ttsk_sg_factor; SgPlanCh::diag): the chain above with diagonal steps.  A
+    // column of a nonzero's row depends on no other column, so the T * w (nonzero, column) pairs of the tile are dealt over
+    // the 64 lanes, U per lane at a time (their gathers of a step are in flight together), and each is carried in a register
+    // from the start row to the tile: no running vectors in LDS, no exchange between lanes; a step gathers one entry of an
+    // (n[s], rank) table through L2.  Every step is fma(v, g, +0.0): one
+    // rounding, and the bits a kind-4 step gives on the diagonal core of the same table (its other terms are zeros added to
+    // a sum that starts at +0.0).
+    __device__ __forceinline__ void diag_factor(int f)
+    {
+        const SgF &F = a.f[f];
+        const SgPlanCh &c = a.ch[f];
+        const int rho = c.rank[0];
+        const uint32_t *dg = cd + c.doff * T;
+        wave_lds_sync();                                        // the digits, written by the lanes of their nonzeros
+        constexpr int U = 4;                                    // pairs a lane carries at a time: their gathers of a step travel together
+        const int items = T * F.w;
+#pragma unroll 1
+        for (int i0 = lane; i0 < items; i0 += 64 * U) {
+            int e[U], col[U];
+            double v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = i0 + 64 * u < items ? i0 + 64 * u : items - 1;      // (beyond the tile: the last pair once more, not stored)
+                e[u] = i / F.w;
+                col[u] = c.lo + i - e[u] * F.w;
+                v[u] = c.has_table ? tabs[c.toff + e[u] * 2 * F.units + col[u]] : 1.0;
+            }
+#pragma unroll 1
+            for (int s = 0; s < c.steps; ++s) {
+                const double *cs = a.core[f][s];
+                double g[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) g[u] = cs[(int64_t)dg[s * T + e[u]] * rho + col[u]];
+#pragma unroll
+                for (int u = 0; u < U; ++u) v[u] = fma(v[u], g[u], 0.0);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (i0 + 64 * u < items) tile[e[u] * a.tcols + a.off[f] + col[u] - c.lo] = v[u];
+        }
+        wave_lds_sync();                                        // the rows, read by the lanes of the products
+    }
+
     __device__ __forceinline__ void chain()
     {
 #pragma unroll 1
         for (int f = 0; f < 3; ++f)
-            if (a.f[f].kind == 4) chain_factor(f);
+            if (a.f[f].kind == 4) {
+                if (a.ch[f].diag) diag_factor(f);
+                else chain_factor(f);
+            }
     }
 
     // store the finished slice k: the wave's first slice and (final) its last one go to the partial blocks

@@ -78,7 +78,7 @@ inline SgDiv sg_div_make(uint64_t d)
 }
 SG_HD inline uint32_t sg_div(uint32_t x, SgDiv v) { return (uint32_t)(((uint64_t)x * v.mul) >> v.sh); }
 
-// a chain factor (kind 4 of ttsk_sg_factor) as the kernel walks it
+// a chain factor (kinds 4 and 5 of ttsk_sg_factor) as the kernel walks it
 struct SgPlanCh {
     int steps, has_table;
     int lo;                           // first column of the last rank the factor keeps
@@ -88,6 +88,7 @@ struct SgPlanCh {
     uint32_t rows, n[SG_CHAIN_MAX];   // divisors of the flat index, in the order they are taken
     SgDiv drows, dn[SG_CHAIN_MAX];
     int rank[SG_CHAIN_MAX + 1];
+    int diag;                         // kind 5: the steps are diagonal, core[s] an (n[s], rank) table; everything above as for kind 4
 };
 
 // the digits of `flat`: the row of the start table (0 without one), then the index into each core; `j` is the last digit
@@ -152,7 +153,11 @@ inline int sg_plan_chain(const ttsk_sg_factor *f, int i, int w32, SgPlan *p)
             PLAN_FAIL(TTSK_ERR_UNSUPPORTED, "ttsk_sparse_gauss_pass: factor %d: chain rank %d is %d, up to %d are covered", i, s, c.rank[s], SG_CHAIN_RANK);
         if (c.rank[s] > widest) widest = c.rank[s];
     }
-    if (!c.has_table && c.rank[0] != 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain from the first core with rank %d in front of it", i, c.rank[0]);
+    if (c.diag) {                                  // one rank throughout; without a table the start is that many ones
+        for (int s = 1; s <= c.steps; ++s)
+            if (c.rank[s] != c.rank[0])
+                PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: a diagonal chain of ranks %d and %d, it has one rank throughout", i, c.rank[0], c.rank[s]);
+    } else if (!c.has_table && c.rank[0] != 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain from the first core with rank %d in front of it", i, c.rank[0]);
     for (int s = 0; s < c.steps; ++s) {
         if (!ch->core[s]) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain core %d is NULL", i, s);
         if (ch->n[s] < 1) PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: chain mode %d has size %lld", i, s, (long long)ch->n[s]);
@@ -182,8 +187,12 @@ inline int sg_plan(const ttsk_sg_factor *A, const ttsk_sg_factor *B, const ttsk_
         F.kind = fs[i]->kind;
         if (F.kind) F.w = fs[i]->w;
         const int full = fs[i]->full, nnz = fs[i]->nnz, lo = fs[i]->rank_min;
-        if (!(F.kind >= 0 && F.kind <= 4 && F.w >= 1 && F.w <= 32))
+        if (!(F.kind >= 0 && F.kind <= 5 && F.w >= 1 && F.w <= 32))
             PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: kind %d, width %d", i, F.kind, F.w);
+        if (F.kind == 5) {                             // a chain with diagonal steps: planned and walked as kind 4, but for the flag
+            F.kind = 4;
+            p->ch[i].diag = 1;
+        }
         if (F.kind == 3 && !(full >= 1 && full <= 32 && nnz >= 0 && nnz <= full && lo >= 0 && lo + F.w <= full))
             PLAN_FAIL(TTSK_ERR_ARG, "ttsk_sparse_gauss_pass: factor %d: sign row of %d entries, %d non-zero, columns [%d, %d)", i, full,
                       nnz, lo, lo + F.w);

@@ -44,12 +44,15 @@ def drm_pair(shape, left_drm, right_drm, *, kinds=(TensorTrainDRM,), need_left: 
     ``tt_fused.try_orth_sketch``              TensorTrainDRM  orthogonal  yes    no         no
     ``tt_fused.try_orth_sketch_batch``        TensorTrainDRM  orthogonal  yes    no         no
     ``sketch.stream_sketch_batch``            TensorTrainDRM  yes         no     yes        yes
-    ``sparse_fused.try_sparse_gauss_sketch``  hashed, train   yes         no     yes        yes
+    ``sparse_fused.try_sparse_gauss_sketch``  hashed, train,  yes         no     yes        yes
+                                              Khatri-Rao
     ========================================  ==============  ==========  =====  =========  ===============
 
     ``stream_sketch_batch`` leaves the count of cores to ``TTSketchPlan``.  The sparse path takes SparseGaussianDRM,
-    SparseSignDRM and TensorTrainDRM in any pairing: the hashed DRMs have no cores, so it asks for no count here and tests
-    the number of modes, and ``d - 1`` cores of a train, with its other limits."""
+    SparseSignDRM, TensorTrainDRM and KhatriRaoDRM in any pairing: the hashed DRMs have no cores, so it asks for no count
+    here and tests the number of modes, and ``d - 1`` cores of a train or matrices of a Khatri-Rao DRM, with its other
+    limits.  Every other caller declines a KhatriRaoDRM: its sketches of trains, CP and Tucker tensors run on the generic
+    driver."""
     # (plain tests, no generator expressions: this runs on every public sketch call)
     if type(right_drm) not in kinds or not right_drm.transpose:
         return False

@@ -12,6 +12,11 @@ A TensorTrainDRM's row is a row of a table of its partial products (``_Side._tt_
 rule allows) taken a few chain steps further inside the pass (kind 4 of ``ttsk_sg_factor``): the sums of
 ``TensorTrainDRM.sketch_sparse`` without its panels.  Pairs with a train are routed (``paths.resolve``; the rule is
 ``chain_route_ms``): "composed" declines, and the generic driver runs the panels.
+
+A KhatriRaoDRM's row is the elementwise product of one row per mode of its small matrices: a row of a table of those
+products (``_Side._kr_table``, built level by level with ``ttsk_kr_rows``) taken a few diagonal chain steps further inside
+the pass (kind 5 of ``ttsk_sg_factor``) -- no hash, no ``ndtri``, no rank x rank step.  Pairs of Khatri-Rao and hashed DRMs
+always take the passes; beside a train the route's rule decides, a Khatri-Rao step counted as its w multiply-adds.
 """
 from __future__ import annotations
 
@@ -24,6 +29,7 @@ import numpy as np
 from . import _native as nat
 from . import paths
 from .device import DevArray, axpby, contract, copy_into
+from .drm.khatri_rao_drm import KhatriRaoDRM
 from .drm.sparse_gaussian_drm import SparseGaussianDRM
 from .drm.sparse_sign_drm import SparseSignDRM
 from .drm.tensor_train_drm import TensorTrainDRM
@@ -40,7 +46,8 @@ CHAIN_MAX = 8                    # steps of a chain factor (TTSK_SG_CHAIN_MAX of
 
 
 class _Chain(ctypes.Structure):
-    """ttsk_sg_chain: the cores a kind-4 factor walks from its start table (or, with ``rows`` = 0, from the first core)"""
+    """ttsk_sg_chain: the cores a kind-4 factor walks from its start table (or, with ``rows`` = 0, from the first core); for
+    kind 5 the (n, w) tables of its diagonal steps, every rank w"""
     _fields_ = [("steps", ctypes.c_int), ("rows", ctypes.c_uint64), ("core", ctypes.c_void_p * CHAIN_MAX),
                 ("n", ctypes.c_int64 * CHAIN_MAX), ("rank", ctypes.c_int * (CHAIN_MAX + 1))]
 
@@ -68,6 +75,8 @@ class _Side:
         self.drm = drm
         self.sign = type(drm) is SparseSignDRM
         self.tt = type(drm) is TensorTrainDRM
+        self.kr = type(drm) is KhatriRaoDRM
+        self.chained = self.tt or self.kr                  # its deep levels are chain factors: 32-bit streams, routed beside a train
         self.shape = tuple(int(n) for n in shape)          # in the order the DRM walks the tensor
         self.nnz = nnz
         self.cache = drm.__dict__.setdefault("_sg_tables", {})
@@ -150,6 +159,49 @@ class _Side:
         f = _Factor(4, w, lo, src, 0, 0, tab.ptr if tab is not None else None, 0, 0, ctypes.pointer(ch))
         return f, (tab, devs, ch)
 
+    # ---- a Khatri-Rao DRM: tables of the rows of every prefix, per (level, columns), up to a start level; beyond, a chain
+    # of diagonal steps (kind 5) through column cuts of its matrices.  Table and chain multiply in the same order, mode by
+    # mode with one rounding each, so a row has the same bits wherever the table ends.
+    def _kr_use_table(self, j: int, w: int) -> bool:
+        P = self.prefixes(j)
+        return P < 2**31 and 2 * P <= self.nnz and P * w * 8 <= TABLE_BYTES
+
+    def _kr_start(self, k: int) -> int:
+        """``start_level`` for the columns of level k: the tables below it hold those columns"""
+        k0 = -1
+        while k0 < k and self._kr_use_table(k0 + 1, self.width(k)):
+            k0 += 1
+        return k0
+
+    def _kr_table(self, j: int, lo: int, hi: int) -> DevArray:
+        """T_j[flat, :] = G_0[i_0, lo:hi] * G_1[i_1, lo:hi] * ... * G_j[i_j, lo:hi] (left to right), flat as ``_tt_table``:
+        from T_{j-1} by one ``ttsk_kr_rows``; keyed by the matrices, which the entry holds"""
+        mats = tuple(self.drm.mats[:j + 1])
+        key = ("kr", j, self.shape[:j + 1], tuple(id(m) for m in mats), lo, hi)
+        if key not in self.cache:
+            G = self.drm.dev_cols(j, lo, hi)
+            out = DevArray.zeros((self.prefixes(j) + 1, hi - lo))           # (one spare row, as every table)
+            prev = self._kr_table(j - 1, lo, hi) if j else None
+            nat.call("ttsk_kr_rows", prev, self.prefixes(j - 1) if j else 1, G, self.shape[j], hi - lo, out, 0)
+            self.cache[key] = (out, mats)
+        return self.cache[key][0]
+
+    def _kr_factor(self, k: int, src: int, mul: int):
+        lo, hi, w = int(self.drm.rank_min[k]), int(self.drm.rank_max[k]), self.width(k)
+        k0 = self._kr_start(k)
+        if k0 == k:                                        # the level itself has a table: a plain table factor
+            tab = self._kr_table(k, lo, hi)
+            return _Factor(1, w, lo, src, mul, 0, tab.ptr, 0, 0), tab
+        tab = self._kr_table(k0, lo, hi) if k0 >= 0 else None
+        devs = [self.drm.dev_cols(j, lo, hi) for j in range(k0 + 1, k + 1)]
+        ch = _Chain()
+        ch.steps, ch.rows = k - k0, self.prefixes(k0) if k0 >= 0 else 0
+        ch.rank[0] = w
+        for s, G in enumerate(devs):
+            ch.core[s], ch.n[s], ch.rank[s + 1] = G.ptr, self.shape[k0 + 1 + s], w
+        f = _Factor(5, w, 0, src, 0, 0, tab.ptr if tab is not None else None, 0, 0, ctypes.pointer(ch))
+        return f, (tab, devs, ch)
+
     def table(self, k: int) -> DevArray:
         drm = self.drm
         key = (k, self.shape[:k + 1], int(drm.rank_min[k]), int(drm.rank_max[k]), int(drm.seed))
@@ -171,6 +223,8 @@ class _Side:
         """the factor of level k and what must outlive the pass that reads it"""
         if self.tt:
             return self._tt_factor(k, src, mul)
+        if self.kr:
+            return self._kr_factor(k, src, mul)
         tab = self.table(k) if self.use_table(k) else None
         kind = 1 if tab is not None else (3 if self.sign else 2)
         f = _Factor(kind, self.width(k), int(self.drm.rank_min[k]), src, mul, self.seed(k),
@@ -180,14 +234,20 @@ class _Side:
 
     def cost(self, k: int) -> int:
         """what making the factor in the pass costs per nonzero (for choosing the side an Omega rides on): sampled columns;
-        for a chain the multiply-adds of its steps, rank x rank each"""
+        for a chain the multiply-adds of its steps, rank x rank each; w each for the diagonal steps of a Khatri-Rao DRM"""
         if self.tt:
             rk = [1] + [self.full(j) for j in range(k + 1)]
             return sum(rk[j] * rk[j + 1] for j in range(self.start_level(k) + 1, k + 1))
+        if self.kr:
+            return self.width(k) * (k - self._kr_start(k))
         return 0 if self.use_table(k) else self.width(k)
 
     def route_work(self, k: int) -> int:
-        """``cost`` as the route's rule counts it: the steps through a core that does not stay in the L2 weigh more"""
+        """``cost`` as the route's rule counts it: the steps through a core that does not stay in the L2 weigh more.  A
+        Khatri-Rao step counts as its w multiply-adds -- by analogy with a train's step; nothing measured backs that count
+        (the constants of ``chain_route_ms`` were fitted to train pairs only)."""
+        if self.kr:
+            return self.cost(k)
         rk = [1] + [self.full(j) for j in range(k + 1)]
         return sum(rk[j] * rk[j + 1] * (ROUTE_BIG_CORE_WEIGHT if rk[j] * self.shape[j] * rk[j + 1] * 8 > ROUTE_BIG_CORE_BYTES else 1)
                    for j in range(self.start_level(k) + 1, k + 1))
@@ -202,6 +262,12 @@ class _Side:
             if any(tuple(int(x) for x in self.drm.cores[j].shape) != (rk[j], self.shape[j], rk[j + 1]) for j in range(k + 1)):
                 return False
             return k - self.start_level(k) <= CHAIN_MAX
+        if self.kr:                                       # a matrix per level, as the walk expects it, with the rows the level hands out
+            lo, hi = int(self.drm.rank_min[k]), int(self.drm.rank_max[k])
+            if any(tuple(int(x) for x in m.shape)[1:] != (self.shape[j],) or not 0 <= lo < hi <= int(m.shape[0])
+                   for j, m in enumerate(self.drm.mats[:k + 1])):
+                return False
+            return k - self._kr_start(k) <= CHAIN_MAX
         if self.sign and not self.use_table(k):
             return self.staged(k) <= MAX_WIDTH and 0 <= int(self.drm.nnz[k]) <= int(self.drm.true_rank[k])
         return True
@@ -283,10 +349,11 @@ def _riders(L: _Side, R: _Side, d: int) -> dict:
 def _route_inputs(L: _Side, R: _Side, rider: dict, d: int) -> Tuple[int, int, int]:
     """what ``chain_route_ms`` is asked with, per nonzero: the (weighted) multiply-adds of the chain steps over all passes; the
     panel columns of both DRMs over all levels; the multiply-adds of the panel path's steps, rank x rank per level of a train"""
-    work = sum(L.route_work(mu - 1) for mu in range(1, d) if L.tt) + sum(R.route_work(d - 2 - mu) for mu in range(d - 1) if R.tt)
-    work += sum(S.route_work(k) for S, k in ((L, k) if side == "left" else (R, d - 2 - k) for side, k in rider.values()) if S.tt)
+    work = sum(L.route_work(mu - 1) for mu in range(1, d) if L.chained) + sum(R.route_work(d - 2 - mu) for mu in range(d - 1) if R.chained)
+    work += sum(S.route_work(k) for S, k in ((L, k) if side == "left" else (R, d - 2 - k) for side, k in rider.values()) if S.chained)
     panels = sum(S.full(k) for S in (L, R) for k in range(d - 1))
     panel_fma = sum((S.full(k - 1) if k else 1) * S.full(k) for S in (L, R) if S.tt for k in range(d - 1))
+    panel_fma += sum(S.width(k) for S in (L, R) if S.kr for k in range(d - 1))      # (a Khatri-Rao panel step: w products)
     return work, panels, panel_fma
 
 
@@ -314,17 +381,22 @@ def try_sparse_gauss_sketch(tensor, left_drm, right_drm, method):
         return None
     if max(shape) > MAX_MODE:
         return None
-    if not drm_pair(shape, left_drm, right_drm, kinds=(SparseGaussianDRM, SparseSignDRM, TensorTrainDRM), cores=False):
+    if not drm_pair(shape, left_drm, right_drm, kinds=(SparseGaussianDRM, SparseSignDRM, TensorTrainDRM, KhatriRaoDRM), cores=False):
         return None
     L = _Side(left_drm, shape, N)
     R = _Side(right_drm, shape[::-1], N)          # factor nu of the right DRM = suffix of d - 1 - nu.. = R_mu with mu = d - 2 - nu
-    if any(S.tt and len(S.drm.cores) != d - 1 for S in (L, R)):
+    if any(S.tt and len(S.drm.cores) != d - 1 for S in (L, R)) or any(S.kr and len(S.drm.mats) != d - 1 for S in (L, R)):
         return None
-    if (L.tt or R.tt) and not all(_small_stream(shape, mu) for mu in range(d)):
+    if (L.chained or R.chained) and not all(_small_stream(shape, mu) for mu in range(d)):
         return None                               # a chain factor reads the digits of a flat index that did not wrap
     if any(not L.covered(k) or not R.covered(k) for k in range(d - 1)):
         return None
     rider = _riders(L, R, d)
+    if (L.kr or R.kr) and not (L.tt or R.tt):
+        # Khatri-Rao and hashed DRMs in any pairing take the passes, as pairs of hashed DRMs do; only a forced "composed"
+        # (tests, benchmarks) gives the pair to the panels of the generic driver
+        if paths.resolve(None) == "composed":
+            return None
     if L.tt or R.tt:
         # the route (pairs of two hashed DRMs have this path only): "composed" is the panels of TensorTrainDRM.sketch_sparse
         # and the atomics of ttsk_sparse_psi -- a decline, the generic driver runs them
@@ -363,7 +435,7 @@ def try_sparse_gauss_sketch(tensor, left_drm, right_drm, method):
         for f in (A, B, C):
             if f is not None and f.kind in (2, 3):
                 sampled += f.w
-            if f is not None and f.kind == 4:
+            if f is not None and f.kind in (4, 5):
                 chain_steps += f.chain.contents.steps
         ref = lambda f: None if f is None else ctypes.byref(f)
         nat.call("ttsk_sparse_gauss_pass_u32" if small else "ttsk_sparse_gauss_pass", fl, fr, jj, vv, N, int(shape[mu]),
