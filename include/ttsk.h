@@ -284,6 +284,18 @@ int ttsk_fill_normal(double *dev_out, size_t n, uint64_t seed, double scale, int
  * give it (the d - 1 cores of a TensorTrainDRM, tensor.py:358-371: one launch instead of d - 1).  Host arrays. */
 int ttsk_fill_normal_many(int count, double *const *dev_outs, const size_t *ns, const uint64_t *seeds,
                           const double *scales, int stream);
+/* ---- products with a Gaussian matrix that is never stored (csrc/gauss_lazy.hip, plan in csrc/gauss_lazy_plan.h) ----
+ * G is the (row_hi x cols) array ttsk_fill_normal(seed, scale 1) writes, rows [row_lo, row_hi) of it: its entries are
+ * sampled where an fp64 MFMA GEMM consumes them, bit for bit the stored ones.  w = row_hi - row_lo.
+ *   left:  Z (w x Q, leading dimension ldz) = G[row_lo:row_hi, 0:cols] Xu,  Xu (cols x Q) row-major, leading dimension ldx
+ *   right: Out (rows x w, ldo) = S G[row_lo:row_hi, 0:cols]^T,             S (rows x cols) row-major, leading dimension lds
+ * Fixed order of summation, no atomics: the same bits on every call.  w = 0 or no columns / rows: nothing is done.
+ * TTSK_ERR_UNSUPPORTED (the caller fills the matrix and multiplies): w > 64, an extent of 2^31 or more, row_hi * cols
+ * beyond 2^63. */
+int ttsk_gauss_lazy_left(uint64_t seed, int64_t row_lo, int64_t row_hi, int64_t cols, const double *dev_xu, int64_t Q, int64_t ldx,
+                         double *dev_z, int64_t ldz, int stream);
+int ttsk_gauss_lazy_right(uint64_t seed, int64_t row_lo, int64_t row_hi, int64_t cols, const double *dev_s, int64_t rows, int64_t lds,
+                          double *dev_out, int64_t ldo, int stream);
 
 /* ---- sparse-input kernels --------------------------------------------------
  * TensorTrainDRM.sketch_sparse (tensor_train_drm.py:60-69): per nonzero e,

@@ -5,7 +5,7 @@ Python host code with the reference's module layout and API (``sketch``, ``sketc
 ``tt_svd``) over a C-ABI HIP library (``include/ttsk.h`` -> ``tt_sketch_amd/libttsk.so``).
 There is no CPU fallback: compute entry points raise if the library or a GPU is missing.
 """
-from .drm import ALL_DRM, DenseGaussianDRM, KhatriRaoDRM, SparseGaussianDRM, SparseSignDRM, TensorTrainDRM
+from .drm import ALL_DRM, DenseGaussianDRM, KhatriRaoDRM, LazyGaussianDRM, SparseGaussianDRM, SparseSignDRM, TensorTrainDRM
 from .hadamard_product import HadamardProduct, hadamard_round
 from .operator_product import OperatorProduct
 from .sketch import (SketchedTensorTrain, assemble_sketched_tt, blocked_stream_sketch, hmt_sketch,

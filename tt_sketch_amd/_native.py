@@ -116,6 +116,8 @@ ENTRY_POINTS = {
     "ttsk_sparse_sign_table": Entry([POINTER(U64), I, I, I, I, I, U64, P, I], QUEUE),
     "ttsk_fill_normal": Entry([P, S, U64, c_double, I], QUEUE),
     "ttsk_fill_normal_many": Entry([I, POINTER(P), POINTER(S), POINTER(U64), POINTER(c_double), I], QUEUE),
+    "ttsk_gauss_lazy_left": Entry([U64, I64, I64, I64, P, I64, I64, P, I64, I], QUEUE),
+    "ttsk_gauss_lazy_right": Entry([U64, I64, I64, I64, P, I64, I64, P, I64, I], QUEUE),
     "ttsk_sparse_ttdrm_step": Entry([P, I64, P, I64, I64, P, S, P, I], QUEUE),
     "ttsk_kr_rows": Entry([P, I64, P, I64, I64, P, I], QUEUE),
     "ttsk_kr_step": Entry([P, P, I64, I64, P, S, P, I], QUEUE),

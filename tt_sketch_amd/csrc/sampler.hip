@@ -39,29 +39,7 @@ __device__ __forceinline__ void ndtri_block(bool live, double u, size_t g, doubl
     __syncthreads();
 }
 
-// The same split for a whole LDS tile of samples: the producer loop stores scale * ndtri(u) for central
-// samples and parks the tail samples' u in their slot, queueing the slot number; after ONE barrier the
-// queue is drained by all threads, full waves of tail code.  (ndtri_block above pays three barriers per
-// 256 samples, i.e. per column of a row tile.)
-__device__ __forceinline__ void tile_sample(double u, int slot, double scale, double *tile, unsigned short *q, int *qn)
-{
-    if (nd_central(u)) {
-        tile[slot] = scale * ndtri_dev(u);
-    } else {
-        tile[slot] = u;
-        q[atomicAdd(qn, 1)] = (unsigned short)slot;
-    }
-}
-__device__ __forceinline__ void tile_drain(double scale, double *tile, const unsigned short *q, const int *qn)
-{
-    __syncthreads();
-    const int n = *qn;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int slot = q[i];
-        tile[slot] = scale * ndtri_dev(tile[slot]);
-    }
-    __syncthreads();
-}
+// (tile_sample / tile_drain, the same split for a whole LDS tile of samples: sampler_dev.h)
 
 __global__ void hash_kernel(uint64_t *v, size_t n)
 {

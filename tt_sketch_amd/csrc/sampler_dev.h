@@ -230,5 +230,28 @@ __device__ inline double ndtri_dev(double y0)
     return ndtri_tail_dev(y0);
 }
 
+// The central / tail split for a whole LDS tile of samples (sampler.hip's fills, gauss_lazy.hip): the producer loop stores scale * ndtri(u) for central
+// samples and parks the tail samples' u in their slot, queueing the slot number; after ONE barrier the
+// queue is drained by all threads, full waves of tail code.  (ndtri_block of sampler.hip pays three barriers per
+// 256 samples, i.e. per column of a row tile.)
+__device__ __forceinline__ void tile_sample(double u, int slot, double scale, double *tile, unsigned short *q, int *qn)
+{
+    if (nd_central(u)) {
+        tile[slot] = scale * ndtri_dev(u);
+    } else {
+        tile[slot] = u;
+        q[atomicAdd(qn, 1)] = (unsigned short)slot;
+    }
+}
+__device__ __forceinline__ void tile_drain(double scale, double *tile, const unsigned short *q, const int *qn)
+{
+    __syncthreads();
+    const int n = *qn;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int slot = q[i];
+        tile[slot] = scale * ndtri_dev(tile[slot]);
+    }
+    __syncthreads();
+}
 
 }  // namespace ttsk

@@ -381,9 +381,12 @@ def copy_into(dst: DevArray, src: DevArray, stream=0):
 
 
 def as_dev(x, stream=0) -> DevArray:
-    """DevArray as is; NumPy arrays (e.g. from a user-defined DRM) are uploaded."""
+    """DevArray as is; an object that forms its matrix on the device (``__dev_array__``, the counterpart of
+    ``__array__``: ``LazyGaussian``) as that matrix; NumPy arrays (e.g. from a user-defined DRM) are uploaded."""
     if isinstance(x, DevArray):
         return x
+    if hasattr(x, "__dev_array__"):
+        return x.__dev_array__()
     return DevArray.from_host(np.asarray(x, dtype=np.float64), stream=stream)
 
 

@@ -15,12 +15,18 @@ covers the shape (``_first_pass``), from two otherwise; Z_1 and Psi_1 read Z_0 (
 where Z_0 is large, twice otherwise; no
 matrix larger than n^{d-2} x rho exists; same numbers as the reference up to the order of summation
 (tests: golden fixtures at 1e-12, C2 at full size).
+
+``DenseGaussianDRM(stored=False)`` hands out recipes of another kind (``LazyGaussian``: seed, row range, row length).  They
+take the generic formulas above -- the same matrices, so the same choices -- with the two products computed by
+``ttsk_gauss_lazy_left`` / ``ttsk_gauss_lazy_right``, which sample the entries of the matrix where they are multiplied; a shape
+outside the kernels' cover fills the matrix for the duration of the one product and takes ``contract``.
 """
 import os
 
 import numpy as np
 
 from ..device import DevArray, as_dev, contract
+from ..drm.dense_gaussian_drm import LazyGaussian
 
 _shared = {}     # key -> (objects the key's ids refer to ..., product); cleared by general_sketch_device
 _perm_cache = {}  # (buffer of a DRM matrix A_3, view) -> (that buffer, its transposed copy for ttsk_dense_left_pass)
@@ -68,10 +74,11 @@ def _unfold(X, k):
 
 def _norm(x):
     """None and recipes as they are; anything else as a device matrix."""
-    return x if x is None or isinstance(x, ChainedUnfolding) else as_dev(x)
+    return x if x is None or isinstance(x, (ChainedUnfolding, LazyGaussian)) else as_dev(x)
 
 
-def _mat(x) -> DevArray:
+def _mat(x):
+    """a chained recipe as its matrix; a lazy Gaussian stays a recipe (``_left_product`` / ``_right_product`` take it)"""
     return x.materialise() if isinstance(x, ChainedUnfolding) else x
 
 
@@ -79,6 +86,8 @@ def _ident(x):
     """What identifies a sketching matrix for the lifetime of one general_sketch."""
     if x is None or isinstance(x, ChainedUnfolding):
         return id(x)
+    if isinstance(x, LazyGaussian):
+        return ("lazy", x.seed, x.row_lo, x.row_hi, x.cols)
     return (id(x.buf), x.offset, x.shape, x.strides)
 
 
@@ -89,6 +98,8 @@ def prepare_left(tensor, left_contractions) -> bool:
     from .. import _native as nat
     if os.environ.get("TTSK_DENSE_LEFT_PASS", "1") == "0":
         return False
+    if any(isinstance(x, LazyGaussian) for x in left_contractions):
+        return False                                         # recipes: nothing to transpose, nothing is filled for this pass
     X = tensor.dev_data()
     A = [_norm(x) for x in left_contractions]
     if X.ndim < 5 or len(A) < 4 or any(isinstance(a, ChainedUnfolding) or a is None for a in A[:4]) or not X.is_contiguous():
@@ -125,12 +136,54 @@ def prepare_left(tensor, left_contractions) -> bool:
     return True
 
 
+def _rows2d(S: DevArray):
+    """(S, its leading dimension) where S's rows are contiguous and apart; a contiguous copy otherwise"""
+    rows, cols = S.shape
+    if (cols == 1 or S.strides[1] == 1) and (rows == 1 or S.strides[0] >= cols):
+        return S, (S.strides[0] if rows > 1 else cols)
+    return S.contiguous(), cols
+
+
+def _lazy_left(A: LazyGaussian, Xu: DevArray) -> DevArray:
+    """G Xu for a recipe G (w, P) and Xu (P, Q): ``ttsk_gauss_lazy_left``; outside its cover the filled matrix and ``contract``"""
+    from .. import _native as nat
+    Xu, ldx = _rows2d(Xu)
+    w, P = A.shape
+    if Xu.shape[0] != P:
+        raise ValueError(f"a lazy Gaussian sketch of {P} columns against an unfolding of {Xu.shape[0]} rows")
+    Q = Xu.shape[1]
+    Z = DevArray.empty((w, Q))
+    try:
+        nat.call("ttsk_gauss_lazy_left", A.seed % 2 ** 64, A.row_lo, A.row_hi, P, Xu, Q, ldx, Z, Q, 0)
+    except nat.TtskUnsupported:
+        return contract("ip,pq->iq", A.materialise(), Xu)
+    return Z
+
+
+def _lazy_right(S: DevArray, B: LazyGaussian) -> DevArray:
+    """S G^T for S (rows, cols) and a recipe G (w, cols): ``ttsk_gauss_lazy_right``, or the filled matrix and ``contract``"""
+    from .. import _native as nat
+    S, lds = _rows2d(S)
+    w, cols = B.shape
+    if S.shape[1] != cols:
+        raise ValueError(f"a lazy Gaussian sketch of {cols} columns against {S.shape[1]}")
+    rows = S.shape[0]
+    out = DevArray.empty((rows, w))
+    try:
+        nat.call("ttsk_gauss_lazy_right", B.seed % 2 ** 64, B.row_lo, B.row_hi, cols, S, rows, lds, out, w, 0)
+    except nat.TtskUnsupported:
+        return contract("bq,mq->bm", S, B.materialise())
+    return out
+
+
 def _left_product(A, X, mu):
     """A X^{<mu+1>}, (l, prod n_{>mu}); A is the left sketch of modes 0..mu."""
     key = ("left", _ident(A), id(X.buf), X.offset, mu)
     hit = _shared.get(key)
     if hit is None:
-        if not isinstance(A, ChainedUnfolding):
+        if isinstance(A, LazyGaussian):
+            Z = _lazy_left(A, _unfold(X, mu + 1))
+        elif not isinstance(A, ChainedUnfolding):
             Z = contract("ip,pq->iq", A, _unfold(X, mu + 1))
         elif A.prev is None:
             Z = contract("kp,kq->pq", A.core[0], _unfold(X, 1))             # the one pass over X
@@ -167,6 +220,8 @@ def _right_product(S: DevArray, B) -> DevArray:
         if q * r > rows * rho:
             U = contract("qp,bqt->bpt", B.prev._rows(), S.reshape(rows, q, t))
             return contract("bpt,ptm->bm", U, B.core)
+    if isinstance(B, LazyGaussian):
+        return _lazy_right(S, B)
     return contract("bq,mq->bm", S, _mat(B))
 
 
@@ -248,6 +303,11 @@ def _psi0_generic(X, B) -> DevArray:
     return hit[2]
 
 
+def _apply_left(A, M: DevArray) -> DevArray:
+    """A M for a left sketching matrix A (l, p), stored or a lazy Gaussian, and a small matrix M (p, q)"""
+    return _lazy_left(A, M) if isinstance(A, LazyGaussian) else contract("ip,pj->ij", A, M)
+
+
 def sketch_omega_dense(left_sketch, right_sketch, *, tensor, mu: int, **kwargs):
     """Omega_mu = A_mu X^{<mu+1>} B_mu^T."""
     X = tensor.dev_data()
@@ -262,10 +322,10 @@ def sketch_omega_dense(left_sketch, right_sketch, *, tensor, mu: int, **kwargs):
         # Omega_0 = A_0 X^{<1>} B_0^T = A_0 Psi_0 (Psi_0 = X^{<1>} B_0^T, tensor_train... dense_sketch.py:29-36 with no left
         # sketch): Psi_0 has to read the tensor and B_0 anyway; Omega_0 from it is an (l x n_0) x (n_0 x r) product instead of
         # a pass over the first left product (2.7 GB at C2) and B_0 (5.4 GB) once more
-        return contract("ip,pj->ij", A, _psi0_generic(X, B))
+        return _apply_left(A, _psi0_generic(X, B))
     if A.shape[0] <= B.shape[0]:
         return _right_product(_left_product(A, X, mu), B)
-    return contract("ip,pj->ij", A, _right_product(_unfold(X, mu + 1), B))
+    return _apply_left(A, _right_product(_unfold(X, mu + 1), B))
 
 
 def sketch_psi_dense(left_sketch, right_sketch, *, tensor, mu: int, **kwargs):
@@ -286,4 +346,7 @@ def sketch_psi_dense(left_sketch, right_sketch, *, tensor, mu: int, **kwargs):
     if key in _shared or l * J * K * Lr + l * K * Lr * r <= J * K * Lr * r + l * J * K * r:
         T = _left_product(A, X, mu - 1)                          # shared with Omega_{mu-1}
         return _right_product(T.reshape(l * K, Lr), B).reshape(l, K, r)
-    return contract("ij,jkm->ikm", A, _right_product(X.reshape(J * K, Lr), B).reshape(J, K, r))
+    R = _right_product(X.reshape(J * K, Lr), B)
+    if isinstance(A, LazyGaussian):
+        return _lazy_left(A, R.reshape(J, K * r)).reshape(l, K, r)
+    return contract("ij,jkm->ikm", A, R.reshape(J, K, r))
