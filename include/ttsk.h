@@ -154,7 +154,16 @@ int ttsk_tt_sketch_sum(int nb, int d, const int64_t *n, const int64_t *s, const 
  * (more than the device has: the whole device; fewer than nb: one workgroup per tensor).  Process-wide until changed;
  * takes effect with the next call; queues nothing.  A budget changes
  * how many partial sums a result is added up from: sketches under different budgets agree to rounding, not bit for bit;
- * under one setting they are the same bits on every call.  For tests and measurements.  TTSK_ERR_ARG: a value below -1. */
+ * under one setting they are the same bits on every call.  For tests and measurements.  TTSK_ERR_ARG: a value below -1.
+ * The policy's one piece of history is process-wide too: the stream of the one-call sketch queued LAST by any thread (none
+ * before the first); ttsk_tt_orth_sketch and ttsk_tt_orth_sketch_batch count as such a sketch on every stream they run
+ * chains on (their chains go through the same driver, unbudgeted themselves).  A call counts as a pipelined caller's exactly when that stream is another one than its own, so under -1
+ * the grids, and with them the bits, of a batch of 8 tensors or more depend on where the call before it went and on nothing
+ * else: after a call on stream 2 the next call on stream 0 is split, the one after that on stream 0 is not.  A caller that
+ * needs the bits of a call alone on its stream makes one call on that stream first, or sets the budgets.  Whatever the
+ * history, the three calls may be queued on any library stream, adjacent ones included, with others in flight: a call's
+ * helper (stream + 1) mod TTSK_NUM_STREAMS is forked behind what its own stream holds and joined back, its workspace is its
+ * own stream's (tests/test_gpu_streams_in_flight.py). */
 int ttsk_tt_sketch_split(int right_cus, int left_cus, int psi_cus);
 /* One interior step of a TensorTrainDRM chain for nb tensors of one signature, both products in one launch
  * with the intermediate kept on chip (csrc/chain_fused.h):
@@ -755,7 +764,11 @@ int ttsk_tt_orth_sketch(int d, const int64_t *n, const int64_t *s, const int64_t
  * joined back into `stream`, a verdict per tensor.
  *   X, cores_out     count * d pointers, tensor-major;   omega_out   count * (d - 1) pointers (orthogonal)
  *   dev_status       count ints in device memory: 1 = a fast factorisation of that tensor was rejected (repeat it on the
- *                    robust path: ttsk_pinv / ttsk_qr_thin); read after ttsk_sync(stream) */
+ *                    robust path: ttsk_pinv / ttsk_qr_thin); read after ttsk_sync(stream)
+ * The verdicts come back in dev_status ALONE: whichever form ran, the deferred flag of every stream it used, `stream`
+ * included, is clear afterwards (ttsk_deferred_status reads 0 on all of them).  A flag that an earlier, unrelated call left on
+ * one of the OTHER streams is dropped; one left on `stream` itself counts against the batch's first tensor (the fused form:
+ * against all).  (ttsk_tt_orth_sketch, the single call, sets the flag of its own stream only: its helper carries none.) */
 int ttsk_tt_orth_sketch_batch(int count, int d, const int64_t *n, const int64_t *s, const int64_t *lt, const int64_t *rt,
                               const double *const *X, const double *const *DL, const double *const *DR,
                               double *const *cores_out, double *const *omega_out, int *dev_status, int stream);
@@ -780,8 +793,11 @@ int ttsk_pinv_batch(int count, const double *const *dev_omegas, int64_t l, int64
 /* assemble_sketched_tt (sketch.py:400-443) as one call: direction 0 ("right") C_mu = Psi_mu pinv(Omega_mu), mu < d - 1,
  * C_{d-1} = Psi_{d-1}; direction 1 ("left") C_0 = Psi_0, C_{mu+1} = pinv(Omega_mu) Psi_{mu+1}.  lr / rr: the d - 1 sketch
  * ranks; psi[mu] (lr[mu-1], n[mu], rr[mu]) contiguous; omega[mu] (lr[mu], rr[mu]); work[mu]: rr[mu] * lr[mu] doubles that
- * receive pinv(Omega_mu).  Pair mu runs on stream (stream + mu) mod TTSK_NUM_STREAMS with ttsk_pinv's robust fallback
- * queued behind the fast attempt (no read-back); all streams are joined into `stream` before the call returns. */
+ * receive pinv(Omega_mu).  Omega of one shape: the pseudo-inverses are batched launches on `stream`, and in direction 0 so
+ * are the products of the interior pairs whose mode size is n[1].  Every other pair mu runs on the helper stream
+ * (stream + 1 + mu) mod TTSK_NUM_STREAMS (pairs 8 apart share one; pair 7 is on `stream` itself) with ttsk_pinv's robust
+ * fallback queued behind the fast attempt (no read-back); every helper is forked behind `stream` when its first pair reaches
+ * it and joined into `stream` before the call returns. */
 int ttsk_tt_assemble(int d, const int64_t *n, const int64_t *lr, const int64_t *rr, const double *const *dev_psi,
                      const double *const *dev_omega, double *const *dev_cores_out, double *const *dev_work, int direction,
                      int stream);

@@ -416,9 +416,10 @@ int ttsk_tt_orth_sketch_batch(int count, int d, const int64_t *n, const int64_t 
 
 // assemble_sketched_tt (sketch.py:400-443) as ONE call: C_mu = Psi_mu pinv(Omega_mu) ("right", direction = 0) or
 // pinv(Omega_{mu-1}) Psi_mu ("left", direction = 1).  The d - 1 (pseudo-inverse, product) pairs are independent: pair k
-// runs on library stream k mod nstreams -- fast attempt, the Jacobi kernel queued behind it with the attempt's verdict
-// as its predicate (ttsk_pinv_begin / ttsk_pinv_end without a rank read-back), then the product -- and every stream is
-// joined into `stream` before the call returns.  No host synchronisation.
+// that is not part of a batched launch on `stream` runs on the helper stream (stream + 1 + k) mod TTSK_NUM_STREAMS (`qof`
+// below; pairs 8 apart share one, pair 7 is on `stream` itself) -- fast attempt, the Jacobi kernel queued behind it with
+// the attempt's verdict as its predicate (ttsk_pinv_begin / ttsk_pinv_end without a rank read-back), then the product --
+// and every helper that was forked is joined into `stream` before the call returns.  No host synchronisation.
 //   psi[mu]     (l_{mu-1}, n[mu], r_mu) contiguous, l_{-1} = r_{d-1} = 1;   omega[mu] (l_mu, r_mu), mu < d - 1
 //   cores_out   right: (l_{mu-1}, n, l_mu), last = psi[d-1];  left: (r_{mu-1}, n, r_mu), first = psi[0]
 //   work[k]     (r_k, l_k) doubles each: the pseudo-inverses (caller's, so that they outlive the call)
